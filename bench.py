@@ -22,6 +22,14 @@ and the per-shard top-k lists are exchanged over RCCL, each rank sequence-scores
 line also carries `scan_throughput` (db rows x query rows per second of scan-kernel time, max over ranks) and the
 event time of every collective of the exchange protocol.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the last step's outputs
+(--dump-outputs DIR) and print the line.  Every side figure -- per-kernel event times, roofline and live HBM traffic,
+the serial and HBM-resident loops, the other scaling mode, the fp16-storage and other-model legs, the batch curve, the
+single-query block, the seq_score seam, the CPU baseline and the CLI leg -- runs under --full only (their --no-* options
+still switch them off there); without --full their keys are null and `kernels` is empty.  --full also records the
+library's profiling events around every launch of the timed loop (a plain run leaves them off), so its `value` is not
+like for like with a plain run's: compare plain runs with plain runs.
 """
 import argparse
 import json
@@ -175,6 +183,29 @@ def cpu_baseline_leg(args, params, sd, shard, song_pos, q_pcm_mine, res, k, n_ro
     return cpu, par
 
 
+DUMP_DECISION_BYTES = 8 << 20        # --dump-outputs: at most 64 MB in all
+DUMP_FINGERPRINT_BYTES = 48 << 20
+
+
+def _seeded_rows(n, keep):
+    """all n rows, or a fixed seeded sample of `keep` of them (sorted): the same rows in every run of the same shapes"""
+    if keep >= n:
+        return slice(None)
+    return np.sort(np.random.default_rng(20240601).choice(n, size=keep, replace=False))
+
+
+def dump_outputs(path, res, emb):
+    """--dump-outputs: what the last timed step returned, as path/<name>.npy -- every field of the per-query decisions
+    as float64 (decision_song.npy, decision_offset.npy, ...) and the step's fingerprints as float32 (fingerprints.npy)"""
+    os.makedirs(path, exist_ok=True)
+    rows = _seeded_rows(len(res), DUMP_DECISION_BYTES // (8 * len(res.dtype.names)))
+    for name in res.dtype.names:
+        np.save(os.path.join(path, "decision_%s.npy" % name), np.asarray(res[name][rows], dtype=np.float64))
+    fp = emb.float().cpu().numpy()
+    rows = _seeded_rows(fp.shape[0], DUMP_FINGERPRINT_BYTES // (4 * fp.shape[1]))
+    np.save(os.path.join(path, "fingerprints.npy"), np.ascontiguousarray(fp[rows]))
+
+
 def self_launch(n, backend):
     """`python bench.py --gpus N` without a launcher: start N ranks of this very command (one per GPU, RCCL unless
     PFANN_DIST_BACKEND says otherwise) and return their exit status.  Fails before starting anything when the box does
@@ -237,9 +268,19 @@ def main():
                     help="run the sharded protocol (two-phase search, all-to-all, merge, all-gathers, device pick) even at "
                          "world 1: every collective then really goes through the backend (RCCL on one GPU)")
     ap.add_argument("--dump-decisions", default=None, help="write (song, offset, score) per query as .npy (rank 0)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (rank 0): every field of "
+                         "the per-query decisions (float64) and the fingerprints (float32; a fixed seeded sample of rows when "
+                         "they exceed 48 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every side figure (see the module docstring); off: only the headline's timed steps")
     args = ap.parse_args()
     if args.queries is None:
         args.queries = 4096 if args.scaling == "strong" else 512
+    if not args.full:
+        # the side legs all hang off these switches (the seq_score seam off --no-cpu-baseline, the batch curve and the
+        # single-query block off the profiling events); serial / hbm_resident / other_scaling_mode test args.full
+        args.no_prof = args.no_cpu_baseline = args.no_alt = args.no_cli = args.no_live_traffic = True
 
     # ------------------------------------------------------------------ ranks: launch, verify, never fall through
     # `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) starts its own N ranks, one per GPU, through
@@ -559,6 +600,8 @@ def main():
     elapsed = max_over_ranks(elapsed)
     n_seg = Q * QUERY_SEGS
     value = n_seg * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, emb)
     collectives = None
     my_collectives = {}
     if use_sharded and prof:
@@ -574,7 +617,7 @@ def main():
     # ---- the same K batches one at a time (H2D, kernels, D2H, host wait; then the next): what `value` was through round 3's
     # first half, kept for comparison
     serial = None
-    if two_deep is not None:
+    if two_deep is not None and args.full:
         fence()
         tp = time.perf_counter()
         for _ in range(args.steps):
@@ -587,7 +630,7 @@ def main():
 
     # ---- the same step with the query PCM already resident in HBM (reported beside `value`)
     pcie = None
-    if emu <= 1:
+    if emu <= 1 and args.full:
         step(False)
         fence()
         tp = time.perf_counter()
@@ -602,7 +645,7 @@ def main():
     # ---- N > 1, default (weak) mode: the same job in the OTHER scaling mode as a side figure, so SCALE runs stay
     # comparable with round 1's strong-scaling numbers: --queries queries for the WHOLE job, split over the ranks
     other_mode = None
-    if world > 1 and args.scaling == "strong" and emu <= 1 and Q // 8 >= 1:
+    if args.full and world > 1 and args.scaling == "strong" and emu <= 1 and Q // 8 >= 1:
         # the weak-scaling side figure: every rank brings Q/8 queries of its own (512 at the default 4096): equals the
         # headline job at N = 8 and is 1/8 ... 1/2 of it below
         per = min(Q // 8, Q // world)            # (every rank synthesised at least Q // world queries)
@@ -618,7 +661,7 @@ def main():
                       "ms_per_step": round(1e3 * el / args.steps, 3), "queries_per_step": sw["Q"],
                       "what": "weak scaling: %d queries per step and rank (%d per step for the job) against the same 1 M-segment "
                               "db" % (per, sw["Q"])}
-    elif world > 1 and args.scaling == "weak" and emu <= 1:
+    elif args.full and world > 1 and args.scaling == "weak" and emu <= 1:
         sw = make_workload([hi - lo for lo, hi in split_even(args.queries, world)])
         step(True, sw)
         fence()

@@ -35,7 +35,6 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 REF = "/root/reference"
 OUT = os.path.join(REPO, "tests", "golden")
 sys.path.insert(0, REPO)
-sys.path.insert(0, REF)
 
 from pfann_amd import synth  # noqa: E402
 
@@ -346,6 +345,7 @@ def gen_accuracy():
 
 
 if __name__ == "__main__":
+    sys.path.insert(0, REF)      # the generators import the reference's modules; the tests only use the input makers
     os.makedirs("logs", exist_ok=True)
     which = sys.argv[1:] or ["encoder", "segmenter", "database", "accuracy"]
     if "encoder" in which:

@@ -22,7 +22,8 @@ def _json(r):
 
 
 def test_plain_invocation_spawns_the_ranks_it_was_asked_for():
-    r = _run(["--gpus", "2", "--launch-check"], PFANN_DIST_BACKEND="gloo")
+    # PFANN_FORCE_DEVICE=0: on a box with one GPU both gloo ranks share it instead of rank 1 asking for a device 1
+    r = _run(["--gpus", "2", "--launch-check"], PFANN_DIST_BACKEND="gloo", PFANN_FORCE_DEVICE="0")
     assert r.returncode == 0, r.stderr[-3000:]
     out = _json(r)
     assert out["n_gpus"] == 2 and out["ranks_seen"] == 2 and out["backend"] == "gloo"

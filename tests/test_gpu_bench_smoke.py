@@ -13,7 +13,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract_small():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--queries", "16", "--db-songs", "400", "--cpu-queries", "4", "--cli-songs", "40", "--cli-queries", "8"],
+                        "--queries", "16", "--db-songs", "400", "--cpu-queries", "4", "--cli-songs", "40", "--cli-queries", "8", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -60,6 +60,44 @@ def test_bench_json_contract_small():
     assert bc[-1]["fraction_of_largest_group_rate"] == 1.0
 
 
+def test_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline of --steps timed steps and no side figure; --dump-outputs writes the
+    last step's decisions (every field, float64; the same as --dump-decisions) and fingerprints (float32), and a second run
+    with the same arguments writes bit-identical outputs."""
+    import numpy as np
+    common = ["--steps", "3", "--warmup", "1", "--db-songs", "400", "--queries", "16", "--max-batch", "512"]
+    dumps = []
+    for run in range(2):
+        out_dir, dec = tmp_path / ("out%d" % run), str(tmp_path / ("dec%d.npy" % run))
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + common +
+                           ["--dump-outputs", str(out_dir), "--dump-decisions", dec],
+                           capture_output=True, text=True, timeout=900, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "segments/s" and out["dtype"] == "f32"
+        assert out["higher_is_better"] is True and out["value"] > 0 and out["ms_per_step"] > 0
+        assert abs(out["value"] * out["ms_per_step"] / 1e3 - 16 * 19) < 0.01 * 16 * 19
+        for key in ("roofline", "single_query_scan_roofline", "cpu_baseline", "oracle_decision_parity", "serial", "hbm_resident",
+                    "seq_score_seam", "cli", "alt_modes", "batch_curve", "other_scaling_mode", "scan_throughput",
+                    "critical_path", "collectives"):
+            assert out[key] is None, key
+        assert out["kernels"] == {}
+        arrs = {f: np.load(str(out_dir / f)) for f in sorted(os.listdir(str(out_dir)))}
+        assert sorted(arrs) == ["decision_n_cand.npy", "decision_offset.npy", "decision_score.npy", "decision_shift.npy",
+                                "decision_song.npy", "fingerprints.npy"]
+        assert arrs["fingerprints.npy"].dtype == np.float32 and arrs["fingerprints.npy"].shape == (16 * 19, 128)
+        assert np.allclose(np.linalg.norm(arrs["fingerprints.npy"], axis=1), 1.0, atol=1e-5)
+        for f, a in arrs.items():
+            assert f == "fingerprints.npy" or (a.dtype == np.float64 and a.shape == (16,)), f
+        d = np.load(dec)
+        assert np.array_equal(d, np.stack([arrs["decision_song.npy"], arrs["decision_offset.npy"], arrs["decision_score.npy"]], 1))
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_live_traffic_of_the_conv_gemms_is_measured_under_rocprofv3(tmp_path):
     """bench.py's roofline.traffic leg (tools/live_traffic.py): two rocprofv3 --pmc passes of a child that pushes one launch
     group (9728 windows) through the encoder.  Every one of the 15 conv GEMM launches of both repetitions is
@@ -83,7 +121,7 @@ def test_two_deep_and_serial_loops_decide_alike(tmp_path):
     --serial runs them one at a time.  Same decisions either way, and the JSON says which loop ran."""
     import numpy as np
     common = ["--steps", "3", "--warmup", "1", "--db-songs", "600", "--queries", "24", "--no-cpu-baseline", "--no-cli",
-              "--no-alt", "--max-batch", "512"]
+              "--no-alt", "--max-batch", "512", "--full"]
     outs, lines = [], []
     for extra, name in ((["--serial"], "serial.npy"), ([], "deep.npy")):
         p = str(tmp_path / name)
@@ -132,7 +170,7 @@ def test_two_rank_default_is_the_same_job_strong_scaling_with_scan_throughput_an
     tools' own 2 ranks.  2 ranks on this box's one GPU (gloo-staged collectives)."""
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--queries", "48", "--db-songs", "600", "--max-batch", "512", "--cli-songs", "60",
-                        "--cli-queries", "12"],
+                        "--cli-queries", "12", "--full"],
                        capture_output=True, text=True, timeout=1200, cwd=REPO,
                        env=_clean_env(PFANN_DIST_BACKEND="gloo", PFANN_FORCE_DEVICE="0", PFANN_MAX_BATCH="512"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -226,7 +264,7 @@ def test_rccl_collectives_of_the_sharded_path_on_one_gpu(tmp_path):
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                             "--master-addr", "127.0.0.1", "--master-port", "29743", os.path.join(REPO, "bench.py"),
                             "--gpus", "1", "--force-sharded", "--steps", "3", "--warmup", "1", "--db-songs", "600", "--queries", "24",
-                            "--no-cpu-baseline", "--no-cli", "--no-alt", "--max-batch", "512", "--dump-decisions", path],
+                            "--no-cpu-baseline", "--no-cli", "--no-alt", "--max-batch", "512", "--full", "--dump-decisions", path],
                            capture_output=True, text=True, timeout=900, cwd=REPO,
                            env=_clean_env(MASTER_ADDR="127.0.0.1", PFANN_EXCHANGE_STREAM=flag))
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

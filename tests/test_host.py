@@ -592,7 +592,8 @@ def test_sharded_result_writer_equals_single_writer_gloo(tmp_path, world):
     script = tmp_path / "w.py"
     script.write_text(WRITER_WORKER)
     env = {k: v for k, v in os.environ.items() if k not in ("PFANN_GPUS", "PFANN_FORCE_SHARDED")}
-    env.update(MASTER_ADDR="127.0.0.1", PFANN_DIST_BACKEND="gloo", OMP_NUM_THREADS="1")
+    # PFANN_FORCE_DEVICE=0: on a box with one GPU every gloo rank shares it instead of rank 1 asking for a device 1
+    env.update(MASTER_ADDR="127.0.0.1", PFANN_DIST_BACKEND="gloo", OMP_NUM_THREADS="1", PFANN_FORCE_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
            "127.0.0.1", "--master-port", str(29300 + world + os.getpid() % 150), str(script), REPO, str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Compact view of a bench.py JSON line (stdin or file): headline, roofline, single-query block, per-kernel times."""
+"""Compact view of a bench.py JSON line (stdin or file): headline; roofline, single-query block and per-kernel times
+when the line comes from `bench.py --full`."""
 import json
 import sys
 

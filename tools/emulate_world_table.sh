@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/r4/emulate_world.txt}
 mkdir -p $(dirname $OUT)
 for n in 1 2 4 8; do
   if [ $n = 1 ]; then E="X=1"; else E="PFANN_EMULATE_WORLD=$n"; fi
-  env $E python bench.py --steps 4 --warmup 1 --serial --no-cli --no-cpu-baseline --no-alt 2>/dev/null | python -c "
+  env $E python bench.py --full --steps 4 --warmup 1 --serial --no-cli --no-cpu-baseline --no-alt 2>/dev/null | python -c "
 import json,sys
 b=json.loads([l for l in sys.stdin if l.startswith('{')][0])
 k=b['kernels']

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-layer table of the fused conv GEMM from a `PFANN_PROF_LAYERS=1 python bench.py ...` JSON line
+"""Per-layer table of the fused conv GEMM from a `PFANN_PROF_LAYERS=1 python bench.py --full ...` JSON line
 (the library then tags every launch with its layer shape):
     python tools/per_layer_table.py gpurun_out/per_layer.json > profiles/r2/per_layer.txt
 Columns: tile, rows per sample, M (= B * rows), N, K_live, us per launch, TFLOP/s, fraction of the fp32 MFMA peak,
