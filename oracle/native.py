@@ -1,4 +1,4 @@
-"""ctypes access to the C restatement (oracle/seqscore_c.c).  TEST INFRASTRUCTURE."""
+"""ctypes access to the C restatements (oracle/seqscore_c.c, oracle/exactdot_c.c).  TEST INFRASTRUCTURE."""
 import ctypes
 import os
 import subprocess
@@ -10,11 +10,31 @@ _SO = os.path.join(_HERE, "_build", "liboracle.so")
 _lib = None
 
 
+# source -> its own flags.  exactdot_c.c states one fp32 summation order bit for bit: no contraction of a*b+c into an
+# fma the source does not write, no fast-math reassociation (its fmaf calls are libm's correctly rounded ones)
+_SOURCES = {"seqscore_c.c": ["-O2"], "exactdot_c.c": ["-O2", "-ffp-contract=off", "-fno-fast-math"]}
+
+
 def build(force=False):
-    src = os.path.join(_HERE, "seqscore_c.c")
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
+    srcs = [os.path.join(_HERE, f) for f in _SOURCES]
+    if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["gcc", "-O2", "-fopenmp", "-shared", "-fPIC", src, "-lm", "-o", _SO])
+        # objects and the library are built under names of this process and the library moved into place at once:
+        # processes that build at the same time never see each other's half-written files
+        tag = ".%d" % os.getpid()
+        objs = []
+        try:
+            for f, flags in _SOURCES.items():
+                obj = os.path.join(os.path.dirname(_SO), f[:-2] + tag + ".o")
+                objs.append(obj)
+                subprocess.check_call(["gcc"] + flags + ["-fopenmp", "-fPIC", "-c", os.path.join(_HERE, f), "-o", obj])
+            tmp = _SO + tag + ".tmp"
+            subprocess.check_call(["gcc", "-fopenmp", "-shared"] + objs + ["-lm", "-o", tmp])
+            os.replace(tmp, _SO)
+        finally:
+            for obj in objs:
+                if os.path.exists(obj):
+                    os.remove(obj)
     return _SO
 
 
@@ -29,6 +49,8 @@ def lib():
         _lib.oracle_flat_ip_topk.argtypes = [f32p, ctypes.c_int64, ctypes.c_int, f32p, ctypes.c_int,
                                              ctypes.c_int, f32p, i64p]
         _lib.oracle_flat_ip_topk.restype = None
+        _lib.oracle_canon_scores.argtypes = [f32p, f32p, ctypes.c_int, i64p, i64p, ctypes.c_int64, f32p]
+        _lib.oracle_canon_scores.restype = None
     return _lib
 
 
@@ -61,3 +83,19 @@ def flat_ip_topk(query, db, k):
     lib().oracle_flat_ip_topk(_p(db, ctypes.c_float), db.shape[0], d, _p(query, ctypes.c_float), nq, k,
                               _p(D, ctypes.c_float), _p(I, ctypes.c_int64))
     return D, I
+
+
+def canon_scores(query, db, qi, xi):
+    """float32[len(qi)]: the canonical fp32 score (oracle/exactdot_c.c) of each pair (query[qi[i]], db[xi[i]])."""
+    query = np.ascontiguousarray(query, np.float32)
+    db = np.ascontiguousarray(db, np.float32)
+    d = query.shape[1]
+    assert d % 4 == 0 and db.shape[1] == d
+    qi = np.ascontiguousarray(qi, np.int64).ravel()
+    xi = np.ascontiguousarray(xi, np.int64).ravel()
+    assert qi.shape == xi.shape
+    assert qi.size == 0 or (0 <= qi.min() and qi.max() < query.shape[0] and 0 <= xi.min() and xi.max() < db.shape[0])
+    out = np.empty(qi.size, np.float32)
+    lib().oracle_canon_scores(_p(query, ctypes.c_float), _p(db, ctypes.c_float), d, _p(qi, ctypes.c_int64),
+                              _p(xi, ctypes.c_int64), qi.size, _p(out, ctypes.c_float))
+    return out

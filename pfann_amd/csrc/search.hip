@@ -796,7 +796,7 @@ __global__ void fill_empty_kernel(float *D, int64_t *I, int64_t total) {
 }
 
 // ---- small batches (nq <= 32, d = 64 / 128): the HBM-bound streaming path ------------------------------
-//   n <= CAP            : one dense pass (every score kept) + select;
+//   n <= CAP            : one dense pass (every score kept) + select (fp32 rows with an fp16 copy: + canonical re-scoring);
 //   otherwise           : group-maximum pass over every R-th row (2048 groups) -> k-th best group maximum = tau
 //                         (radix select of 2048 values) -> full pass emitting scores >= tau into 32 sub-lists per
 //                         row (~R*k survivors) -> 256-thread radix select + rank sort.
@@ -835,6 +835,9 @@ static int search_small(const void *rows, int64_t n, int d, const void *qrows, i
             ProfScope ps("scan_topk", s, n * bytes_per_row);
             PF_SMALL(2, (unsigned)std::min<int64_t>(512, cdiv(n, 128)));
         }
+        // fp32 rows with an fp16 copy: the MFMA scores are a pre-filter, the select re-scores in the canonical order
+        // (search_f16.hip, launch_select_dense), so a row's score has the bits it has on every other re-scoring path
+        if (ELT == 4 && db32 != nullptr) return launch_select_dense(ws, nq, n, k, D, I, label_base, q32, db32, d, xnorm_max, s);
         return launch_select(ws, nq, k, 1, D, I, label_base, 1, s);
     }
     constexpr int GRID = 512, W = GRID * 4;            // persistent: 2 workgroups per CU; W groups in the sampled pass
@@ -920,7 +923,8 @@ int search_topk(const float *db, const void *dbh, float xnorm_max, int64_t n, in
         int rc;
         if (half_only) rc = search_small<2>(dbh, n, d, ws.qh, nq, k, D, I, label_base, q, nullptr, xnorm_max, ws, s);
         else if (small_pre) rc = search_small<2>(dbh, n, d, ws.qh, nq, k, D, I, label_base, q, db, xnorm_max, ws, s);
-        else rc = search_small<4>(db, n, d, q, nq, k, D, I, label_base, q, nullptr, xnorm_max, ws, s);
+        // (an fp32 shard of <= CAP rows with its fp16 copy: canonical scores, db32 = the rows themselves)
+        else rc = search_small<4>(db, n, d, q, nq, k, D, I, label_base, q, dbh != nullptr && n <= CAP ? db : nullptr, xnorm_max, ws, s);
         if (rc) return rc;
         if (n > CAP && folded_small_path(d)) return 0;         // the fallback ran inside search_small's last launch
         return launch_topk_fallback(ws, q, db, dbh, n, d, nq, k, D, I, label_base, s);

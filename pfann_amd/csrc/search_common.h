@@ -44,6 +44,38 @@ struct ScanParams {
 };
 
 
+// The canonical fp32 score of a row, computed by the four adjacent lanes 4 c .. 4 c + 3 of a candidate:
+//   canon_part: lane sub's fma chain, p_sub = fmaf(x[e + t], q[e + t], p_sub) over e = 4 sub, 4 sub + 16, ... < d, t = 0..3
+//   canon_sum:  (p0 + p1) + (p2 + p3), in every lane of the four
+// Every exact re-scoring site uses it (the select kernels of search_f16.hip, topk_fallback_body), so a row's fp32 score has
+// the same bits whichever kernel, shard split or batch produced it; oracle/exactdot_c.c states the same order in C.
+// T = float: the fp32 rows; T = _Float16: fp16-only storage (the fallback, where the s16 scores are the result).  xv and qv
+// are 16-byte aligned (d % 4 == 0).
+template <typename T>
+__device__ __forceinline__ float canon_part(const T *__restrict__ xv, const float *qv, int d, int sub) {
+    float part = 0.f;
+    for (int e = sub * 4; e < d; e += 16) {
+        float x0, x1, x2, x3;
+        if constexpr (sizeof(T) == 4) {
+            const float4 x4 = *reinterpret_cast<const float4 *>(xv + e);
+            x0 = x4.x; x1 = x4.y; x2 = x4.z; x3 = x4.w;
+        } else {
+            typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+            const f16x4 h4 = *reinterpret_cast<const f16x4 *>(xv + e);
+            x0 = (float)h4[0]; x1 = (float)h4[1]; x2 = (float)h4[2]; x3 = (float)h4[3];
+        }
+        const float4 q4 = *reinterpret_cast<const float4 *>(qv + e);
+        part = fmaf(x0, q4.x, part); part = fmaf(x1, q4.y, part);
+        part = fmaf(x2, q4.z, part); part = fmaf(x3, q4.w, part);
+    }
+    return part;
+}
+__device__ __forceinline__ float canon_sum(float part) {
+    part += __shfl_xor(part, 1, 64);             // lane 4c: p0 + p1, lane 4c + 2: p2 + p3
+    part += __shfl_xor(part, 2, 64);             // (p0 + p1) + (p2 + p3) (fp32 addition commutes: every lane has the same bits)
+    return part;
+}
+
 __device__ inline void bitonic_sort_u64(unsigned long long *s, int P, int tid, int nt) {
     for (int k = 2; k <= P; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -66,14 +98,13 @@ __device__ inline void topk_fallback_body(int64_t m, int *row_ovf, const float *
                                           int64_t n, int d, int k, float *D, int64_t *I, int64_t label_base) {
     constexpr int FB = 2048, RPP = NT / 2;        // buffer slots; rows per pass (NT / 4 row groups x 2)
     __shared__ unsigned long long buf[FB];
-    __shared__ float qs[1024];
+    __shared__ __attribute__((aligned(16))) float qs[1024];
     __shared__ int s_cnt;
     __shared__ unsigned long long s_T;
     if (row_ovf[m] == 0) return;
-    // FOUR lanes per row, partial sums over e = 4 sub, 4 sub + 16, ..., combined as (p0 + p1) + (p2 + p3): the summation
-    // order of the select kernels' exact re-scoring (search_f16.hip), so a row's fp32 score has the same bits whether it comes
-    // out of a select or out of this fallback (round 6: with eight lanes per row a list overflow on one path of a sharded
-    // search moved a score by one ulp against the single-shard run)
+    // four lanes per row, the canonical summation order (canon_part / canon_sum): a row's fp32 score has the same bits
+    // whether it comes out of a select or out of this fallback (round 6: with eight lanes per row a list overflow on one
+    // path of a sharded search moved a score by one ulp against the single-shard run)
     const int tid = threadIdx.x, sub = tid & 3, grp = tid >> 2;
     for (int e = tid; e < d; e += NT) qs[e] = ELT == 4 ? q[m * d + e] : (float)(_Float16)q[m * d + e];
     if (tid == 0) { s_cnt = 0; s_T = ~0ull; }
@@ -85,22 +116,10 @@ __device__ inline void topk_fallback_body(int64_t m, int *row_ovf, const float *
             const int64_t row = base + u * (NT / 4) + grp;
             float part = 0.f;
             if (row < n) {
-                for (int e = sub * 4; e < d; e += 16) {
-                    float x0, x1, x2, x3;
-                    if (ELT == 4) {
-                        const float4 x4 = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(dbv) + row * d + e);
-                        x0 = x4.x; x1 = x4.y; x2 = x4.z; x3 = x4.w;
-                    } else {
-                        typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-                        const f16x4 h4 = *reinterpret_cast<const f16x4 *>(reinterpret_cast<const _Float16 *>(dbv) + row * d + e);
-                        x0 = (float)h4[0]; x1 = (float)h4[1]; x2 = (float)h4[2]; x3 = (float)h4[3];
-                    }
-                    part = fmaf(x0, qs[e], part); part = fmaf(x1, qs[e + 1], part);
-                    part = fmaf(x2, qs[e + 2], part); part = fmaf(x3, qs[e + 3], part);
-                }
+                if (ELT == 4) part = canon_part(reinterpret_cast<const float *>(dbv) + row * d, qs, d, sub);
+                else part = canon_part(reinterpret_cast<const _Float16 *>(dbv) + row * d, qs, d, sub);
             }
-            part += __shfl_xor(part, 1, 64);
-            part += __shfl_xor(part, 2, 64);
+            part = canon_sum(part);
             if (sub == 0 && row < n) {
                 const unsigned long long key = pack_key(part, (unsigned)row);
                 if (key < T) buf[atomicAdd(&s_cnt, 1)] = key;       // s_cnt <= FB - RPP before the pass
@@ -148,6 +167,9 @@ int launch_select_rescore(SearchWorkspace &ws, int64_t nq, int k, int mode, floa
 // fallback of flagged rows in ONE launch
 int launch_select_rescore_small(SearchWorkspace &ws, int64_t nq, int k, float *D, int64_t *I, int64_t label_base,
                                 const float *q32, const float *db32, int d, int nsub, int rescore, hipStream_t s);
+// dense small shard with an fp32 copy: canonical re-scoring of the dense pass's keys, eps from xnorm_max in the kernel
+int launch_select_dense(SearchWorkspace &ws, int64_t nq, int64_t n, int k, float *D, int64_t *I, int64_t label_base, const float *q32,
+                        const float *db32, int d, float xnorm_max, hipStream_t s);
 int launch_select_tail(SearchWorkspace &ws, int64_t nq, int k, float *D, int64_t *I, int64_t label_base, const float *q32,
                        const float *db32, const void *fb_rows, int fb_elt, int64_t n, int d, int nsub, int rescore, hipStream_t s);
 

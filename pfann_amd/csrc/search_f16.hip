@@ -793,6 +793,18 @@ __device__ __forceinline__ void sublist_offsets(const int *__restrict__ cnt_row,
 }
 
 constexpr int SMALL_N = 4096;
+
+// Dense small shard with an fp32 copy (search.hip, search_small: n <= CAP, nq <= 32): the keys hold the dense pass's fp32
+// MFMA scores, a pre-filter for the canonical re-scoring.  Half-width of the re-scoring window, |MFMA score - canonical
+// score| <= eps: any fp32 summation order of d rounded products is within (d + 1) u sum|q_i x_i| of q.x (u = 2^-24;
+// doubled for an accumulator that does not round to nearest), the canonical one within (d/4 + 2) u; sum|q_i x_i| <=
+// |q| max|x|; a factor 2 on top, and an absolute term for products below fp32's normal range.  Every thread sums the
+// query row itself (d <= 128 cached loads, the same order in every thread): no reduction, no extra launch.
+__device__ __forceinline__ float dense_canon_eps(const float *__restrict__ qv, int d, float xnorm_max) {
+    float ss = 0.f;
+    for (int e = 0; e < d; ++e) ss = fmaf(qv[e], qv[e], ss);
+    return 2.f * (2.f * (d + 1) + 0.25f * d + 2.f) * 5.9604645e-8f * 1.001f * sqrtf(ss) * xnorm_max + 1e-36f * d;
+}
 __device__ __forceinline__ void select_rescore_small_row(const int64_t m, const unsigned long long *__restrict__ keys,
                                                 const int *__restrict__ cnt, int k, int mode,
                                                 float *__restrict__ thr, float *__restrict__ thr_adj,
@@ -801,7 +813,7 @@ __device__ __forceinline__ void select_rescore_small_row(const int64_t m, const 
                                                 int *overflow, int *__restrict__ row_ovf,
                                                 const float *__restrict__ q32,
                                                 const float *__restrict__ db32, int d, int nsub,
-                                                int rescore) {
+                                                int rescore, float dense_xn = -1.f) {
     constexpr int NT = 256, KPT = SMALL_N / NT;
     __shared__ __attribute__((aligned(16))) unsigned long long skeys[SMALL_N];
     __shared__ int s_n2, s_bin, s_kk;
@@ -827,7 +839,8 @@ __device__ __forceinline__ void select_rescore_small_row(const int64_t m, const 
         }
     }
     __syncthreads();
-    const float e2 = rescore ? 2.0f * eps[m] : 0.f;
+    // (dense_xn >= 0: the dense small-shard pass, eps from the query row -- dense_canon_eps)
+    const float e2 = rescore ? 2.0f * (dense_xn >= 0.f ? dense_canon_eps(q32 + m * d, d, dense_xn) : eps[m]) : 0.f;
     if (n <= k) {
         if (tid == 0) s_n2 = n;
         __syncthreads();
@@ -878,8 +891,9 @@ __device__ __forceinline__ void select_rescore_small_row(const int64_t m, const 
         __syncthreads();
     }
     const int n2 = s_n2;
-    // exact fp32 scores: 4 threads per candidate (fixed reduction order), 4 x 64 candidates in flight per pass.  A
-    // candidate's four lanes sit in one wave, so its key is read before it is replaced in program order: no barrier
+    // exact fp32 scores in the canonical order (canon_part / canon_sum: 4 threads per candidate), 4 x 64 candidates in flight
+    // per pass.  A candidate's four lanes sit in one wave, so its key is read before it is replaced in program order: no
+    // barrier
     const float *qv = q32 + m * d;
     if (rescore)
     for (int c0 = 0; c0 < n2; c0 += NT) {
@@ -896,20 +910,13 @@ __device__ __forceinline__ void select_rescore_small_row(const int64_t m, const 
         for (int u = 0; u < 4; ++u) {
             const int c = c0 + u * (NT / 4) + (tid >> 2);
             if (c < n2) {
-                const float *xv = db32 + (int64_t)row[u] * d;
-                for (int e = sub * 4; e < d; e += 16) {
-                    const float4 x4 = *reinterpret_cast<const float4 *>(xv + e);
-                    const float4 q4 = *reinterpret_cast<const float4 *>(qv + e);
-                    part[u] = fmaf(x4.x, q4.x, part[u]); part[u] = fmaf(x4.y, q4.y, part[u]);
-                    part[u] = fmaf(x4.z, q4.z, part[u]); part[u] = fmaf(x4.w, q4.w, part[u]);
-                }
+                part[u] = canon_part(db32 + (int64_t)row[u] * d, qv, d, sub);
             }
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int c = c0 + u * (NT / 4) + (tid >> 2);
-            part[u] += __shfl_xor(part[u], 1, 64);
-            part[u] += __shfl_xor(part[u], 2, 64);
+            part[u] = canon_sum(part[u]);
             if (c < n2 && sub == 0) skeys[c] = pack_key(part[u], row[u]);
         }
     }
@@ -1074,7 +1081,7 @@ __global__ __launch_bounds__(256) void select_rescore_wave_kernel(const unsigned
         n2 = base;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
-    // exact fp32 scores: 4 lanes per candidate, 16 candidates per pass, select_rescore_small_kernel's summation order
+    // exact fp32 scores in the canonical order (canon_part / canon_sum): 4 lanes per candidate, 16 candidates per pass
     const float *qv = q32 + m * d;
     if (rescore)
         for (int c0 = 0; c0 < n2; c0 += 16) {
@@ -1083,16 +1090,9 @@ __global__ __launch_bounds__(256) void select_rescore_wave_kernel(const unsigned
             unsigned row = 0u;
             if (ci < n2) {
                 row = (unsigned)(sk[ci] & 0xFFFFFFFFull);
-                const float *xv = db32 + (int64_t)row * d;
-                for (int e = sub * 4; e < d; e += 16) {
-                    const float4 x4 = *reinterpret_cast<const float4 *>(xv + e);
-                    const float4 q4 = *reinterpret_cast<const float4 *>(qv + e);
-                    part = fmaf(x4.x, q4.x, part); part = fmaf(x4.y, q4.y, part);
-                    part = fmaf(x4.z, q4.z, part); part = fmaf(x4.w, q4.w, part);
-                }
+                part = canon_part(db32 + (int64_t)row * d, qv, d, sub);
             }
-            part += __shfl_xor(part, 1, 64);
-            part += __shfl_xor(part, 2, 64);
+            part = canon_sum(part);
             if (ci < n2 && sub == 0) sk[ci] = pack_key(part, row);
         }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1128,7 +1128,9 @@ __global__ __launch_bounds__(256) void select_rescore_wave_kernel(const unsigned
 }
 
 // ------------------------------------------------------------------------------------
-// Select with exact re-scoring (step 4 above).  One 1024-thread workgroup per query row.
+// Select with exact re-scoring (step 4 above) for the rows with more than SMALL_N survivors (every other row is
+// select_rescore_small_kernel's or select_rescore_wave_kernel's; a row of at most SMALL_N returns at once).  One
+// 1024-thread workgroup per query row.
 //   mode 0: thr[m] = exact k-th best (or -inf), thr_adj[m] = thr[m] - eps[m]
 //   mode 1: D, I = exact top-k;  list overflow -> overflow flag (+ raised thresholds)
 // ------------------------------------------------------------------------------------
@@ -1140,22 +1142,21 @@ __device__ __forceinline__ void select_rescore_body(const unsigned long long *__
                                            int *overflow, int *row_ovf,
                                            const float *__restrict__ q32,
                                            const float *__restrict__ db32, int d, int nsub,
-                                           int skip_small, int rescore, int64_t m = -1) {
+                                           int rescore, int64_t m = -1, float dense_xn = -1.f) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long skeys[];
     __shared__ int s_n2;
     __shared__ int s_off[NSUB_MAX + 2], s_wt[8];
     if (m < 0) m = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (skip_small && overflow[1] == 0) return;       // every row was handled by select_rescore_small_kernel
+    const int tid = threadIdx.x;
+    // every row was handled by select_rescore_small_kernel (the dense small-shard launch comes only for rows above SMALL_N)
+    if (dense_xn < 0.f && overflow[1] == 0) return;
     // gather the row's nsub sub-lists (sub-list g holds cnt[m*nsub+g] keys at keys[m*CAP + g*subcap])
     const int subcap = CAP / nsub;
     sublist_offsets<1024>(cnt + m * nsub, nsub, subcap, s_off, s_wt);
     const int n = s_off[nsub];
-    if (skip_small && n <= SMALL_N) return;          // done by select_rescore_small_kernel
+    if (n <= SMALL_N) return;          // done by select_rescore_small_kernel
     const bool over = s_off[NSUB_MAX + 1] != 0;
     if (over && mode == 1 && tid == 0) row_ovf[m] = 1;           // topk_fallback_kernel recomputes this row
-    int P = 1;
-    while (P < n) P <<= 1;
     if (nsub == 1) {
         for (int i = tid; i < n; i += 1024) skeys[i] = keys[m * CAP + i];
     } else {
@@ -1167,15 +1168,17 @@ __device__ __forceinline__ void select_rescore_body(const unsigned long long *__
     }
     __syncthreads();
     // candidates that can still belong to the exact top-k: s16 >= (k-th best s16) - 2 eps
-    const float e2 = rescore ? 2.0f * eps[m] : 0.f;
-    unsigned long long *ck = skeys;               // the candidates end up in ck[0 .. n2)
+    const float e2 = rescore ? 2.0f * (dense_xn >= 0.f ? dense_canon_eps(q32 + m * d, d, dense_xn) : eps[m]) : 0.f;
     if (n <= k) {
         if (tid == 0) s_n2 = n;
-    } else if (n <= CAP / 2) {
-        // k-th smallest key by MSB radix select on the 32 score bits (4 passes of 8 bits, LDS
-        // histogram), then compaction of everything above the cut: no sort of the ~16k survivors
+    } else {
+        // k-th smallest key by MSB radix select on the 32 score bits (4 passes of 8 bits, LDS histogram), then in-place
+        // compaction of everything within e2 of it (select_rescore_small_row's steps, 1024 threads, up to CAP keys): no
+        // sort of the survivors
+        constexpr int KPT = CAP / 1024;
         __shared__ int hist[256];
         __shared__ int s_bin, s_kk;
+        const int lane = tid & 63, wave = tid >> 6;
         unsigned prefix = 0;
         int kk = k;
         for (int pass = 0; pass < 4; ++pass) {
@@ -1210,51 +1213,31 @@ __device__ __forceinline__ void select_rescore_body(const unsigned long long *__
         }
         const float cut = ord2f(~prefix) - e2;
         const unsigned cut_hi = ~f2ord(cut);         // score >= cut  <=>  key's high word <= cut_hi
-        ck = skeys + CAP / 2;
+        unsigned long long mine[KPT];                // every thread takes its keys into registers first
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) mine[j] = tid + 1024 * j < n ? skeys[tid + 1024 * j] : ~0ull;
         if (tid == 0) s_n2 = 0;
         __syncthreads();
-        for (int i = tid; i < n; i += 1024) {
-            const unsigned long long key = skeys[i];
-            if ((unsigned)(key >> 32) <= cut_hi) ck[atomicAdd(&s_n2, 1)] = key;
-        }
-    } else {
-        for (int i = n + tid; i < P; i += 1024) skeys[i] = ~0ull;
-        __syncthreads();
-        bitonic_sort_u64(skeys, P, tid, 1024);      // by approximate score, descending
-        if (tid == 0) {
-            const float cut = ord2f(~(unsigned)(skeys[k - 1] >> 32)) - e2;
-            int lo = k, hi = n;                   // first index whose score < cut
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (ord2f(~(unsigned)(skeys[mid] >> 32)) >= cut) lo = mid + 1; else hi = mid;
-            }
-            s_n2 = lo;
-        }
+#pragma unroll
+        for (int j = 0; j < KPT; ++j)
+            if (tid + 1024 * j < n && (unsigned)(mine[j] >> 32) <= cut_hi) skeys[atomicAdd(&s_n2, 1)] = mine[j];
     }
     __syncthreads();
     const int n2 = s_n2;
-    // exact fp32 scores, all candidates of a pass in flight together: 8 threads per candidate, each a
-    // strided set of float4 chunks (a row is read as whole 128-byte lines), fixed reduction order
+    // exact fp32 scores in the canonical order (canon_part / canon_sum: 4 threads per candidate, the order of every other
+    // re-scoring site), all 256 candidates of a pass in flight together
     const float *qv = q32 + m * d;
     if (rescore)
-    for (int c0 = 0; c0 < n2; c0 += 128) {
-        const int c = c0 + (tid >> 3), sub = tid & 7;
+    for (int c0 = 0; c0 < n2; c0 += 256) {
+        const int c = c0 + (tid >> 2), sub = tid & 3;
         float part = 0.f;
         unsigned row = 0;
         if (c < n2) {
-            row = (unsigned)(ck[c] & 0xFFFFFFFFull);
-            const float *xv = db32 + (int64_t)row * d;
-            for (int e = sub * 4; e < d; e += 32) {
-                const float4 x4 = *reinterpret_cast<const float4 *>(xv + e);
-                const float4 q4 = *reinterpret_cast<const float4 *>(qv + e);
-                part = fmaf(x4.x, q4.x, part); part = fmaf(x4.y, q4.y, part);
-                part = fmaf(x4.z, q4.z, part); part = fmaf(x4.w, q4.w, part);
-            }
+            row = (unsigned)(skeys[c] & 0xFFFFFFFFull);
+            part = canon_part(db32 + (int64_t)row * d, qv, d, sub);
         }
-        part += __shfl_xor(part, 1, 64);
-        part += __shfl_xor(part, 2, 64);
-        part += __shfl_xor(part, 4, 64);
-        if (c < n2 && sub == 0) ck[c] = pack_key(part, row);
+        part = canon_sum(part);
+        if (c < n2 && sub == 0) skeys[c] = pack_key(part, row);
     }
     __syncthreads();
     if (n2 <= 1024) {
@@ -1263,29 +1246,29 @@ __device__ __forceinline__ void select_rescore_body(const unsigned long long *__
         unsigned long long mine = ~0ull;
         int rank = 0;
         if (tid < n2) {
-            mine = ck[tid];
-            for (int j = 0; j < n2; ++j) rank += ck[j] < mine ? 1 : 0;
+            mine = skeys[tid];
+            for (int j = 0; j < n2; ++j) rank += skeys[j] < mine ? 1 : 0;
         }
         __syncthreads();
-        if (tid < n2) ck[rank] = mine;
+        if (tid < n2) skeys[rank] = mine;
         __syncthreads();
     } else {
         int P2 = 1;
         while (P2 < n2) P2 <<= 1;
-        for (int i = n2 + tid; i < P2; i += 1024) ck[i] = ~0ull;     // entries beyond n2 can no longer matter
+        for (int i = n2 + tid; i < P2; i += 1024) skeys[i] = ~0ull;     // entries beyond n2 can no longer matter
         __syncthreads();
-        bitonic_sort_u64(ck, P2, tid, 1024);         // by exact score, descending
+        bitonic_sort_u64(skeys, P2, tid, 1024);         // by exact score, descending
     }
     if (mode == 0) {
         if (tid == 0) {
-            const float t = n2 >= k ? ord2f(~(unsigned)(ck[k - 1] >> 32)) : -INFINITY;
+            const float t = n2 >= k ? ord2f(~(unsigned)(skeys[k - 1] >> 32)) : -INFINITY;
             thr[m] = t;
             thr_adj[m] = fmaxf(rescore ? t - eps[m] : t, -1000.f * eps[m]);
         }
     } else {
         for (int i = tid; i < k; i += 1024) {
             if (i < n2) {
-                const unsigned long long key = ck[i];
+                const unsigned long long key = skeys[i];
                 D[m * k + i] = ord2f(~(unsigned)(key >> 32));
                 I[m * k + i] = (int64_t)(unsigned)(key & 0xFFFFFFFFu) + label_base;
             } else {
@@ -1304,8 +1287,8 @@ __global__ __launch_bounds__(1024) void select_rescore_kernel(const unsigned lon
                                                               int *overflow, int *__restrict__ row_ovf,
                                                               const float *__restrict__ q32,
                                                               const float *__restrict__ db32, int d, int nsub,
-                                                              int skip_small, int rescore) {
-    select_rescore_body(keys, cnt, k, mode, thr, thr_adj, eps, D, I, label_base, overflow, row_ovf, q32, db32, d, nsub, skip_small, rescore);
+                                                              int rescore) {
+    select_rescore_body(keys, cnt, k, mode, thr, thr_adj, eps, D, I, label_base, overflow, row_ovf, q32, db32, d, nsub, rescore);
 }
 
 __global__ __launch_bounds__(1024) void select_rescore_list_kernel(const unsigned long long *__restrict__ keys,
@@ -1320,9 +1303,46 @@ __global__ __launch_bounds__(1024) void select_rescore_list_kernel(const unsigne
     if (overflow[1] == 0) return;                     // no row of the list had more than SMALL_N survivors
     const int n_left = overflow[2];
     for (int it = blockIdx.x; it < n_left; it += gridDim.x) {
-        select_rescore_body(keys, cnt, k, mode, thr, thr_adj, eps, D, I, label_base, overflow, row_ovf, q32, db32, d, nsub, 1, rescore, left[it]);
+        select_rescore_body(keys, cnt, k, mode, thr, thr_adj, eps, D, I, label_base, overflow, row_ovf, q32, db32, d, nsub, rescore, left[it]);
         __syncthreads();
     }
+}
+
+// Dense small shard with an fp32 copy (search.hip, search_small: n <= CAP rows, every score of the dense MFMA pass kept, one
+// list per row): the one select that applies, chosen on the host from n -- the 256-thread select for n <= SMALL_N, the
+// 1024-thread body otherwise -- re-scoring in the canonical order with eps computed in the kernel (dense_canon_eps).  One
+// launch, as the plain select of an fp32-only shard.
+__global__ __launch_bounds__(256) void select_dense_small_kernel(const unsigned long long *__restrict__ keys, const int *__restrict__ cnt,
+                                                                 int k, float *D, int64_t *I, int64_t label_base, int *overflow,
+                                                                 int *row_ovf, const float *__restrict__ q32,
+                                                                 const float *__restrict__ db32, int d, float xnorm_max) {
+    select_rescore_small_row(blockIdx.x, keys, cnt, k, 1, nullptr, nullptr, nullptr, D, I, label_base, overflow, row_ovf, q32, db32, d, 1, 1,
+                             xnorm_max);
+}
+__global__ __launch_bounds__(1024) void select_dense_kernel(const unsigned long long *__restrict__ keys, const int *__restrict__ cnt, int k,
+                                                            float *D, int64_t *I, int64_t label_base, int *overflow, int *row_ovf,
+                                                            const float *__restrict__ q32, const float *__restrict__ db32, int d,
+                                                            float xnorm_max) {
+    select_rescore_body(keys, cnt, k, 1, nullptr, nullptr, nullptr, D, I, label_base, overflow, row_ovf, q32, db32, d, 1, 1, -1,
+                        xnorm_max);
+}
+
+int launch_select_dense(SearchWorkspace &ws, int64_t nq, int64_t n, int k, float *D, int64_t *I, int64_t label_base, const float *q32,
+                        const float *db32, int d, float xnorm_max, hipStream_t s) {
+    if (n > CAP) { set_error("select_dense: %lld rows > %d", (long long)n, CAP); return -1; }
+    const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(ws.cl);
+    const float xn = xnorm_max > 0.f ? xnorm_max : 0.f;
+    ProfScope ps("topk_select_rescore", s);
+    if (n <= SMALL_N) {
+        PF_LAUNCH(select_dense_small_kernel, dim3((unsigned)nq), dim3(256), 0, s, keys, ws.cnt, k, D, I, label_base, ws.overflow,
+                  ws.row_ovf, q32, db32, d, xn);
+    } else {
+        if (ensure_dyn_lds((const void *)select_dense_kernel, CAP * 8)) return -1;
+        PF_LAUNCH(select_dense_kernel, dim3((unsigned)nq), dim3(1024), CAP * 8, s, keys, ws.cnt, k, D, I, label_base, ws.overflow,
+                  ws.row_ovf, q32, db32, d, xn);
+    }
+    PF_HIP(hipGetLastError());
+    return 0;
 }
 
 // Last launch of the small-batch search (search.hip, search_small): the rows select_rescore_small_kernel left (more than
@@ -1335,7 +1355,7 @@ __global__ __launch_bounds__(1024) void select_tail_kernel(const unsigned long l
                                                            int *overflow, int *row_ovf, const float *__restrict__ q32,
                                                            const float *__restrict__ db32, int d, int nsub, int rescore,
                                                            const void *__restrict__ fb_rows, int64_t n) {
-    select_rescore_body(keys, cnt, k, 1, thr, thr_adj, eps, D, I, label_base, overflow, row_ovf, q32, db32, d, nsub, 1, rescore);
+    select_rescore_body(keys, cnt, k, 1, thr, thr_adj, eps, D, I, label_base, overflow, row_ovf, q32, db32, d, nsub, rescore);
     __syncthreads();
     topk_fallback_body<FB_ELT, 1024>(blockIdx.x, row_ovf, q32, fb_rows, n, d, k, D, I, label_base);
 }
@@ -1391,7 +1411,7 @@ int launch_select_rescore(SearchWorkspace &ws, int64_t nq, int k, int mode, floa
     PF_LAUNCH(select_rescore_small_kernel, dim3((unsigned)nq), dim3(256), 0, s, keys, ws.cnt, k, mode, ws.thr, ws.thr_adj, ws.eps, D,
               I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, rescore);
     PF_LAUNCH(select_rescore_kernel, dim3((unsigned)nq), dim3(1024), CAP * 8, s, keys, ws.cnt, k, mode, ws.thr, ws.thr_adj, ws.eps, D,
-              I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, 1, rescore);
+              I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, rescore);
     PF_HIP(hipGetLastError());
     return 0;
 }

@@ -9,6 +9,7 @@ import pytest
 
 import make_golden as mg
 from pfann_amd import synth
+from score_bits import assert_canonical_topk, rescoring_path
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -404,6 +405,10 @@ def _check_topk(torch, db, q, k, prefilter=True):
     # reported scores belong to the reported labels
     chk = np.einsum("qkd,qd->qk", db[I[:, :n].clip(0)], q)
     assert np.abs(chk - D[:, :n]).max() < 2e-6
+    # on a re-scoring path (tests/score_bits.py: rescoring_path follows search_topk's dispatch) the scores are the canonical
+    # fp32 bits and the labels the canonical top-k, ties included
+    if rescoring_path(db, q, prefilter):
+        assert_canonical_topk(D, I, q, db, k, what="n=%d d=%d nq=%d k=%d" % (db.shape[0], d, q.shape[0], k))
     return D, I
 
 
@@ -1208,7 +1213,10 @@ def test_melspec_is_bit_stable_beside_a_batched_search(torch_cuda):
 AGGRESSORS = {
     # name: (d, query rows, db rows) -> the scan-class kernels one search call of that shape launches (csrc/search.hip: search_topk)
     "d64_qres": (64, 4085, 120000),         # scan_f16_qres_kernel<4,true> (sampled pass) + scan_f16_qres_kernel<4> (full pass)
-    "d128_generic": (128, 1000, 300000),    # < 1024 query rows: the survivor ladder on scan_f16_kernel<1> (sampled levels) and <4> (full pass)
+    # d = 96 (neither 64 nor 128: no query-stationary kernel, no group-maximum pass at any nq): the survivor ladder on
+    # scan_f16_kernel<1> (dense coarsest level, sampled levels) and <4> (full pass).  (At d = 128 and 33 .. 1023 query rows
+    # every thresholded pass takes scan_f16_qres_kernel since round 6, k > 128 included: only the dense level would be generic.)
+    "d96_generic": (96, 1000, 300000),
     "d128_f16_storage": (128, 4085, 120000),  # fp16-only storage: scan_f16_qres_kernel<8,true,128> + <8,false,64>, s16 scores final
 }
 
@@ -1218,7 +1226,7 @@ AGGRESSORS = {
 def test_melspec_is_bit_stable_beside_every_scan_class_kernel(torch_cuda, aggressor, victim):
     """Round 6: the guard above covers scan_f16_qres_kernel<8,true,128> + <8,false,64> (one d = 128 search
     call runs both) beside the default log-mel.  The same watch for the other instantiations of the fp16-MFMA scan -- d = 64
-    (KS = 4), the generic scan_f16_kernel<1> / <4> of the survivor ladder, fp16-only storage -- and for the second FFT size
+    (KS = 4), the generic scan_f16_kernel<1> / <4> of the survivor ladder (d = 96), fp16-only storage -- and for the second FFT size
     of melspec_kernel (stft_n = 512: a different radix plan): every bit of the log-mel equal to the quiet run's."""
     torch = torch_cuda
     from pfann_amd.database import DeviceIndex

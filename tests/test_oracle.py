@@ -202,3 +202,147 @@ def test_resampler_restatement_properties():
     assert plan[0] == (0, 2646000, 0, 476000) and plan[1] == (2601900, 2646000, 4000, 472000)
     assert sum(p[3] for p in plan) == 125 * 8000
     assert R.chunk_plan(1000, 16000, 8000) == [(0, 1000, 0, 500)]
+
+
+# ---- the canonical fp32 score of the exact search (oracle/exactdot_c.c) ------------------------------------------
+
+from fractions import Fraction
+
+
+def _round_f32(v):
+    """Fraction -> the float32 nearest to it, ties to even, decided exactly against both float32 neighbours (no
+    double rounding through float64).  An exact zero is +0: every sum here starts from +0 in round-to-nearest."""
+    a = np.float32(float(v))
+    if Fraction(float(a)) == v:
+        return a
+    if Fraction(float(a)) > v:
+        lo, hi = np.nextafter(a, np.float32(-np.inf)), a
+    else:
+        lo, hi = a, np.nextafter(a, np.float32(np.inf))
+    dlo, dhi = v - Fraction(float(lo)), Fraction(float(hi)) - v
+    if dlo != dhi:
+        return lo if dlo < dhi else hi
+    return lo if int(lo.view(np.uint32)) & 1 == 0 else hi
+
+
+def _canon_rational(q, x):
+    """The canonical score with every fmaf and add done exactly in rationals and rounded once, as IEEE 754 says."""
+    d = q.shape[0]
+    p = []
+    for l in range(4):
+        acc = np.float32(0.0)
+        for e in range(4 * l, d, 16):
+            for t in range(4):
+                acc = _round_f32(Fraction(float(x[e + t])) * Fraction(float(q[e + t])) + Fraction(float(acc)))
+        p.append(acc)
+    a = _round_f32(Fraction(float(p[0])) + Fraction(float(p[1])))
+    b = _round_f32(Fraction(float(p[2])) + Fraction(float(p[3])))
+    return _round_f32(Fraction(float(a)) + Fraction(float(b)))
+
+
+def _canon_pairs(rng, d, kind, n):
+    """n (q, x) pairs of one kind: unit rows; heavy cancellation; fp16-subnormal-sized components; norms ~1e3."""
+    q = rng.standard_normal((n, d))
+    x = rng.standard_normal((n, d))
+    if kind == "unit":
+        q /= np.linalg.norm(q, axis=1, keepdims=True)
+        x /= np.linalg.norm(x, axis=1, keepdims=True)
+    elif kind == "cancel":
+        # x nearly orthogonal to q, with large terms of both signs: partial sums far above the result
+        q /= np.linalg.norm(q, axis=1, keepdims=True)
+        x -= (x * q).sum(1, keepdims=True) * q
+        x *= 1e3
+        x += 1e-4 * rng.standard_normal((n, d))
+    elif kind == "tiny":
+        # components of the size of fp16 subnormals (6e-8 .. 6e-5), mixed with a few normal ones
+        q = q * 2e-6
+        x = x * 3e-5
+        x[:, ::7] *= 1e4
+    elif kind == "big":
+        q = 1e3 * q / np.linalg.norm(q, axis=1, keepdims=True)
+        x = 1e3 * x / np.linalg.norm(x, axis=1, keepdims=True)
+    return q.astype(np.float32), x.astype(np.float32)
+
+
+@pytest.mark.parametrize("d", [16, 24, 64, 96, 128, 256])
+def test_canonical_score_c_matches_rational_statement(d):
+    """oracle_canon_scores (C, libm fmaf, -ffp-contract=off) equals, bit for bit, the canonical order evaluated with
+    exact rational arithmetic and one correct rounding per operation."""
+    rng = np.random.default_rng(1000 + d)
+    npair = {16: 200, 24: 200, 64: 120, 96: 100, 128: 80, 256: 40}[d]
+    for kind in ("unit", "cancel", "tiny", "big"):
+        q, x = _canon_pairs(rng, d, kind, npair)
+        idx = np.arange(npair)
+        got = native.canon_scores(q, x, idx, idx)
+        want = np.array([_canon_rational(q[i], x[i]) for i in range(npair)], np.float32)
+        bad = np.flatnonzero(got.view(np.int32) != want.view(np.int32))
+        assert bad.size == 0, "d=%d %s: %d of %d pairs differ, first %r vs %r" % (
+            d, kind, bad.size, npair, got[bad[0]], want[bad[0]])
+        # and the order is not a plain left-to-right sum: the statement is specific (a check on the check)
+        if kind == "unit" and d >= 64:
+            seq = np.array([np.float32(sum_seq(q[i], x[i])) for i in range(npair)], np.float32)
+            assert (seq.view(np.int32) != got.view(np.int32)).any()
+
+
+def sum_seq(q, x):
+    acc = np.float32(0.0)
+    for a, b in zip(q, x):
+        acc = np.float32(acc + np.float32(a * b))
+    return acc
+
+
+def test_canonical_score_pair_indexing():
+    """canon_scores scores the pairs it is given: any (query row, db row) pairing, repeats included."""
+    rng = np.random.default_rng(7)
+    q = rng.standard_normal((5, 32)).astype(np.float32)
+    x = rng.standard_normal((9, 32)).astype(np.float32)
+    qi = rng.integers(0, 5, 200)
+    xi = rng.integers(0, 9, 200)
+    got = native.canon_scores(q, x, qi, xi)
+    want = np.array([_canon_rational(q[a], x[b]) for a, b in zip(qi, xi)], np.float32)
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
+    assert native.canon_scores(q, x, [], []).shape == (0,)
+
+
+def _tie_db(rng, n, d, scale=1.0):
+    """Rows with planted exact ties (copies of rows) and near-ties (copies moved by one ulp in one component)."""
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    x *= np.float32(scale)
+    src = rng.integers(0, n, n // 3)
+    dst = rng.permutation(n)[: n // 3]
+    x[dst] = x[src]                                              # exact ties
+    near = rng.permutation(n)[: n // 4]
+    for r in near:
+        j = rng.integers(0, d)
+        x[r, j] = np.nextafter(x[r, j], np.float32(np.inf) if rng.random() < 0.5 else np.float32(-np.inf))
+    return x
+
+
+@pytest.mark.parametrize("d,n,k,scale", [(16, 300, 10, 1.0), (64, 500, 50, 1.0), (96, 400, 7, 1e3), (128, 257, 300, 1.0),
+                                         (128, 600, 1, 3e-2), (24, 100, 100, 1.0)])
+def test_canonical_topk_window_matches_brute_force(d, n, k, scale):
+    """flat_ip_topk_canonical's proven window gives what scoring every row gives, on data with planted exact ties
+    (row copies: ties go to the lower row) and near-ties (one ulp apart), queries taken from the rows themselves (the
+    k-th place sits inside a tie group), and k >= n (padding)."""
+    rng = np.random.default_rng(d * 1000 + n + k)
+    x = _tie_db(rng, n, d, scale)
+    q = np.concatenate([x[rng.integers(0, n, 12)] / np.float32(scale), rng.standard_normal((6, d)).astype(np.float32)])
+    D, I = search.flat_ip_topk_canonical(q, x, k)
+    Db, Ib = search.flat_ip_topk_canonical(q, x, k, brute=True)
+    assert np.array_equal(I, Ib)
+    assert np.array_equal(D.view(np.int32), Db.view(np.int32))
+    kk = min(k, n)
+    assert (I[:, kk:] == -1).all() and (D[:, kk:] == -np.finfo(np.float32).max).all()
+    # every returned score is the canonical score of its label, scores descend, ties go to the lower row
+    mi = np.repeat(np.arange(q.shape[0]), kk)
+    assert np.array_equal(D[:, :kk].ravel().view(np.int32), native.canon_scores(q, x, mi, I[:, :kk].ravel()).view(np.int32))
+    assert (np.diff(D[:, :kk], axis=1) <= 0).all()
+    tie = np.diff(D[:, :kk], axis=1) == 0
+    assert (np.diff(I[:, :kk], axis=1)[tie] > 0).all()
+    # copies really tie inside the returned lists (the case that needs the row rule)
+    if 1 < kk < n:
+        assert tie.any()
+    # against the float64 top-k: the same rows up to the window's width
+    D64, _ = search.flat_ip_topk(q, x, k)
+    assert np.abs(D[:, :kk] - D64[:, :kk]).max() <= 2 * search.canon_window(q, x).max()

@@ -1,5 +1,6 @@
 """Where one 10 s query's 0.9 ms goes (tuning aid): wall time of each stage with a synchronise per call,
-against a 1,000,050-row filler db.   python tools/ubench/one_query.py"""
+against a 1,000,050-row filler db.   python tools/ubench/one_query.py [ROWS]
+(ROWS: a filler db of about that many rows instead, e.g. 8000 for a shard small enough for the dense single pass)"""
 import os
 import sys
 import time
@@ -19,7 +20,7 @@ d, k = params["model"]["d"], params["indexer"]["top_k"]
 dev = torch.device("cuda", 0)
 eng = Engine(params, 0, max_batch=64)
 eng.load_state_dict(synth.make_state_dict_calibrated(params, seed=123))
-n_songs = 16950
+n_songs = int(sys.argv[1]) // 59 if len(sys.argv) > 1 else 16950
 song_pos = np.arange(n_songs + 1, dtype=np.int64) * 59
 g = torch.Generator(device=dev)
 g.manual_seed(1)
