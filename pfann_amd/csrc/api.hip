@@ -823,6 +823,8 @@ int pfann_match(pfann_db *db, const float *q, const int64_t *labels, int k, cons
                 const int32_t *qlen, int64_t nQ, int max_qlen, int frame_shift_mul, float score_alpha, int mode,
                 int only_owned, pfann_match_result *results, float *song_scores, void *stream) {
     PF_HIP(hipSetDevice(db->device));
+    // the contiguous scoring path reads rows as float4 / four halves (rerank.hip), like the search (search.hip: search_topk)
+    if (db->d % 4 != 0) { set_error("match: d %% 4 != 0 (d=%d)", db->d); return -1; }
     RerankArgs a;
     a.db = db->emb; a.dbh = db->emb_h; a.n = db->n; a.d = db->d; a.label_base = db->label_base;
     a.song_pos = db->song_pos; a.n_songs = db->n_songs; a.song_lo = db->song_lo; a.song_hi = db->song_hi;

@@ -384,31 +384,32 @@ __global__ __launch_bounds__(NT) void match_kernel(RerankArgs a) {
             for (int c = tid; c < nc; c += NT) {
                 const Cand cd = unpack_cand(a.mode, sk[c]);
                 if (c > 0 && unpack_cand(a.mode, sk[c - 1]).song == cd.song) continue;   // not a run head
-                double best = 0.0;   // slots start at 0: only scores > 0 are recorded
+                float best = 0.f;    // slots start at 0: only scores > 0 are recorded
                 int besto = 0;
                 bool any = false;
                 for (int e = c; e < nc; ++e) {
                     const Cand ce = unpack_cand(a.mode, sk[e]);
                     if (ce.song != cd.song) break;
-                    double sco;
-                    if (a.mode == 0) sco = (double)score[e] / (double)qlen;   // fsm == 1: sub_len == qlen
-                    else sco = (double)score[e];
-                    // the stored slot is float32: compare against its rounded value like numpy does
-                    if (sco > (any ? (double)(float)best : 0.0)) {
+                    float sco;
+                    if (a.mode == 0) sco = (float)((double)score[e] / (double)qlen);   // fsm == 1: sub_len == qlen
+                    else sco = score[e];
+                    // the stored slot is float32 and numpy compares a Python float with it IN float32 (the score is rounded
+                    // first): a later candidate of the song whose score rounds to the slot's value does not replace it
+                    if (sco > best) {
                         best = sco; any = true;
                         besto = a.mode == 0 ? ce.off : ce.off * a.fsm - ce.shift;
                     }
                 }
-                if (any) { ss[cd.song * 2] = (float)best; ss[cd.song * 2 + 1] = (float)besto; }
+                if (any) { ss[cd.song * 2] = best; ss[cd.song * 2 + 1] = (float)besto; }
             }
         } else if (tid == 0) {
             // python path with frame_shift_mul > 1: songs recur once per shift; replay serially
             for (int c = 0; c < nc; ++c) {
                 const Cand cd = unpack_cand(0, sk[c]);
                 const int sub_len = (qlen - cd.shift + a.fsm - 1) / a.fsm;
-                const double sco = (double)score[c] / (double)sub_len;
-                if (sco > (double)ss[cd.song * 2]) {
-                    ss[cd.song * 2] = (float)sco;
+                const float sco = (float)((double)score[c] / (double)sub_len);    // compared in float32, as above
+                if (sco > ss[cd.song * 2]) {
+                    ss[cd.song * 2] = sco;
                     ss[cd.song * 2 + 1] = (float)(cd.off * a.fsm - cd.shift);
                 }
             }
