@@ -297,6 +297,36 @@ int pfann_match(pfann_db *db, const float *q_dev, const int64_t *labels_dev, int
 #define PFANN_MATCH_ONLY_OWNED 1
 #define PFANN_MATCH_OWNED_BLOCK 2
 
+/* Monitor mode: the sequence matcher over EVERY window of nR long recordings, given the labels of all their rows.
+ * Recording r owns rows [rstart[r], rstart[r]+rlen[r]) of q_dev / labels_dev[.][k].  Its windows start at rows 0, hop,
+ * 2*hop, ... while w0 + window <= rlen[r]; a recording with 0 < rlen < window has exactly one window that covers all its
+ * rows (the answer pfann_match gives for the whole recording); rlen == 0: none.  wfirst_dev[nR+1] = prefix sums of the
+ * windows per recording (the caller computes them by this rule); window w0/hop of recording r is results_dev[wfirst[r] +
+ * w0/hop], and results_dev has wfirst[nR] entries.
+ * Every result is FIELD FOR FIELD what pfann_match returns for the query (qstart = rstart[r] + w0, qlen = window): song,
+ * offset relative to the window's first row, shift, n_cand (the unique candidates nominated by that window's OWN rows),
+ * score.  An alignment is a candidate of a window only if a top-k label of one of the window's rows nominates it (the
+ * reference's rule, database.py:133-140 on emb[w0:w0+window]) even where another alignment would score higher; order and
+ * tie-break are the reference's (np.unique order, strict >, first wins); rows outside the song contribute 0 and the
+ * divisor stays sub_len.
+ * mode 0, frame_shift_mul 1, score_alpha 0 (the default family), fp32 or fp16 storage: ONE kernel (csrc/monitor.hip)
+ * builds the candidate alignments once per chunk of neighbouring windows, computes every needed (alignment, row) inner
+ * product once and forms all window sums from them; fully asynchronous on `stream`.  A window's score bits are a
+ * function of the window's rows and the candidate alone -- not of hop, the chunking, the other windows / recordings of
+ * the call or the storage plan: each row dot is one fixed-layout fp32 reduction ((p0+p1)+(p2+p3) per lane, then the
+ * wave butterfly), a window adds its row dots in ascending row order in fp32, and the total is divided by sub_len in
+ * double.  (pfann_match sums a window as ONE long dot, so on real-valued rows the two agree to fp32 rounding -- within
+ * 1e-6 of the float64 score -- and bit for bit wherever fp32 is exact.)
+ * Everything else -- mode 1, score_alpha != 0, frame_shift_mul > 1, k * (window + hop - 1) > 8192 or window > 256 (no
+ * chunk fits the in-LDS list), or PFANN_WINDOWS_GENERAL=1 in the environment -- takes the general path: the windows
+ * are expanded to (qstart, qlen) pairs on the device and run through pfann_match in bounded launches.  That path reads
+ * wfirst[nR] back first: one synchronisation with `stream`.
+ * The handle must hold the WHOLE database (label_base 0, all songs): a recording is not sharded over GPUs (-1). */
+int pfann_match_windows(pfann_db *db, const float *q_dev, const int64_t *labels_dev, int k,
+                        const int64_t *rstart_dev, const int32_t *rlen_dev, int64_t nR,
+                        int window, int hop, int frame_shift_mul, float score_alpha, int mode,
+                        const int64_t *wfirst_dev, pfann_match_result *results_dev, void *stream);
+
 /* Songs whose rows all live in this shard: [*song_lo, *song_hi) (either pointer may be NULL); returns their number. */
 int pfann_db_owned_songs(pfann_db *db, int *song_lo, int *song_hi);
 

@@ -578,7 +578,7 @@ void pfann_debug_keep(pfann_ctx *c, int on) { c->keep = on != 0; }
 int pfann_prewarm(int device) {
     if (hipSetDevice(device) != hipSuccess) { set_error("pfann_prewarm: no HIP device %d", device); return -1; }
     int rc = launch_noop_api();
-    rc |= prewarm_mel() | prewarm_encoder() | prewarm_encoder_fused() | prewarm_search() | prewarm_search_f16() | prewarm_rerank();
+    rc |= prewarm_mel() | prewarm_encoder() | prewarm_encoder_fused() | prewarm_search() | prewarm_search_f16() | prewarm_rerank() | prewarm_monitor();
     if (hipDeviceSynchronize() != hipSuccess) rc = -1;
     return rc ? -1 : 0;
 }
@@ -641,6 +641,9 @@ struct pfann_db {
     bool prefilter = true;
     void *match_scratch = nullptr;      // long-query candidate slab (keys + sums), grown on demand
     size_t match_scratch_bytes = 0;
+    void *win_scratch = nullptr;        // pfann_match_windows, general path: (qstart, qlen) of the expanded windows
+    size_t win_scratch_bytes = 0;
+    int64_t max_song_rows = 0;          // longest song (pfann_db_load)
     // the seq_score seam (the reference's ctypes call, database.py:178-189): device slab, PINNED host image and a
     // private stream, kept between calls; seq_mu serialises concurrent callers on one handle (the reference's seam is
     // re-entrant: cpp/seqscore.cpp keeps no state)
@@ -675,6 +678,7 @@ void pfann_db_destroy(pfann_db *db) {
     if (db->ws.row_ovf) (void)hipFree(db->ws.row_ovf);
     if (db->ws.left) (void)hipFree(db->ws.left);
     if (db->match_scratch) (void)hipFree(db->match_scratch);
+    if (db->win_scratch) (void)hipFree(db->win_scratch);
     if (db->seq_scratch) (void)hipFree(db->seq_scratch);
     if (db->seq_host) (void)hipHostFree(db->seq_host);
     if (db->seq_stream) (void)hipStreamDestroy(db->seq_stream);
@@ -755,6 +759,8 @@ int pfann_db_load(pfann_db *db, const float *emb, int emb_is_device, int64_t n, 
     }
     db->n = n;
     db->song_pos_h.assign(song_pos, song_pos + n_songs + 1);
+    db->max_song_rows = 0;
+    for (int i = 0; i < n_songs; ++i) db->max_song_rows = std::max(db->max_song_rows, song_pos[i + 1] - song_pos[i]);
     PF_HIP(hipMalloc(&db->song_pos, (size_t)(n_songs + 1) * sizeof(int64_t)));
     PF_HIP(hipMemcpy(db->song_pos, song_pos, (size_t)(n_songs + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     // songs whose rows all live in [label_base, label_base + n)
@@ -862,6 +868,64 @@ int pfann_match(pfann_db *db, const float *q, const int64_t *labels, int k, cons
     }
     a.results = results; a.song_scores = song_scores;
     return launch_match(a, (hipStream_t)stream);
+}
+
+int pfann_match_windows(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart, const int32_t *rlen,
+                        int64_t nR, int window, int hop, int frame_shift_mul, float score_alpha, int mode,
+                        const int64_t *wfirst, pfann_match_result *results, void *stream) {
+    PF_HIP(hipSetDevice(db->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (db->d % 4 != 0) { set_error("match_windows: d %% 4 != 0 (d=%d)", db->d); return -1; }
+    if (window < 1 || hop < 1 || k < 1 || nR < 0) { set_error("match_windows: window=%d hop=%d k=%d nR=%lld", window, hop, k, (long long)nR); return -1; }
+    if (mode != 0 && mode != 1) { set_error("match_windows: unknown mode %d", mode); return -1; }
+    // a recording is matched against ALL songs by one GPU: a shard of a song-sharded database cannot answer
+    if (db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
+        db->song_pos_h.empty() || db->song_pos_h.back() != db->n) {
+        set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
+        return -1;
+    }
+    if (nR == 0) return 0;
+    const int C = match_windows_chunk(k, window, hop);
+    // PFANN_WINDOWS_GENERAL=1: every call takes the general path (A/B timing, tests); read per call, no process state
+    const char *env = getenv("PFANN_WINDOWS_GENERAL");
+    const bool forced = env != nullptr && env[0] != 0 && !(env[0] == '0' && env[1] == 0);
+    const bool fast = !forced && mode == 0 && frame_shift_mul == 1 && score_alpha == 0.0f && C >= 1 &&
+                      db->n_songs < (1 << 28) - 1 && db->max_song_rows < (1ll << 28) - 2 * WIN_SMAX;
+    if (fast) {
+        WindowsArgs a;
+        a.db = db->emb; a.dbh = db->emb_h; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+        a.q = q; a.labels = labels; a.k = k; a.rstart = rstart; a.rlen = rlen; a.nR = nR;
+        a.window = window; a.hop = hop; a.C = C; a.wfirst = wfirst; a.results = results;
+        return launch_match_windows(a, st);
+    }
+    // ---- general path: the windows become (qstart, qlen) pairs on the device and go through pfann_match.  Its launches
+    // are sized on the host, so the number of windows is read back first: ONE synchronisation with the stream.
+    int64_t nW = 0;
+    PF_HIP(hipMemcpyAsync(&nW, wfirst + nR, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PF_HIP(hipStreamSynchronize(st));
+    if (nW <= 0) return 0;
+    const size_t o_ql = (size_t)nW * sizeof(int64_t), need = o_ql + (size_t)nW * sizeof(int32_t);
+    if (db->win_scratch_bytes < need) {              // grow, then free: a failed allocation leaves the handle as it was
+        void *grown = nullptr;
+        PF_HIP(hipMalloc(&grown, need));
+        if (db->win_scratch) (void)hipFree(db->win_scratch);       // (the stream was drained above)
+        db->win_scratch = grown;
+        db->win_scratch_bytes = need;
+    }
+    int64_t *qs = reinterpret_cast<int64_t *>(db->win_scratch);
+    int32_t *ql = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(db->win_scratch) + o_ql);
+    if (launch_expand_windows(rstart, rlen, nR, window, hop, wfirst, nW, qs, ql, st)) return -1;
+    // windows per pfann_match call: its HBM slabs (lists longer than the LDS, or few queries) stay below 256 MB
+    int64_t P = 1;
+    while (P < (int64_t)window * k) P <<= 1;
+    const int64_t step = P > 8192 ? std::max<int64_t>(1, (256ll << 20) / (P * 12)) : 65536;
+    for (int64_t j0 = 0; j0 < nW; j0 += step) {
+        const int64_t n = std::min(step, nW - j0);
+        if (pfann_match(db, q, labels, k, qs + j0, ql + j0, n, window, frame_shift_mul, score_alpha, mode, 0, results + j0,
+                        nullptr, stream))
+            return -1;
+    }
+    return 0;
 }
 
 int pfann_song_scores_to_seconds(pfann_db *db, float *song_scores_dev, int64_t n_pairs, int frame_shift_mul, double hop_size,

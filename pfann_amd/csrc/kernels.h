@@ -122,6 +122,25 @@ int launch_match(const RerankArgs &a, hipStream_t s);
 int launch_match_pack(const pfann_match_result *res, int64_t nQ, unsigned long long *keys, hipStream_t s);
 int launch_match_pick(const unsigned long long *keys, int G, int64_t nQ, pfann_match_result *out, hipStream_t s);
 int launch_song_scores_to_seconds(float *ss, int64_t n_pairs, int fsm, double hop_size, int native_path, hipStream_t s);
+
+// ---- monitor.hip: the matcher over every window of long recordings (pfann_match_windows) ----------------
+static constexpr int WIN_SMAX = 256;    // rows one chunk of windows may span (and the longest window of the fast path)
+struct WindowsArgs {
+    const float *db; const void *dbh;   // fp32 rows, or (db == nullptr) fp16 rows; the WHOLE database (label_base 0)
+    int d;
+    const int64_t *song_pos; int n_songs;
+    const float *q; const int64_t *labels; int k;
+    const int64_t *rstart; const int32_t *rlen; int64_t nR;
+    int window, hop;
+    int C;                  // most window starts per chunk: match_windows_chunk(k, window, hop), >= 1
+    const int64_t *wfirst;  // [nR + 1]
+    pfann_match_result *results;
+};
+// window starts one workgroup can take (0: the lists do not fit the LDS, the caller expands the windows instead)
+int match_windows_chunk(int k, int window, int hop);
+int launch_match_windows(const WindowsArgs &a, hipStream_t s);
+int launch_expand_windows(const int64_t *rstart, const int32_t *rlen, int64_t nR, int window, int hop, const int64_t *wfirst,
+                          int64_t nW, int64_t *qstart, int32_t *qlen, hipStream_t s);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is per device
 int ensure_dyn_lds(const void *func, int bytes);
 
@@ -132,5 +151,6 @@ int prewarm_encoder_fused();
 int prewarm_search();
 int prewarm_search_f16();
 int prewarm_rerank();
+int prewarm_monitor();
 
 }  // namespace pfann

@@ -1,0 +1,313 @@
+// Monitor mode: the sequence matcher over every window of a long recording (pfann_match_windows).
+//
+// The answer for the window that starts at row w0 of a recording is what match_kernel (rerank.hip) gives for the query
+// (qstart = rstart + w0, qlen = window), mode 0: candidates = the alignments (song, offset) that a top-k label of one of
+// THAT window's rows nominates, in np.unique order, score = sum of the window's row dots / sub_len, strict-> first-wins
+// argmax (reference database.py:129-163 applied to emb[w0:w0+window]).  Matching the windows one by one computes every
+// (alignment, row) inner product once per window that contains the row -- up to `window` times -- and sorts candidate
+// lists that are 95 % the same.  Here one workgroup owns a CHUNK of up to C consecutive window starts of one recording:
+//
+//   labels of the chunk's S = (n-1)*hop + window rows -> keys (song, diagonal, row), diagonal = row-in-song - row-in-chunk,
+//      so one alignment is one diagonal whichever window looks at it (its offset in window i is diagonal + i*hop)
+//   -> bitonic sort in LDS: unique alignments are runs of equal (song, diagonal), in np.unique order, each run holding
+//      the rows that nominated it in ascending order
+//   -> one wave per alignment: the dots of the rows that some candidate window of the chunk contains, each computed ONCE
+//      into a per-wave LDS line; then lane i forms the sum of window i if one of its own rows nominated the alignment,
+//      and keeps its first maximum
+//   -> the 16 waves' per-window maxima are merged (ties: the smaller alignment index, i.e. np.unique order).
+//
+// SUMMATION ORDER (a window's score bits depend on the window's rows and the candidate only, not on hop, chunking, the
+// other windows / recordings of the call or the storage plan):
+//   row dot  : lane c holds float4 chunk c (c + 64 m) of the row, four fmaf chains p0..p3 from +0 in ascending m,
+//              s = (p0 + p1) + (p2 + p3), then wave_sum's xor butterfly (32, 16, .., 1).  For d <= 128 a row has at most 32
+//              chunks and two rows share a wave, one per half: lanes 32..63 of the one-row form hold +0 and s is never
+//              -0, so the butterfly's first step is the identity and the 16..1 steps inside a half give the same bits.
+//   window   : tot = 0; tot += dot[row] for the window's rows in ascending order, fp32 (rows outside the song: +0)
+//   score    : (double)tot / (double)sub_len, as mode 0 of match_kernel.
+#include "kernels.h"
+#include "match_common.h"
+#include <algorithm>
+
+namespace pfann {
+
+static constexpr int WIN_NT = 1024;
+static constexpr int WIN_ROW_BITS = 8;                 // row-in-chunk field of a key: S <= WIN_SMAX = 256
+static constexpr int WIN_DIAG_BITS = 28;               // diagonal + WIN_SMAX; the song takes the 28 bits above
+static constexpr int WIN_GRID = 1024;                  // workgroups; each walks the chunk slots blockIdx.x, + gridDim.x, ..
+
+__device__ __forceinline__ int windows_of(int L, int window, int hop) {
+    return L <= 0 ? 0 : (L < window ? 1 : (L - window) / hop + 1);
+}
+
+template <bool F16>
+__global__ __launch_bounds__(WIN_NT) void match_windows_kernel(WindowsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sk[];    // [P] keys, then [P + 1] run heads (ushort)
+    __shared__ long long s_cpos[1024];
+    __shared__ float s_dot[WIN_NT / 64][WIN_SMAX];       // per wave: the row dots of the alignment in hand
+    __shared__ float s_bt[WIN_NT / 64][64];              // per wave and window: best total, its alignment, candidates seen
+    __shared__ int s_ba[WIN_NT / 64][64];
+    __shared__ int s_bn[WIN_NT / 64][64];
+    __shared__ int s_wtot[WIN_NT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nchr = a.d >> 2;
+
+    const int64_t nW = a.wfirst[a.nR];
+    // few windows in the whole call: smaller chunks, so that more than a handful of compute units take part
+    const int C = min(a.C, max(4, (int)((nW + 255) / 256)));
+    // chunk slots: recording r owns the slots [wfirst[r] / C + r, wfirst[r + 1] / C + r + 1), at least ceil(its windows / C)
+    const int64_t n_slots = nW / C + a.nR;
+    int cshift, n_coarse;
+    load_coarse_song_pos<WIN_NT>(a.song_pos, a.n_songs, s_cpos, tid, cshift, n_coarse);
+
+    for (int64_t slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
+        int64_t lo = 0, hi = a.nR;                       // first recording whose slots start after `slot`
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (a.wfirst[mid] / C + mid <= slot) lo = mid + 1; else hi = mid;
+        }
+        const int64_t r = lo - 1;
+        const int L = a.rlen[r];
+        const int64_t nw = min((int64_t)windows_of(L, a.window, a.hop), a.wfirst[r + 1] - a.wfirst[r]);
+        const int64_t c0 = (slot - (a.wfirst[r] / C + r)) * C;       // first window of the chunk
+        if (c0 >= nw) continue;                          // (the whole workgroup: a spare slot)
+        const int nwc = (int)min((int64_t)C, nw - c0);
+        const int wl = min(a.window, L);                 // rows of a window: `window`, or all rows of a shorter recording
+        const int S = (nwc - 1) * a.hop + wl;            // rows the chunk spans (<= WIN_SMAX, S * k <= MAXC: the host's C)
+        const int64_t q0 = a.rstart[r] + c0 * a.hop;
+        const int ntot = S * a.k;
+        int P = 1;
+        while (P < ntot) P <<= 1;
+        unsigned short *heads = reinterpret_cast<unsigned short *>(sk + P);
+
+        // ---- keys (song, diagonal, row)
+        for (int i = tid; i < P; i += WIN_NT) {
+            unsigned long long key = SENT;
+            if (i < ntot) {
+                const int tr = i / a.k;
+                const int64_t lab = a.labels[(q0 + tr) * a.k + (i - tr * a.k)];
+                if (lab >= 0) {
+                    const int song = song_of_label(a.song_pos, a.n_songs, s_cpos, cshift, n_coarse, lab);
+                    const int64_t p = song >= 0 ? lab - a.song_pos[song] : 0;
+                    // (p beyond the field: a label past the last row -- the search never returns one)
+                    if (song >= 0 && p < (1ll << WIN_DIAG_BITS) - 2 * WIN_SMAX)
+                        key = ((unsigned long long)song << (WIN_DIAG_BITS + WIN_ROW_BITS)) |
+                              ((unsigned long long)(unsigned)((int)p - tr + WIN_SMAX) << WIN_ROW_BITS) | (unsigned long long)tr;
+                }
+            }
+            sk[i] = key;
+        }
+        __syncthreads();
+        bitonic_sort_keys<WIN_NT>(sk, P, tid);
+
+        // ---- run heads: heads[a] = first key of alignment a, heads[n] = end of the last run
+        {
+            const int ept = P >= WIN_NT ? P / WIN_NT : 1;
+            int cnt = 0;
+            unsigned hm = 0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int i = tid * ept + e;
+                if (e < ept && i < P && (i == 0 || (sk[i] >> WIN_ROW_BITS) != (sk[i - 1] >> WIN_ROW_BITS))) { hm |= 1u << e; ++cnt; }
+            }
+            int incl = cnt;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += v;
+            }
+            if (lane == 63) s_wtot[wave] = incl;
+            __syncthreads();
+            int base = 0, total = 0;
+            for (int w = 0; w < WIN_NT / 64; ++w) { const int v = s_wtot[w]; if (w < wave) base += v; total += v; }
+            int pos = base + incl - cnt;
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (hm & (1u << e)) heads[pos++] = (unsigned short)(tid * ept + e);
+            if (tid == 0) heads[total] = (unsigned short)P;        // P <= 8192
+            __syncthreads();
+            // the padding / dropped labels sort last as one run of SENT: not an alignment
+            const int nalign = total - (sk[P - 1] == SENT ? 1 : 0);
+
+            // ---- one wave per alignment
+            float best = -INFINITY;
+            int besta = 0x7FFFFFFF, ncand = 0;
+            const int ws = lane * a.hop;
+            const bool wlive = lane < nwc;
+            float *dot = s_dot[wave];
+            const float4 *qb = reinterpret_cast<const float4 *>(a.q + q0 * a.d);
+            for (int al = wave; al < nalign; al += WIN_NT / 64) {
+                const int h0 = heads[al], h1 = heads[al + 1];
+                const unsigned long long key0 = sk[h0];
+                const int song = (int)(key0 >> (WIN_DIAG_BITS + WIN_ROW_BITS));
+                const int diag = (int)((key0 >> WIN_ROW_BITS) & ((1ull << WIN_DIAG_BITS) - 1)) - WIN_SMAX;
+                const int tmin = (int)(key0 & (WIN_SMAX - 1)), tmax = (int)(sk[h1 - 1] & (WIN_SMAX - 1));
+                // windows that can hold a nominating row: i*hop <= row < i*hop + wl
+                const int i_lo = tmin - wl + 1 <= 0 ? 0 : (tmin - wl + a.hop) / a.hop;
+                const int i_hi = min(nwc - 1, tmax / a.hop);
+                if (i_lo > i_hi) continue;               // nominated only by rows between two windows (hop > window)
+                const int r_lo = i_lo * a.hop, r_hi = i_hi * a.hop + wl;     // their rows, inside [0, S)
+                const int64_t start = a.song_pos[song];
+                const int slen = (int)(a.song_pos[song + 1] - start);
+                const int a_lo = max(r_lo, -diag), a_hi = min(r_hi, slen - diag);   // the rows that lie inside the song
+                for (int tr = r_lo + lane; tr < r_hi; tr += 64)
+                    if (tr < a_lo || tr >= a_hi) dot[tr] = 0.f;
+                if (nchr <= 32) {
+                    // two rows per step (one per half wave), four steps in flight: the gather lives on memory-level parallelism
+                    const int half = lane >> 5, hl = lane & 31;
+                    for (int t0 = a_lo; t0 < a_hi; t0 += 8) {
+                        float s[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const int tr = t0 + 2 * u + half;
+                            s[u] = 0.f;
+                            if (tr < a_hi && hl < nchr) {
+                                const float4 w = qb[(int64_t)tr * nchr + hl];
+                                const int64_t ro = (start + diag + tr) * (int64_t)nchr + hl;
+                                float4 v;
+                                if (F16) {
+                                    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+                                    const f16x4 h = reinterpret_cast<const f16x4 *>(a.dbh)[ro];
+                                    v = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+                                } else {
+                                    v = reinterpret_cast<const float4 *>(a.db)[ro];
+                                }
+                                const float p0 = fmaf(v.x, w.x, 0.f), p1 = fmaf(v.y, w.y, 0.f);
+                                const float p2 = fmaf(v.z, w.z, 0.f), p3 = fmaf(v.w, w.w, 0.f);
+                                s[u] = (p0 + p1) + (p2 + p3);
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const float v = wave_sum_half(s[u]);
+                            const int tr = t0 + 2 * u + half;
+                            if (hl == 0 && tr < a_hi) dot[tr] = v;
+                        }
+                    }
+                } else {
+                    for (int tr = a_lo; tr < a_hi; ++tr) {
+                        const float4 *wq = qb + (int64_t)tr * nchr;
+                        const int64_t ro = (start + diag + tr) * (int64_t)nchr;
+                        float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+                        for (int ch = lane; ch < nchr; ch += 64) {
+                            const float4 w = wq[ch];
+                            float4 v;
+                            if (F16) {
+                                typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+                                const f16x4 h = reinterpret_cast<const f16x4 *>(a.dbh)[ro + ch];
+                                v = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+                            } else {
+                                v = reinterpret_cast<const float4 *>(a.db)[ro + ch];
+                            }
+                            p0 = fmaf(v.x, w.x, p0); p1 = fmaf(v.y, w.y, p1); p2 = fmaf(v.z, w.z, p2); p3 = fmaf(v.w, w.w, p3);
+                        }
+                        const float v = wave_sum((p0 + p1) + (p2 + p3));
+                        if (lane == 0) dot[tr] = v;
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the line is written: every lane may read it
+                __builtin_amdgcn_wave_barrier();
+                // lane i = window i: a candidate there only if one of the window's OWN rows nominated the alignment
+                bool mine = false;
+                for (int e = h0; e < h1; ++e) {
+                    const int n = (int)(sk[e] & (WIN_SMAX - 1));
+                    mine |= n >= ws && n < ws + wl;
+                }
+                if (wlive && mine) {
+                    float tot = 0.f;
+                    for (int j = 0; j < wl; ++j) tot += dot[ws + j];
+                    ++ncand;
+                    if (tot > best) { best = tot; besta = al; }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // all read before the next alignment overwrites
+                __builtin_amdgcn_wave_barrier();
+            }
+            s_bt[wave][lane] = best;
+            s_ba[wave][lane] = besta;
+            s_bn[wave][lane] = ncand;
+            __syncthreads();
+            // ---- per window: first maximum in alignment (= np.unique) order over the waves
+            if (tid < nwc) {
+                float b = -INFINITY;
+                int ba = 0x7FFFFFFF, n = 0;
+                for (int w = 0; w < WIN_NT / 64; ++w) {
+                    const float t = s_bt[w][tid];
+                    const int ta = s_ba[w][tid];
+                    n += s_bn[w][tid];
+                    if (ta != 0x7FFFFFFF && (t > b || (t == b && ta < ba))) { b = t; ba = ta; }
+                }
+                pfann_match_result res;
+                res.n_cand = n;
+                if (ba != 0x7FFFFFFF) {
+                    const unsigned long long key = sk[heads[ba]];
+                    res.song = (int)(key >> (WIN_DIAG_BITS + WIN_ROW_BITS));
+                    res.offset = (int)((key >> WIN_ROW_BITS) & ((1ull << WIN_DIAG_BITS) - 1)) - WIN_SMAX + tid * a.hop;
+                    res.shift = 0;
+                    res.score = (double)b / (double)wl;
+                } else {
+                    res.song = -1; res.offset = 0; res.shift = 0; res.score = -INFINITY;
+                }
+                a.results[a.wfirst[r] + c0 + tid] = res;
+            }
+            __syncthreads();                             // the lists are free for the next slot
+        }
+    }
+}
+
+// windows -> (qstart, qlen) of the general path: window g of the call is window g - wfirst[r] of its recording r
+__global__ void expand_windows_kernel(const int64_t *__restrict__ rstart, const int32_t *__restrict__ rlen, int64_t nR, int window,
+                                      int hop, const int64_t *__restrict__ wfirst, int64_t nW, int64_t *__restrict__ qstart,
+                                      int32_t *__restrict__ qlen) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nW) return;
+    int64_t lo = 0, hi = nR - 1;                         // first recording whose windows end after g
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (wfirst[mid + 1] <= g) lo = mid + 1; else hi = mid;
+    }
+    const int64_t w0 = (g - wfirst[lo]) * hop;
+    const int64_t L = rlen[lo];
+    qstart[g] = rstart[lo] + w0;
+    const int64_t left = L - w0;
+    qlen[g] = (int32_t)(left <= 0 ? 0 : (left < window ? left : window));
+}
+
+int launch_expand_windows(const int64_t *rstart, const int32_t *rlen, int64_t nR, int window, int hop, const int64_t *wfirst,
+                          int64_t nW, int64_t *qstart, int32_t *qlen, hipStream_t s) {
+    if (nW <= 0) return 0;
+    PF_LAUNCH(expand_windows_kernel, dim3((unsigned)cdiv(nW, 256)), dim3(256), 0, s, rstart, rlen, nR, window, hop, wfirst, nW,
+              qstart, qlen);
+    PF_HIP(hipGetLastError());
+    return 0;
+}
+
+int match_windows_chunk(int k, int window, int hop) {
+    if (k < 1 || window < 1 || hop < 1 || window > WIN_SMAX) return 0;
+    int64_t c = ((int64_t)(MAXC / k) - window + 1) / hop;           // (C * hop + window - 1) * k <= MAXC
+    c = std::min<int64_t>(c, (WIN_SMAX - window) / hop + 1);        // (C - 1) * hop + window <= WIN_SMAX
+    return (int)std::max<int64_t>(0, std::min<int64_t>(c, 64));     // one lane per window
+}
+
+int launch_match_windows(const WindowsArgs &a, hipStream_t s) {
+    if (a.nR <= 0) return 0;
+    if (a.C < 1 || a.C > match_windows_chunk(a.k, a.window, a.hop)) { set_error("match_windows: chunk of %d windows does not fit", a.C); return -1; }
+    if (a.n_songs >= (1 << 28) - 1) { set_error("match_windows: too many songs"); return -1; }
+    const int lds_max = MAXC * 8 + (MAXC + 8) * 2;
+    const void *fn = a.db != nullptr ? (const void *)match_windows_kernel<false> : (const void *)match_windows_kernel<true>;
+    if (ensure_dyn_lds(fn, lds_max)) return -1;
+    int P = 1;
+    while (P < ((a.C - 1) * a.hop + a.window) * a.k) P <<= 1;
+    const size_t lds = (size_t)P * 8 + (size_t)(P + 8) * 2;
+    ProfScope ps("seq_match_windows", s);
+    if (a.db != nullptr) PF_LAUNCH(match_windows_kernel<false>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
+    else PF_LAUNCH(match_windows_kernel<true>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
+    PF_HIP(hipGetLastError());
+    return 0;
+}
+
+__global__ void noop_monitor_kernel() {}
+int prewarm_monitor() {
+    hipLaunchKernelGGL(noop_monitor_kernel, dim3(1), dim3(1), 0, 0);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace pfann

@@ -10,12 +10,11 @@
 //   -> first-wins strict-> argmax in the reference's own candidate order, so ties resolve
 //      to the smallest (song, offset) exactly as the reference does.
 #include "kernels.h"
+#include "match_common.h"
 #include <algorithm>
 
 namespace pfann {
 
-static constexpr int MAXC = 8192;       // candidate slots per query (qlen * top_k)
-static constexpr unsigned long long SENT = ~0ull;
 static constexpr int OFF_BIAS = 1 << 27;
 
 struct Cand { int song, off, shift; };
@@ -39,62 +38,19 @@ __device__ __forceinline__ Cand unpack_cand(int mode, unsigned long long key) {
     return c;
 }
 
-// Thread tid owns the positions i = tid + m*NT.  A compare-exchange distance j < 64 pairs positions of the same 64-aligned
-// group, i.e. two lanes of ONE wave: those steps need no workgroup barrier (a wave's LDS operations execute in order, and
-// within one instruction all 64 lanes read before any of them writes), only the steps with j >= 64 and the hand-over
-// between the two kinds do.  For P = 2048 that is 21 barriers instead of 66 (the one-query matcher spent 30 us of its
-// 74 us candidate phase in them).
-template <int NT>
-__device__ void bitonic_sort_keys(unsigned long long *sk, int P, int tid) {
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (j >= 32 || j == (k >> 1)) __syncthreads();     // positions written by other waves are read from here on
-            else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            for (int i = tid; i < P; i += NT) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long x = sk[i], y = sk[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((x > y) == up) { sk[i] = y; sk[ixj] = x; }
-                }
-            }
-        }
-    }
-    __syncthreads();
-}
-
 // ---- candidates (database.py:133-138 / seqscore.cpp:49-60): labels[t][i] -> packed (song, offset, shift) keys in sk[0..P)
 // (SENT for label -1, songs of other shards under only_owned, and the padding up to P).  No trailing barrier.
 template <int NT>
 __device__ void make_candidate_keys(const RerankArgs &a, int64_t q0, int ntot, int P, unsigned long long *sk, long long *s_cpos, int tid) {
-        // song of a label = upper_bound over song_pos: 15+ dependent global loads per label when searched directly
-        // (a third of this phase for one query); the first ~10 levels run on a coarse copy in LDS instead
-        int cshift = 0;
-        while ((a.n_songs >> cshift) > 1023) ++cshift;
-        const int n_coarse = (a.n_songs >> cshift) + 1;
-        for (int i = tid; i < n_coarse; i += NT) s_cpos[i] = a.song_pos[(int64_t)i << cshift];
-        __syncthreads();
+        int cshift, n_coarse;
+        load_coarse_song_pos<NT>(a.song_pos, a.n_songs, s_cpos, tid, cshift, n_coarse);
         for (int i = tid; i < P; i += NT) {
             unsigned long long key = SENT;
             if (i < ntot) {
                 const int t = i / a.k;
                 const int64_t lab = a.labels[(q0 + t) * a.k + (i - t * a.k)];
                 if (lab >= 0) {
-                    // largest s with song_pos[s] <= lab  (searchsorted side='right' - 1)
-                    int cl = 0, ch = n_coarse;    // coarse: entries before cl are <= lab, from ch on > lab
-                    while (cl < ch) {
-                        const int mid = (cl + ch) >> 1;
-                        if (s_cpos[mid] <= lab) cl = mid + 1; else ch = mid;
-                    }
-                    // song_pos[(cl-1) << cshift] <= lab < song_pos[cl << cshift] (when those exist): the same predicate
-                    // on the narrowed range gives the same answer as on [0, n_songs)
-                    int lo = cl > 0 ? (cl - 1) << cshift : 0;
-                    int hi = min(a.n_songs, cl << cshift);   // song_pos has n_songs+1 entries; search [0, n_songs)
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        if (a.song_pos[mid] <= lab) lo = mid + 1; else hi = mid;
-                    }
-                    const int song = lo - 1;
+                    const int song = song_of_label(a.song_pos, a.n_songs, s_cpos, cshift, n_coarse, lab);
                     const int tim = t / a.fsm, shift = t - tim * a.fsm;
                     const int off = (int)(lab - a.song_pos[song] - tim);
                     const bool owned = song >= a.song_lo && song < a.song_hi;

@@ -259,6 +259,39 @@ class DeviceIndex:
             return out, ss
         return self.results_to_host(res), ss
 
+    def match_windows(self, q, labels, rstart, rlen, window, hop, fsm=1, alpha=0.0, mode=0, to_host=True):
+        """Sequence matcher over every window of nR recordings (pfann_match_windows): recording r owns rows
+        [rstart[r], rstart[r] + rlen[r]) of q / labels.  -> (results, wfirst): window i of recording r -- rows
+        [i * hop, i * hop + window) of it -- is results[wfirst[r] + i], field for field what `match` returns for that
+        slice; results is the structured array, or with to_host=False the device tensor."""
+        window, hop = int(window), int(hop)
+        if window < 1 or hop < 1:
+            raise ValueError("match_windows: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
+        q = q.to(self.device, torch.float32).contiguous()
+        labels = labels.to(self.device, torch.int64).contiguous()
+        rs_np = np.ascontiguousarray(rstart, dtype=np.int64)
+        rl_np = np.ascontiguousarray(rlen, dtype=np.int32)
+        nR = int(rl_np.shape[0])
+        assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
+        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
+        nW = int(wfirst[-1])
+        res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        if nW:
+            rs = _l.upload_async(rs_np, self.device, np.int64)
+            rl = _l.upload_async(rl_np, self.device, np.int32)
+            wf = _l.upload_async(wfirst, self.device, np.int64)
+            _l.check(self.lib.pfann_match_windows(self.handle, q.data_ptr(), labels.data_ptr(), labels.shape[1], rs.data_ptr(),
+                                                  rl.data_ptr(), nR, window, hop, int(fsm), float(alpha), int(mode),
+                                                  wf.data_ptr(), res.data_ptr(), self._stream()), "pfann_match_windows")
+        return (self.results_to_host(res) if to_host else res), wfirst
+
+
+def window_counts(rlen, window, hop):
+    """windows per recording (include/pfann_amd.h, pfann_match_windows): starts 0, hop, 2*hop, .. while w0 + window <= L;
+    one window over all rows when 0 < L < window; none when L == 0"""
+    L = np.asarray(rlen, dtype=np.int64)
+    return np.where(L <= 0, 0, np.where(L < window, 1, (L - window) // hop + 1)).astype(np.int64)
+
 
 def _fine_to_time(fine, fsm, hop_size):
     """fine = t*fsm - shift  ->  (t - shift/fsm) * hop_size, as database.py:148 computes it."""
@@ -498,6 +531,72 @@ class Database:
     def query_batch(self, emb, qstart, qlen, want_song_scores=False, mode=None):
         """emb: torch cuda [sum(qlen), d] unit-norm rows; -> list of (score, (song, time), song_score|None)."""
         return self.query_finish(self.query_launch(emb, qstart, qlen, want_song_scores, mode))
+
+    # ---- monitor mode: every window of long recordings ----------------------------------------------
+    def monitor_launch(self, emb, rstart, rlen, window, hop, edge_window=0):
+        """First half of monitor mode: ONE search of all rows (each row once, however many windows contain it), then the
+        windowed matcher, launched asynchronously like query_launch.  emb: torch cuda [rows, d]; recording r owns rows
+        [rstart[r], rstart[r] + rlen[r]); window, hop in segments.  edge_window > 0: the same labels are matched a second
+        time in short windows of that many segments at hop 1 (monitor_finish leaves them in p["edge_rows"]): they place
+        the edges of a detection far better than the long windows' scores do (monitor.merge_windows)."""
+        if self.sharded is not None:
+            raise _l.PfannError("monitor mode is not song-sharded: a recording is matched on one GPU against the whole "
+                                "database (run without PFANN_GPUS / ranks)")
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        D, I = self.index.search(emb, self.top_k)
+        ev[1].record()
+        res, wfirst = self.index.match_windows(emb, I, rstart, rlen, window, hop, self.frame_shift_mul, self.score_alpha,
+                                               1 if cpp_accelerate else 0, to_host=False)
+        fine = self.index.match_windows(emb, I, rstart, rlen, edge_window, 1, self.frame_shift_mul, self.score_alpha,
+                                        1 if cpp_accelerate else 0, to_host=False) if edge_window > 0 else None
+        ev[2].record()
+        return {"res": res, "wfirst": wfirst, "fine": fine, "ev": ev, "hop": int(hop), "keep": (emb, I), "dev": self.index.device,
+                "mode": 1 if cpp_accelerate else 0}
+
+    MONITOR_DTYPE = np.dtype([("w0", "<i8"), ("score", "<f8"), ("song", "<i8"), ("time_s", "<f8")])
+
+    def monitor_finish(self, p):
+        """Second half: -> per recording a structured array (w0, score, song, time_s), one entry per window: its first
+        row, and score / song / time exactly as query_finish reports them for that slice (no candidate: -inf, -1, 0)."""
+        if getattr(self, "_copy_stream", None) is None:
+            self._copy_stream = torch.cuda.Stream(p["dev"])
+            self._pin = {}
+        with torch.cuda.stream(self._copy_stream):
+            self._copy_stream.wait_event(p["ev"][-1])
+            res = self.index.results_to_host(p["res"])
+        if self.timer is not None:
+            self.timer.mark_gpu("search", p["ev"][0], p["ev"][1])
+            self.timer.mark_gpu("rerank", p["ev"][1], p["ev"][2])
+            self.timer.resolve()
+        out = self._monitor_rows(res, p["wfirst"], p["hop"], p["mode"])
+        if p.get("fine") is not None:
+            with torch.cuda.stream(self._copy_stream):
+                p["edge_rows"] = self._monitor_rows(self.index.results_to_host(p["fine"][0]), p["fine"][1], 1, p["mode"])
+        return out
+
+    def _monitor_rows(self, res, wfirst, hop, mode):
+        fsm = self.frame_shift_mul
+        out = []
+        for r in range(len(wfirst) - 1):
+            rr = res[wfirst[r]:wfirst[r + 1]]
+            rows = np.zeros(rr.shape[0], dtype=self.MONITOR_DTYPE)
+            rows["w0"] = np.arange(rr.shape[0], dtype=np.int64) * hop
+            off, shift = rr["offset"].astype(np.int64), rr["shift"].astype(np.int64)
+            if mode == 1:                            # query_embeddings_cpp: float32 score and fine-frame time, > 0 only
+                sc = rr["score"].astype(np.float32)
+                ok = (rr["song"] >= 0) & (sc > 0)
+                fine = (off * fsm - shift).astype(np.float32).astype(np.float64)
+                rows["score"] = np.where(ok, sc.astype(np.float64), 0.0)
+                rows["song"] = np.where(rr["song"] >= 0, rr["song"], -1)
+                rows["time_s"] = np.where(ok, fine * self.hop_size / fsm, 0.0)
+            else:
+                ok = rr["song"] >= 0
+                rows["score"] = np.where(ok, rr["score"], -np.inf)
+                rows["song"] = np.where(ok, rr["song"], -1)
+                rows["time_s"] = np.where(ok, (off - shift / fsm) * self.hop_size, 0.0)
+            out.append(rows)
+        return out
 
     # ---- the reference's per-query contract ---------------------------------------------
     def query_embeddings(self, query):
