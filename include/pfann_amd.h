@@ -250,6 +250,18 @@ int pfann_search_bound(pfann_db *db, const float *q_dev, int64_t nq, int k, int 
 int pfann_search_topk_bounded(pfann_db *db, const float *q_dev, int64_t nq, int k, const float *lb_dev,
                               float *D_dev, int64_t *I_dev, void *stream);
 
+/* What a search call with this shape launches, as text, without touching a GPU (no handle: the shape is all it depends
+ * on, besides the PFANN_* A/B switches of the process).  storage: 0 = fp32 rows only (also: pre-filter off), 1 = fp32 rows
+ * with their fp16 copy, 2 = fp16-only storage; phase: 0 = pfann_search_topk, 1 = pfann_search_bound (mtop = its m),
+ * 2 = pfann_search_topk_bounded, with resume_with_lb = 1 when it follows the pfann_search_bound of the same (q_dev, nq, k).
+ * nq is one chunk (<= 16384 rows).  One line per launch in order -- `<kernel> grid=<workgroups> block=<threads> lds=<dynamic
+ * bytes>`, the kernel named as a kernel trace prints it without return type, namespace and parameter list -- then one
+ * `flags ...` line: path, q_prep (none / launch / folded), fallback (none / launch / tail), canonical_scores, error.  A shape
+ * the search rejects gives the flags line alone, error=<which>.  Returns the length of the whole text (buf receives at most
+ * len - 1 characters of it), -1 for an unknown storage or phase. */
+int pfann_search_plan(int64_t n, int d, int64_t nq, int k, int storage, int phase, int resume_with_lb, int mtop,
+                      char *buf, int len);
+
 /* Exact top-k of arbitrary (score,label) lists: in[nq][m] -> out[nq][k] (merging per-shard
  * top-k lists after an all-gather).  Entries with label<0 are ignored. */
 int pfann_topk_merge(pfann_db *db, const float *S_dev, const int64_t *L_dev, int64_t nq, int m,

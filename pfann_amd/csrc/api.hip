@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "kernels.h"
+#include "search_plan.h"
 
 namespace pfann { int launch_rows_to_half(const float *x, int64_t n, int d, void *xh, float *norm_max_dev, hipStream_t s); }
 
@@ -806,6 +807,18 @@ int pfann_search_topk_bounded(pfann_db *db, const float *q, int64_t nq, int k, c
     if (nq > 16384) { set_error("pfann_search_topk_bounded: at most 16384 query rows per call (got %lld)", (long long)nq); return -1; }
     return search_topk(db->emb, (db->prefilter || db->emb == nullptr) ? db->emb_h : nullptr, db->xnorm_max, db->n, db->d,
                        db->label_base, q, nq, k, D, I, db->ws, (hipStream_t)stream, 2, const_cast<float *>(lb));
+}
+
+int pfann_search_plan(int64_t n, int d, int64_t nq, int k, int storage, int phase, int resume_with_lb, int mtop, char *buf, int len) {
+    if (storage < STORE_F32 || storage > STORE_F16 || phase < 0 || phase > 2 || (buf == nullptr && len > 0)) {
+        set_error("pfann_search_plan: storage=%d phase=%d", storage, phase);
+        return -1;
+    }
+    SearchShape sh;
+    sh.n = n; sh.d = d; sh.nq = nq; sh.k = k; sh.storage = storage; sh.phase = phase; sh.mtop = mtop;
+    sh.resume = phase == 2 && resume_with_lb != 0;
+    sh.has_lb = phase == 2;
+    return print_search_plan(plan_search(sh, search_tuning()), buf, len);
 }
 
 int pfann_topk_merge(pfann_db *db, const float *S, const int64_t *L, int64_t nq, int m, int k, float *D,

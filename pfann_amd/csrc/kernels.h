@@ -60,11 +60,9 @@ int launch_myg_ln(const SubLayer &Llast, const float *z, const float *part, int 
 // ---- search.hip ----------------------------------------------------------------------
 struct SearchWorkspace {
     int64_t cap_q = 0;      // query rows the buffers are sized for
-    int cap_c = 0;          // candidate slots per query row
     float *thr = nullptr;   // [cap_q]
     int *cnt = nullptr;     // [cap_q]
-    float *cs = nullptr;    // [cap_q][cap_c]
-    int64_t *cl = nullptr;  // [cap_q][cap_c]
+    int64_t *cl = nullptr;  // [cap_q][CAP] packed survivor keys (a sampled pass: [cap_q][groups] group maxima)
     int *overflow = nullptr;   // [0] unused, [1] rows left to the big select kernel, [2] rows the wave-per-row select left, [3] spare
     int *left = nullptr;       // [cap_q] the rows counted in overflow[2]: the workgroup selects then walk THIS list with a small grid
     int *row_ovf = nullptr;    // [cap_q] set by a select kernel whose row lost survivors (a sub-list overflowed);

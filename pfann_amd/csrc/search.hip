@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256, 2) void scan_emit_kernel(ScanParams p) {
     const __amdgpu_buffer_rsrc_t srd_q = make_srd(p.q + mq0 * p.d, (unsigned long long)(p.nq - mq0) * p.d * 4ull);
     // one window per 32-row sub-tile: on a coarse sampling level of a large shard (row_stride up to 65536) the
     // rows of one 128-row tile span more than the 2 GB a buffer offset can address, 32 rows never do
-    // (launch_scan checks 31 * row_stride * d * 4 < 2 GB)
+    // (search_plan.h checks 31 * row_stride * d * 4 < 2 GB)
     __amdgpu_buffer_rsrc_t srd_db[BR];
     unsigned doff[BR];
 #pragma unroll
@@ -596,27 +596,6 @@ __global__ __launch_bounds__(256) void group_max_select_wave_kernel(const float 
     }
 }
 
-int launch_group_max_select(SearchWorkspace &ws, int64_t nq, int G, int k, int ncnt, bool with_eps, float margin, hipStream_t s,
-                            float *topm = nullptr, int mtop = 0, float margin_out = 0.f, int *zero_me = nullptr) {
-    if (G < 1 || G > 4096) { set_error("group select: %d groups (the kernel's LDS array holds 4096)", G); return -1; }
-    ProfScope ps("topk_group_select", s);
-    static const bool no_wave = getenv("PFANN_NO_WAVE_GROUP_SELECT") != nullptr;       // A/B aid: the workgroup form
-    const float *gm = reinterpret_cast<const float *>(ws.cl);
-    const float *ep = with_eps ? ws.eps : nullptr;
-    const dim3 wgrid((unsigned)cdiv(nq, 4));
-    if (!no_wave && G <= 64 * 8)
-        PF_LAUNCH(group_max_select_wave_kernel<8>, wgrid, dim3(256), 0, s, gm, G, k, ws.thr, ws.cnt, ncnt, ep, ws.thr_adj, margin, topm,
-                  mtop, margin_out, zero_me, nq);
-    else if (!no_wave && G <= 64 * 16)
-        PF_LAUNCH(group_max_select_wave_kernel<16>, wgrid, dim3(256), 0, s, gm, G, k, ws.thr, ws.cnt, ncnt, ep, ws.thr_adj, margin, topm,
-                  mtop, margin_out, zero_me, nq);
-    else
-    PF_LAUNCH(group_max_select_kernel, dim3((unsigned)nq), dim3(256), 0, s, reinterpret_cast<const float *>(ws.cl), G, k, ws.thr,
-              ws.cnt, ncnt, with_eps ? ws.eps : nullptr, ws.thr_adj, margin, topm, mtop, margin_out, zero_me);
-    PF_HIP(hipGetLastError());
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------
 // Exact fallback for rows whose survivor lists overflowed (row_ovf[m] != 0): thousands of rows tying at the
 // k-th score, or hundreds of near-duplicates landing in one sub-list.  ONE workgroup per flagged row streams the
@@ -632,17 +611,6 @@ __global__ __launch_bounds__(256) void topk_fallback_kernel(int *__restrict__ ro
                                                             float *__restrict__ D, int64_t *__restrict__ I,
                                                             int64_t label_base) {
     topk_fallback_body<ELT, 256>(blockIdx.x, row_ovf, q, dbv, n, d, k, D, I, label_base);
-}
-
-
-int launch_topk_fallback(SearchWorkspace &ws, const float *q, const float *db, const void *dbh, int64_t n, int d,
-                         int64_t nq, int k, float *D, int64_t *I, int64_t label_base, hipStream_t s) {
-    if (d > 1024) { set_error("search_topk: d=%d > 1024", d); return -1; }
-    ProfScope ps("topk_fallback", s);
-    if (db != nullptr) PF_LAUNCH(topk_fallback_kernel<4>, dim3((unsigned)nq), dim3(256), 0, s, ws.row_ovf, q, (const void *)db, n, d, k, D, I, label_base);
-    else PF_LAUNCH(topk_fallback_kernel<2>, dim3((unsigned)nq), dim3(256), 0, s, ws.row_ovf, q, dbh, n, d, k, D, I, label_base);
-    PF_HIP(hipGetLastError());
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------
@@ -719,58 +687,6 @@ int ensure_dyn_lds(const void *func, int bytes) {
     return 0;
 }
 
-// generic scan (any nq, any d): fp32 MFMA tiles, one survivor list per row
-static int launch_scan(const float *db, int64_t n, int d, int64_t stride, const float *q, int64_t nq,
-                       const float *thr, SearchWorkspace &ws, hipStream_t s) {
-    ScanParams p;
-    p.q = q; p.db = db; p.nq = nq; p.d = d;
-    p.row_stride = stride;
-    p.nrows = (n + stride - 1) / stride;
-    p.thr = thr; p.cnt = ws.cnt; p.keys = reinterpret_cast<unsigned long long *>(ws.cl);
-    p.nsub = 1; p.gmax = nullptr;
-    if ((unsigned long long)31 * stride * d * 4ull >= 0x7FFF0000ull) {
-        set_error("scan: sampling stride %lld x d %d exceeds the 2 GB window of a 32-row sub-tile", (long long)stride, d);
-        return -1;
-    }
-    if (thr == nullptr) {
-        if (p.nrows > CAP) { set_error("scan: dense level with %lld rows > %d", (long long)p.nrows, CAP); return -1; }
-        PF_LAUNCH(fill_int_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, s, ws.cnt, (int)p.nrows, nq);
-    } else {
-        PF_HIP(hipMemsetAsync(ws.cnt, 0, sizeof(int) * nq, s));
-    }
-    ProfScope ps(stride == 1 ? "scan_topk" : "scan_topk_sample", s, 2.0 * (double)nq * p.nrows * d);
-    if (nq <= 32) {
-        p.n_tiles_m = 1;
-        PF_LAUNCH((scan_emit_kernel<32, 128, 32, 32, 1>), dim3((unsigned)cdiv(p.nrows, 128)), dim3(256), 0, s, p);
-    } else if (nq <= 64) {
-        p.n_tiles_m = 1;
-        PF_LAUNCH((scan_emit_kernel<64, 64, 32, 32, 1>), dim3((unsigned)cdiv(p.nrows, 64)), dim3(256), 0, s, p);
-    } else {
-        p.n_tiles_m = cdiv(nq, 128);
-        const int64_t db_tiles = cdiv(p.nrows, 128);
-        // long runs of query tiles per block only when the grid still fills the chip many times over
-        if (db_tiles * cdiv(p.n_tiles_m, 4) >= 4096)
-            PF_LAUNCH((scan_emit_kernel<128, 128, 64, 64, 4>), dim3((unsigned)(db_tiles * cdiv(p.n_tiles_m, 4))),
-                               dim3(256), 0, s, p);
-        else
-            PF_LAUNCH((scan_emit_kernel<128, 128, 64, 64, 1>), dim3((unsigned)(db_tiles * p.n_tiles_m)),
-                               dim3(256), 0, s, p);
-    }
-    PF_HIP(hipGetLastError());
-    return 0;
-}
-
-static int launch_select(SearchWorkspace &ws, int64_t nq, int k, int mode, float *D, int64_t *I,
-                         int64_t label_base, int nsub, hipStream_t s) {
-    if (ensure_dyn_lds((const void *)select_kernel, CAP * 8)) return -1;
-    ProfScope ps("topk_select", s);
-    PF_LAUNCH(select_kernel, dim3((unsigned)nq), dim3(1024), CAP * 8, s,
-                       reinterpret_cast<const unsigned long long *>(ws.cl), ws.cnt, k, mode, ws.thr, D, I,
-                       label_base, ws.row_ovf, nsub);
-    PF_HIP(hipGetLastError());
-    return 0;
-}
-
 static int ensure_ws(SearchWorkspace &ws, int64_t nq) {
     if (ws.cap_q >= nq) return 0;
     if (ws.thr) { (void)hipFree(ws.thr); (void)hipFree(ws.cnt); (void)hipFree(ws.cl); (void)hipFree(ws.row_ovf); (void)hipFree(ws.left); }
@@ -786,84 +702,12 @@ static int ensure_ws(SearchWorkspace &ws, int64_t nq) {
     PF_HIP(hipMalloc(&ws.row_ovf, sizeof(int) * cap));
     PF_HIP(hipMemset(ws.row_ovf, 0, sizeof(int) * cap));     // kept zero by topk_fallback_kernel afterwards
     ws.cap_q = cap;
-    ws.cap_c = CAP;
     return 0;
 }
 
 __global__ void fill_empty_kernel(float *D, int64_t *I, int64_t total) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < total) { D[i] = -3.4028234663852886e38f; I[i] = -1; }
-}
-
-// ---- small batches (nq <= 32, d = 64 / 128): the HBM-bound streaming path ------------------------------
-//   n <= CAP            : one dense pass (every score kept) + select (fp32 rows with an fp16 copy: + canonical re-scoring);
-//   otherwise           : group-maximum pass over every R-th row (2048 groups) -> k-th best group maximum = tau
-//                         (radix select of 2048 values) -> full pass emitting scores >= tau into 32 sub-lists per
-//                         row (~R*k survivors) -> 256-thread radix select + rank sort.
-// Four short launches around the one pass that reads the shard; no host synchronisation.
-// db32 != nullptr with ELT == 2: `rows` is the fp16 copy of an fp32 shard -- the scan is a pre-filter with the rigorous
-// margin of q_prep_kernel (half the bytes of the fp32 pass), the select re-scores in exact fp32 like the batched path.
-// d = 128 and n > CAP: five launches instead of eight -- query preparation at the head of the group-maximum pass, the
-// select's counter zeroed by the group select, big select + exact fallback (both normally idle) in one launch.
-// PFANN_NO_FOLDED_SMALL=1: one launch per stage, as for d = 64.  (Going further -- the group select / the select as the
-// tail of the pass before it, run by workgroups 0 .. nq-1 once every workgroup has arrived -- was built and measured:
-// the in-kernel hand-over costs what the launch it replaces costs, 85.7 vs 82.6 us per call; profiles/r3/NOTES.md.)
-static bool folded_small_path(int d) {
-    static const bool off = getenv("PFANN_NO_FOLDED_SMALL") != nullptr;
-    return d == 128 && !off;
-}
-
-template <int ELT>
-static int search_small(const void *rows, int64_t n, int d, const void *qrows, int64_t nq, int k, float *D, int64_t *I,
-                        int64_t label_base, const float *q32, const float *db32, float xnorm_max, SearchWorkspace &ws, hipStream_t s) {
-    const bool prefilter = ELT == 2 && db32 != nullptr;
-    ScanParams p;
-    p.q = reinterpret_cast<const float *>(qrows); p.db = reinterpret_cast<const float *>(rows);
-    p.nq = nq; p.d = d; p.cnt = ws.cnt; p.keys = reinterpret_cast<unsigned long long *>(ws.cl);
-    p.n_tiles_m = 1; p.gmax = nullptr; p.thr = nullptr;
-    const double bytes_per_row = (double)d * ELT;
-#define PF_SMALL(MODE, GRID)                                                                                  \
-    do {                                                                                                      \
-        if (d == 128) PF_LAUNCH((scan_small_kernel<128, ELT, MODE>), dim3(GRID), dim3(256), 0, s, p);         \
-        else PF_LAUNCH((scan_small_kernel<64, ELT, MODE>), dim3(GRID), dim3(256), 0, s, p);                    \
-        PF_HIP(hipGetLastError());                                                                            \
-    } while (0)
-    if (n <= CAP) {
-        p.row_stride = 1; p.nrows = n; p.nsub = 1;
-        PF_LAUNCH(fill_int_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, s, ws.cnt, (int)n, nq);
-        {
-            ProfScope ps("scan_topk", s, n * bytes_per_row);
-            PF_SMALL(2, (unsigned)std::min<int64_t>(512, cdiv(n, 128)));
-        }
-        // fp32 rows with an fp16 copy: the MFMA scores are a pre-filter, the select re-scores in the canonical order
-        // (search_f16.hip, launch_select_dense), so a row's score has the bits it has on every other re-scoring path
-        if (ELT == 4 && db32 != nullptr) return launch_select_dense(ws, nq, n, k, D, I, label_base, q32, db32, d, xnorm_max, s);
-        return launch_select(ws, nq, k, 1, D, I, label_base, 1, s);
-    }
-    constexpr int GRID = 512, W = GRID * 4;            // persistent: 2 workgroups per CU; W groups in the sampled pass
-    int64_t R = k <= 128 ? 16 : (k <= 512 ? 4 : 2);    // expected survivors of the full pass ~ R * k
-    if (R > n / W) R = n / W;                          // at least one sampled row per group (n > CAP = 4 W)
-    p.row_stride = R; p.nrows = (n + R - 1) / R; p.nsub = 1;
-    p.gmax = reinterpret_cast<float *>(ws.cl);         // [nq][W] floats; the keys are written after tau is known
-    const bool folded = folded_small_path(d);
-    if (folded && ELT == 2) { p.q32 = q32; p.xnorm_max = xnorm_max; p.qh_out = ws.qh; p.eps = ws.eps; p.row_ovf = ws.row_ovf; }
-    {
-        ProfScope ps("scan_topk_sample", s, p.nrows * bytes_per_row);
-        PF_SMALL(1, GRID);
-    }
-    if (launch_group_max_select(ws, nq, W, k, 32, prefilter, prefilter ? 2.f : 0.f, s, nullptr, 0, 0.f,
-                                folded ? ws.overflow + 1 : nullptr)) return -1;
-    p.row_stride = 1; p.nrows = n; p.nsub = 32; p.thr = prefilter ? ws.thr_adj : ws.thr; p.gmax = nullptr; p.q32 = nullptr;
-    {
-        ProfScope ps("scan_topk", s, n * bytes_per_row);
-        PF_SMALL(0, GRID);
-    }
-#undef PF_SMALL
-    if (!folded) return launch_select_rescore(ws, nq, k, 1, D, I, label_base, q32, db32, d, 32, prefilter ? 1 : 0, s);
-    if (launch_select_rescore_small(ws, nq, k, D, I, label_base, q32, db32, d, 32, prefilter ? 1 : 0, s)) return -1;
-    // the fallback streams the exact rows: fp32 where the shard has them
-    return launch_select_tail(ws, nq, k, D, I, label_base, q32, db32, ELT == 4 ? rows : (db32 ? (const void *)db32 : rows),
-                              db32 != nullptr || ELT == 4 ? 4 : 2, n, d, 32, prefilter ? 1 : 0, s);
 }
 
 // phase 1 on a path without a sampled threshold: no information
@@ -878,124 +722,93 @@ __global__ void bound_in_kernel(float *__restrict__ thr_adj, const float *__rest
     if (m < nq) thr_adj[m] = fmaxf(thr_adj[m], lb[m] - margin * eps[m]);
 }
 
+// One stage of the plan: the kernel it names with the arguments the stage and the call give it.
+static int launch_stage(const SearchStage &st, const StageArgs &a) {
+    SearchWorkspace &ws = a.ws;
+    hipStream_t s = a.s;
+    const dim3 grid(st.grid), block(st.block);
+    const float *gm = reinterpret_cast<const float *>(ws.cl), *ep = st.with_eps ? ws.eps : nullptr;
+    float *topm = st.topm ? a.lb : nullptr;
+    const int mtop = st.topm ? a.mtop : 0;
+    int *zero_me = st.zero_me ? ws.overflow + 1 : nullptr;       // the select's overflow counter (one memset less)
+    switch (st.kernel) {
+#define X(id, ...) case K_##id: PF_LAUNCH((__VA_ARGS__), grid, block, st.lds, s, scan_params(st, a)); break;
+    PF_SCAN_KERNELS(X)
+#undef X
+    case K_FILL_EMPTY: PF_LAUNCH(fill_empty_kernel, grid, block, 0, s, a.D, a.I, a.nq * a.k); break;
+    case K_BOUND_NONE: PF_LAUNCH(bound_none_kernel, grid, block, 0, s, a.lb, a.nq * a.mtop); break;
+    case K_BOUND_IN: PF_LAUNCH(bound_in_kernel, grid, block, 0, s, ws.thr_adj, ws.eps, st.margin, a.lb, a.nq); break;
+    case K_FILL_INT: PF_LAUNCH(fill_int_kernel, grid, block, 0, s, ws.cnt, st.fill, a.nq); break;
+    case K_GROUP_SELECT:
+        PF_LAUNCH(group_max_select_kernel, grid, block, 0, s, gm, st.G, a.k, ws.thr, ws.cnt, st.ncnt, ep, ws.thr_adj, st.margin, topm, mtop,
+                  st.margin_out, zero_me);
+        break;
+    case K_GROUP_SELECT_WAVE_8:
+        PF_LAUNCH(group_max_select_wave_kernel<8>, grid, block, 0, s, gm, st.G, a.k, ws.thr, ws.cnt, st.ncnt, ep, ws.thr_adj, st.margin, topm,
+                  mtop, st.margin_out, zero_me, a.nq);
+        break;
+    case K_GROUP_SELECT_WAVE_16:
+        PF_LAUNCH(group_max_select_wave_kernel<16>, grid, block, 0, s, gm, st.G, a.k, ws.thr, ws.cnt, st.ncnt, ep, ws.thr_adj, st.margin, topm,
+                  mtop, st.margin_out, zero_me, a.nq);
+        break;
+    case K_SELECT:
+        if (ensure_dyn_lds((const void *)select_kernel, CAP * 8)) return -1;
+        PF_LAUNCH(select_kernel, grid, block, st.lds, s, reinterpret_cast<const unsigned long long *>(ws.cl), ws.cnt, a.k, st.mode, ws.thr,
+                  a.D, a.I, a.label_base, ws.row_ovf, st.nsub);
+        break;
+    case K_FALLBACK_4:
+        PF_LAUNCH(topk_fallback_kernel<4>, grid, block, 0, s, ws.row_ovf, a.q, (const void *)a.db, a.n, a.d, a.k, a.D, a.I, a.label_base);
+        break;
+    case K_FALLBACK_2:
+        PF_LAUNCH(topk_fallback_kernel<2>, grid, block, 0, s, ws.row_ovf, a.q, a.dbh, a.n, a.d, a.k, a.D, a.I, a.label_base);
+        break;
+    default: return launch_stage_f16(st, a);
+    }
+    PF_HIP(hipGetLastError());
+    return 0;
+}
+
+// Validate, size the workspace, plan (search_plan.h: every choice of kernel, grid and threshold is made there), run the stages.
 int search_topk(const float *db, const void *dbh, float xnorm_max, int64_t n, int d, int64_t label_base,
                 const float *q, int64_t nq, int k, float *D, int64_t *I, SearchWorkspace &ws, hipStream_t s,
                 int phase, float *lb, int mtop) {
     if (nq <= 0) return 0;
-    const bool resume = phase == 2 && ws.bound_valid && ws.bound_q == q && ws.bound_nq == nq && ws.bound_k == k;
-    if (phase != 2 || !resume) ws.bound_valid = false;
-    auto no_bound = [&]() -> int {               // phase 1 on a path without a sampled threshold
-        PF_LAUNCH(bound_none_kernel, dim3((unsigned)cdiv(nq * mtop, 256)), dim3(256), 0, s, lb, nq * mtop);
-        PF_HIP(hipGetLastError());
-        return 0;
-    };
-    if (k < 1 || k > 1024) { set_error("search_topk: k=%d outside 1..1024", k); return -1; }
-    if (d % 4 != 0) { set_error("search_topk: d=%d must be a multiple of 4", d); return -1; }
-    if (n >= (1ll << 32)) { set_error("search_topk: shard rows %lld >= 2^32", (long long)n); return -1; }
-    if (n == 0 && phase == 1) return no_bound();
-    if (n == 0) {
-        PF_LAUNCH(fill_empty_kernel, dim3((unsigned)cdiv(nq * k, 256)), dim3(256), 0, s, D, I, nq * k);
-        PF_HIP(hipGetLastError());
-        return 0;
-    }
-    if (db == nullptr && dbh == nullptr) { set_error("search_topk: no rows"); return -1; }
-    if (ensure_ws(ws, nq)) return -1;
-    const bool half_only = db == nullptr;               // fp16-only storage: s16 scores are final
-    // <= 32 query rows against an fp32 shard that also keeps its fp16 copy: stream the fp16 rows (half the bytes) as a
-    // pre-filter and re-score exactly; PFANN_SMALL_F32=1 keeps the fp32 streaming pass (A/B timing)
-    static const bool small_f32 = getenv("PFANN_SMALL_F32") != nullptr;
-    const bool small = nq <= 32 && (d == 128 || d == 64);
-    const bool small_pre = small && !half_only && dbh != nullptr && n > CAP && !small_f32;
-    const bool need_qh = half_only || (dbh != nullptr && nq > 32) || small_pre;      // (33 .. 64 rows took the fp32 ladder up to round 5)
-    if (need_qh) {
-        if (ws.qh_elems < nq * d) {
+    SearchShape sh;
+    sh.n = n; sh.d = d; sh.nq = nq; sh.k = k; sh.phase = phase; sh.mtop = mtop;
+    sh.storage = db == nullptr ? STORE_F16 : (dbh != nullptr ? STORE_F32_COPY : STORE_F32);
+    sh.resume = phase == 2 && ws.bound_valid && ws.bound_q == q && ws.bound_nq == nq && ws.bound_k == k;
+    sh.has_lb = lb != nullptr;
+    if (!sh.resume) ws.bound_valid = false;
+    const SearchPlan plan = plan_search(sh, search_tuning());
+    if (plan.error != PLAN_OK) { set_error("%s", plan.error_msg); return -1; }
+    if (n > 0) {
+        if (db == nullptr && dbh == nullptr) { set_error("search_topk: no rows"); return -1; }
+        if (ensure_ws(ws, nq)) return -1;
+        if (plan.need_qh && ws.qh_elems < nq * d) {
             if (ws.qh) { PF_HIP(hipStreamSynchronize(s)); (void)hipFree(ws.qh); }
             ws.qh = nullptr; ws.qh_elems = 0;
             PF_HIP(hipMalloc(&ws.qh, (size_t)nq * d * 2));
             ws.qh_elems = nq * d;
         }
-        // (the folded small path prepares the query rows at the head of its group-maximum pass)
-        const bool prep_in_scan = small && phase != 1 && n > CAP && folded_small_path(d);
-        if (!resume && !prep_in_scan && launch_q_prep(q, nq, d, xnorm_max, ws.qh, ws.eps, ws.row_ovf, s)) return -1;
     }
-    if (small) {
-        if (phase == 1) return no_bound();
-        int rc;
-        if (half_only) rc = search_small<2>(dbh, n, d, ws.qh, nq, k, D, I, label_base, q, nullptr, xnorm_max, ws, s);
-        else if (small_pre) rc = search_small<2>(dbh, n, d, ws.qh, nq, k, D, I, label_base, q, db, xnorm_max, ws, s);
-        // (an fp32 shard of <= CAP rows with its fp16 copy: canonical scores, db32 = the rows themselves)
-        else rc = search_small<4>(db, n, d, q, nq, k, D, I, label_base, q, dbh != nullptr && n <= CAP ? db : nullptr, xnorm_max, ws, s);
-        if (rc) return rc;
-        if (n > CAP && folded_small_path(d)) return 0;         // the fallback ran inside search_small's last launch
-        return launch_topk_fallback(ws, q, db, dbh, n, d, nq, k, D, I, label_base, s);
-    }
-    // ---- generic ladder: the shard is scanned at strides R^L .. R, 1; the coarsest level keeps everything
-    // sampling ratio per level: expected survivors ~ R*k per query, kept <= CAP/4
-    // (R = 8 and 4 were measured for the batched path too: more passes and selects cost more than the
-    // shorter survivor lists save)
-    const int R = k <= 128 ? 16 : (k <= 512 ? 4 : 2);
-    int levels = 0;
-    int64_t stride = 1;
-    // the coarsest level is scanned densely and fully sorted per query row: keep it <= 4096 rows (a
-    // 1/8 shard of 1 M rows would otherwise sort 8192 keys per row); it still holds > 4096/R >= k rows
-    const int64_t DENSE_CAP = 4096;
-    while ((n + stride - 1) / stride > DENSE_CAP) { stride *= R; ++levels; }
-    if (need_qh) {
-        // ---- fp16 MFMA scan (search_f16.hip).  fp32 storage: pre-filter with a rigorous margin + exact fp32
-        // re-scoring (same exact result); fp16-only storage: eps = 0, the s16 scores are the result
-        const int rescore = half_only ? 0 : 1;
-        {
-            // one group-maximum pass over every 4th row instead of the dense + 1/16 survivor levels; shards too small
-            // to give 4 k groups at that stride (the 1/4 and 1/8 shards of a multi-GPU job) are sampled more densely
-            int G = 0, rc = 1;
-            const float margin = rescore ? 1.f : 0.f;
-            if (resume) { G = ws.bound_G; rc = 0; }
-            else if (k <= 128 && getenv("PFANN_NO_GMAX") == nullptr)
-                for (int64_t gs = 4; gs >= 1 && rc == 1; gs >>= 1) rc = launch_scan_f16_gmax(dbh, n, d, gs, ws.qh, nq, k, ws, &G, s);
-            if (rc < 0) return -1;
-            if (rc == 0) {
-                if (!resume && launch_group_max_select(ws, nq, G, k, 0, true, rescore ? 2.f : 0.f, s, phase == 1 ? lb : nullptr,
-                                                       phase == 1 ? mtop : 0, margin)) return -1;
-                if (phase == 1) {
-                    ws.bound_valid = true; ws.bound_q = q; ws.bound_nq = nq; ws.bound_k = k; ws.bound_G = G;
-                    return 0;
-                }
-                if (resume && lb != nullptr) {
-                    PF_LAUNCH(bound_in_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, s, ws.thr_adj, ws.eps, margin, lb, nq);
-                    PF_HIP(hipGetLastError());
-                    ws.bound_valid = false;
-                }
-                int nsub = 1;
-                if (launch_scan_f16(dbh, n, d, 1, ws.qh, nq, ws.thr_adj, ws, true, &nsub, s)) return -1;
-                if (launch_select_rescore(ws, nq, k, 1, D, I, label_base, q, db, d, nsub, rescore, s, resume && lb != nullptr)) return -1;
-                return launch_topk_fallback(ws, q, db, dbh, n, d, nq, k, D, I, label_base, s);
-            }
-            if (phase == 1) return no_bound();
+    const StageArgs a{db, dbh, xnorm_max, n, d, label_base, q, nq, k, D, I, lb, mtop, ws, s};
+    for (int i = 0; i < plan.n_stages;) {
+        const SearchStage &st = plan.stages[i];
+        if (st.zero_cnt) PF_HIP(hipMemsetAsync(ws.cnt, 0, sizeof(int) * nq, s));
+        if (st.tag == nullptr) {
+            if (launch_stage(st, a)) return -1;
+            ++i;
+            continue;
         }
-        const float *ta = nullptr;
-        for (int lev = levels; lev >= 1; --lev) {
-            int nsub = 1;
-            if (launch_scan_f16(dbh, n, d, stride, ws.qh, nq, ta, ws, true, &nsub, s)) return -1;
-            if (launch_select_rescore(ws, nq, k, 0, nullptr, nullptr, 0, q, db, d, nsub, rescore, s)) return -1;
-            ta = ws.thr_adj;
-            stride /= R;
-        }
-        int nsub = 1;
-        if (launch_scan_f16(dbh, n, d, 1, ws.qh, nq, ta, ws, true, &nsub, s)) return -1;
-        if (launch_select_rescore(ws, nq, k, 1, D, I, label_base, q, db, d, nsub, rescore, s)) return -1;
-        return launch_topk_fallback(ws, q, db, dbh, n, d, nq, k, D, I, label_base, s);
+        ProfScope ps(st.tag, s, st.work);
+        if (st.zero_overflow) PF_HIP(hipMemsetAsync(ws.overflow + 1, 0, 2 * sizeof(int), s));
+        for (const int end = i + st.scope; i < end; ++i)
+            if (launch_stage(plan.stages[i], a)) return -1;
     }
-    if (phase == 1) return no_bound();
-    const float *thr = nullptr;
-    for (int lev = levels; lev >= 1; --lev) {
-        if (launch_scan(db, n, d, stride, q, nq, thr, ws, s)) return -1;
-        if (launch_select(ws, nq, k, 0, nullptr, nullptr, 0, 1, s)) return -1;
-        thr = ws.thr;
-        stride /= R;
-    }
-    if (launch_scan(db, n, d, 1, q, nq, thr, ws, s)) return -1;
-    if (launch_select(ws, nq, k, 1, D, I, label_base, 1, s)) return -1;
-    return launch_topk_fallback(ws, q, db, dbh, n, d, nq, k, D, I, label_base, s);
+    // the hand-over between the two phases of a sharded search, valid for exactly this (q, nq, k)
+    if (plan.leaves_bound) { ws.bound_valid = true; ws.bound_q = q; ws.bound_nq = nq; ws.bound_k = k; ws.bound_G = plan.G; }
+    if (plan.consumes_bound) ws.bound_valid = false;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1065,7 +878,6 @@ __global__ __launch_bounds__(256) void bound_reduce_kernel(const float *__restri
     if (row >= nq) return;
     const int n = G * m;
     unsigned key[VPL];
-    int present = 0;
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
         const int i = lane + 64 * j;
@@ -1073,13 +885,12 @@ __global__ __launch_bounds__(256) void bound_reduce_kernel(const float *__restri
         if (i < n) {
             const int g = i / m, c = i - g * m;
             const float v = cands[((int64_t)g * nq + row) * m + c];
-            if (v > -3.0e38f) { key[j] = f2ord(v); ++present; }   // -inf / -FLT_MAX padding = absent
+            if (v > -3.0e38f) key[j] = f2ord(v);                    // -inf / -FLT_MAX padding = absent
         }
     }
     int total = 0;
 #pragma unroll
     for (int j = 0; j < VPL; ++j) total += __popcll(__ballot(key[j] != 0u));
-    (void)present;
     if (total < k) { if (lane == 0) lb[row] = -3.4028234663852886e38f; return; }
     unsigned prefix = 0u;
     for (int bit = 31; bit >= 0; --bit) {

@@ -1,13 +1,12 @@
 // Shared pieces of the exact top-k search (search.hip, search_f16.hip).
 #pragma once
 #include "kernels.h"
+#include "search_plan.h"
 
 namespace pfann {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-static constexpr int CAP = 8192;   // survivor slots per query row
 
 __device__ __forceinline__ unsigned f2ord(float f) {   // monotone float -> uint
     const unsigned u = __float_as_uint(f);
@@ -151,27 +150,36 @@ __device__ inline void topk_fallback_body(int64_t m, int *row_ovf, const float *
     if (tid == 0) row_ovf[m] = 0;
 }
 
-// ---- fp16 pre-filter path (search_f16.hip) ------------------------------------------------
-int launch_rows_to_half(const float *x, int64_t n, int d, void *xh, float *norm_max_dev, hipStream_t s);
-int launch_q_prep(const float *q, int64_t nq, int d, float xnorm_max, void *qh, float *eps, int *row_ovf, hipStream_t s);
-int launch_scan_f16_gmax(const void *dbh, int64_t n, int d, int64_t stride, const void *qh, int64_t nq, int k,
-                         SearchWorkspace &ws, int *n_groups_out, hipStream_t s);
-int launch_scan_f16(const void *dbh, int64_t n, int d, int64_t stride, const void *qh, int64_t nq,
-                    const float *thr_adj, SearchWorkspace &ws, bool allow_sublists, int *nsub_out, hipStream_t s);
-// rescore = 1: survivors within 2 eps of the k-th best approximate score are re-scored in exact fp32 from db32;
-// rescore = 0: the keys' scores are final (eps is not read)
-int launch_select_rescore(SearchWorkspace &ws, int64_t nq, int k, int mode, float *D, int64_t *I, int64_t label_base,
-                          const float *q32, const float *db32, int d, int nsub, int rescore, hipStream_t s,
-                          bool few_survivors = false);
-// small-batch path (search_small): the 256-thread select alone, then big select (rows with > SMALL_N survivors) + exact
-// fallback of flagged rows in ONE launch
-int launch_select_rescore_small(SearchWorkspace &ws, int64_t nq, int k, float *D, int64_t *I, int64_t label_base,
-                                const float *q32, const float *db32, int d, int nsub, int rescore, hipStream_t s);
-// dense small shard with an fp32 copy: canonical re-scoring of the dense pass's keys, eps from xnorm_max in the kernel
-int launch_select_dense(SearchWorkspace &ws, int64_t nq, int64_t n, int k, float *D, int64_t *I, int64_t label_base, const float *q32,
-                        const float *db32, int d, float xnorm_max, hipStream_t s);
-int launch_select_tail(SearchWorkspace &ws, int64_t nq, int k, float *D, int64_t *I, int64_t label_base, const float *q32,
-                       const float *db32, const void *fb_rows, int fb_elt, int64_t n, int d, int nsub, int rescore, hipStream_t s);
+// What the stages of one search_topk call are launched with (search_plan.h says which and how large).
+struct StageArgs {
+    const float *db; const void *dbh;    // fp32 rows / fp16 rows (either may be absent)
+    float xnorm_max;
+    int64_t n; int d; int64_t label_base;
+    const float *q; int64_t nq; int k;
+    float *D; int64_t *I;
+    float *lb; int mtop;
+    SearchWorkspace &ws;
+    hipStream_t s;
+    // the rows a re-scoring select reads: the fp32 rows where the fp16 ones were only a pre-filter
+    const float *db32(const SearchStage &st) const { return st.rescore ? db : nullptr; }
+};
+// the ScanParams of a scan stage
+inline ScanParams scan_params(const SearchStage &st, const StageArgs &a) {
+    ScanParams p;
+    p.q = st.elt == 2 ? reinterpret_cast<const float *>(a.ws.qh) : a.q;
+    p.db = st.elt == 2 ? reinterpret_cast<const float *>(a.dbh) : a.db;
+    p.nq = a.nq; p.d = a.d; p.row_stride = st.stride; p.nrows = st.nrows;
+    p.thr = st.thr == THR_NONE ? nullptr : (st.thr == THR_ADJ ? a.ws.thr_adj : a.ws.thr);
+    p.cnt = a.ws.cnt; p.keys = reinterpret_cast<unsigned long long *>(a.ws.cl);
+    p.n_tiles_m = st.n_tiles_m; p.nsub = st.nsub;
+    p.gmax = st.gmax ? reinterpret_cast<float *>(a.ws.cl) : nullptr;       // [nq][groups] floats; the keys come after tau is known
+    if (st.fold_prep) { p.q32 = a.q; p.xnorm_max = a.xnorm_max; p.qh_out = a.ws.qh; p.eps = a.ws.eps; p.row_ovf = a.ws.row_ovf; }
+    return p;
+}
 
+// ---- search_f16.hip ------------------------------------------------------------------------
+int launch_rows_to_half(const float *x, int64_t n, int d, void *xh, float *norm_max_dev, hipStream_t s);
+// launches the stage if its kernel lives in search_f16.hip (the fp16 scans, query preparation, the re-scoring selects)
+int launch_stage_f16(const SearchStage &st, const StageArgs &a);
 
 }  // namespace pfann

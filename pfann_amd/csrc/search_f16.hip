@@ -77,13 +77,6 @@ __global__ void q_prep_kernel(const float *__restrict__ q, int64_t nq, int d, fl
     }
 }
 
-int launch_q_prep(const float *q, int64_t nq, int d, float xnorm_max, void *qh, float *eps, int *row_ovf, hipStream_t s) {
-    PF_LAUNCH(q_prep_kernel, dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, s, q, nq, d, xnorm_max,
-                       reinterpret_cast<_Float16 *>(qh), eps, row_ovf);
-    PF_HIP(hipGetLastError());
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------
 // fp16 scan: same tiling/pipeline as scan_emit_kernel<128,128,64,64,QT> (search.hip) with the
 // operands stored as halves: a 128-byte K-tile holds 64 k (vs 32 floats), the 16-byte fragment a
@@ -372,7 +365,7 @@ __global__ __launch_bounds__(256, DBR == 64 ? 3 : (NBUF == 3 ? 1 : 2)) void scan
     // BAL: a 16-lane read group holds fragment rows (l31 >> 2) in {0,3,5,6} or {1,2,4,7} x (l31 & 3) = 0..3, i.e. tile rows
     // 8 a + 4 wn + b: the key is built from a mod 4 and b so that the sixteen hit sixteen different bank groups again
     auto key = [](int r) { return BAL ? (((r >> 3) & 3) * (4 / RP)) | ((r & 3) / RP) : (r / RP) & (CPR - 1); };
-    // the 64-row-tile instantiation is the full pass: launched with stride 1 only (launch_scan_f16), so the row step is a
+    // the 64-row-tile instantiation is the full pass: launched with stride 1 only (search_plan.h), so the row step is a
     // compile-time 1 there and the sixteen (8 g + e) * stride products of the survivor path are immediates, not registers
     const int64_t rstride = DBR == 64 ? 1 : p.row_stride;
     const int64_t last_row = (p.nrows - 1) * rstride;
@@ -386,7 +379,7 @@ __global__ __launch_bounds__(256, DBR == 64 ? 3 : (NBUF == 3 ? 1 : 2)) void scan
         const int ci = (wave * NLD + u) * 64 + lane;
         const int r = ci / CPR, cs = ci % CPR;
         lrow[u] = r;
-        goff[u] = (unsigned)((unsigned long long)r * (unsigned long long)rstride * ROWB) + (unsigned)((cs ^ key(r)) * 16);   // (launchers: qres_stride_ok)
+        goff[u] = (unsigned)((unsigned long long)r * (unsigned long long)rstride * ROWB) + (unsigned)((cs ^ key(r)) * 16);   // (search_plan.h: qres_stride_ok)
     }
     auto load_tile = [&](int64_t t, float *Bd) {
         const int64_t r0 = t * DBR * rstride;
@@ -621,131 +614,9 @@ extern "C" int pfann_debug_set_scan_trace(void *buf, unsigned cap_blocks) {
 }
 #endif
 
-// The query-stationary kernel addresses a db tile with 32-bit chunk offsets against a per-tile descriptor of 0x7FFFFFF0 bytes:
-// the last row of a strided 128-row tile must lie inside it (stride <= ~66 k, i.e. shards below ~268 M rows for the ladder's
-// largest stride); beyond that the launchers take the generic kernel / the survivor ladder.
-static inline bool qres_stride_ok(int64_t stride, int d) {
-    return 127ll * stride * (2ll * d) + 2ll * d <= 0x7FFFFFF0ll;
-}
-
-// Fewest query rows that take the query-stationary kernels (sampled group-maximum pass + full pass with sub-lists).  Up to
-// round 5 this was 1024: between the streaming small-batch kernel (<= 32 rows) and 1024 rows the survivor ladder ran on the
-// generic kernel with one to eight query tiles -- two sampled levels + full pass = 1.1-1.4 ms whatever the row count
-// (profiles/r6/scan_mid_before.txt), the hole in the middle of the batch curve.  PFANN_QRES_MIN_NQ=1024 restores it (A/B).
-static inline int64_t qres_min_nq() {
-    static const int64_t v = getenv("PFANN_QRES_MIN_NQ") ? atoll(getenv("PFANN_QRES_MIN_NQ")) : 33;
-    return v;
-}
-
-// Sampled group-maximum pass (every `stride`-th row): fills gmax[nq][*n_groups_out] for group_max_select.
-// Returns 1 (not applicable: use the survivor ladder) when the shapes do not give >= 4 k groups per row.
-int launch_scan_f16_gmax(const void *dbh, int64_t n, int d, int64_t stride, const void *qh, int64_t nq, int k,
-                         SearchWorkspace &ws, int *n_groups_out, hipStream_t s) {
-    ScanParams p;
-    p.q = reinterpret_cast<const float *>(qh);
-    p.db = reinterpret_cast<const float *>(dbh);
-    p.nq = nq; p.d = d; p.row_stride = stride;
-    p.nrows = (n + stride - 1) / stride;
-    p.thr = nullptr; p.cnt = ws.cnt; p.keys = nullptr;
-    p.n_tiles_m = cdiv(nq, 128);
-    const int64_t db_tiles = cdiv(p.nrows, 128);
-    if (!(d == 128 || d == 64) || nq < qres_min_nq() || db_tiles < 16 || !qres_stride_ok(stride, d)) return 1;
-    // few query tiles (the middle of the batch curve): up to 64 slices, so that one tile still becomes 64 workgroups
-    const int s_max = p.n_tiles_m * 32 < 512 ? 64 : 32;
-    int S = (int)(2048 / p.n_tiles_m);
-    S = S < 1 ? 1 : (S > s_max ? s_max : S);
-    // no more groups than the threshold needs: 5 k of them (64 per slice) give the k-th best group maximum the same quality
-    // as 1000-1600 did -- the full pass that follows is not a microsecond slower -- while the group select, whose cost is
-    // the number of groups, halves: 0.77 -> 0.45 ms per 77,824 rows at 8 shards, 0.48 -> 0.29 on one GPU
-    // (profiles/r4/sharded_scan_model.txt; PFANN_GMAX_S overrides)
-    // ... but never fewer slices than fill the chip twice, and WHOLE rounds of the 512 resident workgroups: 76 query tiles x
-    // 8 slices are 1.2 rounds (the sampled pass itself slows from 0.64 to 0.78 ms), x 14 are 2.08 rounds (0.72: the last
-    // 0.08 of a round costs a round), x 13 are 1.93
-    const int s_cap = std::max(std::max(8, (5 * k + 63) / 64), (int)(1024 / p.n_tiles_m));
-    if (S > s_cap) S = s_cap;
-    static const int gs_env = getenv("PFANN_GMAX_S") ? atoi(getenv("PFANN_GMAX_S")) : 0;      // tuning aid: slices of the sampled pass
-    if (gs_env > 0) S = gs_env > 64 ? 64 : gs_env;       // (G = 64 S groups: the group select holds at most 4096 of them)
-    if (S > db_tiles) S = (int)db_tiles;
-    const int G = S * 64;                    // one group per (slice, row position in the 128-row tile up to the lane half)
-    if (G < 4 * k || db_tiles < 4 * (int64_t)S) return 1;      // >= 4 rows per group
-    p.nsub = S;
-    p.gmax = reinterpret_cast<float *>(ws.cl);
-    ProfScope ps("scan_topk_f16_sample", s, 2.0 * (double)nq * p.nrows * d);
-    const dim3 grid((unsigned)(p.n_tiles_m * S));
-    // at most one workgroup per CU: nobody covers a tile's round trip -> three tile buffers (96 KB, one workgroup per CU)
-    if (d == 128 && p.n_tiles_m * S <= 256) PF_LAUNCH((scan_f16_qres_kernel<8, true, 128, 3>), grid, dim3(256), 0, s, p);
-    else if (d == 128) PF_LAUNCH((scan_f16_qres_kernel<8, true>), grid, dim3(256), 0, s, p);
-    else PF_LAUNCH((scan_f16_qres_kernel<4, true>), grid, dim3(256), 0, s, p);
-    PF_HIP(hipGetLastError());
-    *n_groups_out = G;
-    return 0;
-}
-
 __global__ void fill_int2_kernel(int *p, int v, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
-}
-
-int launch_scan_f16(const void *dbh, int64_t n, int d, int64_t stride, const void *qh, int64_t nq,
-                    const float *thr_adj, SearchWorkspace &ws, bool allow_sublists, int *nsub_out, hipStream_t s) {
-    ScanParams p;
-    p.q = reinterpret_cast<const float *>(qh);
-    p.db = reinterpret_cast<const float *>(dbh);
-    p.nq = nq; p.d = d;
-    p.row_stride = stride;
-    p.nrows = (n + stride - 1) / stride;
-    p.thr = thr_adj; p.cnt = ws.cnt; p.keys = reinterpret_cast<unsigned long long *>(ws.cl);
-    p.nsub = 1;
-    if (thr_adj == nullptr) {
-        if (p.nrows > CAP) { set_error("scan: dense level with %lld rows > %d", (long long)p.nrows, CAP); return -1; }
-        PF_LAUNCH(fill_int2_kernel, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, s, ws.cnt, (int)p.nrows, nq);
-    } else {
-        PF_HIP(hipMemsetAsync(ws.cnt, 0, sizeof(int) * nq, s));
-    }
-    ProfScope ps(stride == 1 ? "scan_topk_f16" : "scan_topk_f16_sample", s, 2.0 * (double)nq * p.nrows * d);
-    p.n_tiles_m = cdiv(nq, 128);
-    const int64_t db_tiles = cdiv(p.nrows, 128);
-    static const bool no_qres = getenv("PFANN_NO_QRES") != nullptr;
-    bool qres_lists = false;
-    if (thr_adj != nullptr && allow_sublists && !no_qres && (d == 128 || d == 64) && nq >= qres_min_nq() && db_tiles >= 16 && qres_stride_ok(stride, d)) {
-        qres_lists = true;
-        // S interleaved db slices: about four rounds of the 512 resident workgroups, sub-lists of >= 256; with few query
-        // tiles up to 64 slices (sub-lists of 128: a row's ~330 survivors spread over them), so that one query tile still
-        // becomes 64 workgroups
-        const int s_max = p.n_tiles_m * 32 < 768 ? 64 : 32;
-        int S = (int)(2048 / p.n_tiles_m);
-        S = S < 1 ? 1 : (S > s_max ? s_max : S);
-        // whole rounds of the resident workgroups: with three per CU (64-row tiles) 76 query tiles x 26 slices are 2.57
-        // rounds of 768; 30 slices (2.97 rounds) run the pass in 2.77 instead of 2.91 ms (20: 2.82, 32: 2.97)
-        static const bool dbr64_s = getenv("PFANN_SCAN_DBR128") == nullptr;
-        if (dbr64_s && d == 128 && stride == 1) {
-            const int64_t slots = 768, rounds = (p.n_tiles_m * (int64_t)S + slots - 1) / slots;
-            const int64_t s2 = rounds * slots / p.n_tiles_m;
-            if (s2 >= S && s2 <= s_max) S = (int)s2;
-        }
-        static const int s_env = getenv("PFANN_SCAN_S") ? atoi(getenv("PFANN_SCAN_S")) : 0;
-        if (s_env > 0) S = s_env;
-        if (S > db_tiles) S = (int)db_tiles;
-        p.nsub = S;
-        // (no counter reset: every (row, private list) count is written by the lane that owns it, cnt[nq][4 S])
-        const dim3 grid((unsigned)(p.n_tiles_m * S));
-        // 64-row db tiles, three workgroups per CU (168 VGPRs) for the full pass: 2.97 -> 2.86 ms on the bench's 9728 x 1 M
-        // pass, back to back on one box (four per CU would need <= 128 VGPRs: 35 spilled); PFANN_SCAN_DBR128=1: the old tiles
-        static const bool dbr64 = getenv("PFANN_SCAN_DBR128") == nullptr;
-        static const bool nbuf3_always = getenv("PFANN_SCAN_NBUF3") != nullptr;       // (A/B aid)
-        if (d == 128 && dbr64 && stride == 1 && (p.n_tiles_m * S < 768 || nbuf3_always))      // less than one round of the resident slots
-            PF_LAUNCH((scan_f16_qres_kernel<8, false, 64, 3>), grid, dim3(256), 0, s, p);
-        else if (d == 128 && dbr64 && stride == 1) PF_LAUNCH((scan_f16_qres_kernel<8, false, 64>), grid, dim3(256), 0, s, p);
-        else
-        if (d == 128) PF_LAUNCH((scan_f16_qres_kernel<8>), grid, dim3(256), 0, s, p);
-        else PF_LAUNCH((scan_f16_qres_kernel<4>), grid, dim3(256), 0, s, p);
-    } else if (db_tiles * cdiv(p.n_tiles_m, 4) >= 4096)
-        PF_LAUNCH((scan_f16_kernel<4>), dim3((unsigned)(db_tiles * cdiv(p.n_tiles_m, 4))), dim3(256), 0, s, p);
-    else
-        PF_LAUNCH((scan_f16_kernel<1>), dim3((unsigned)(db_tiles * p.n_tiles_m)), dim3(256), 0, s, p);
-    PF_HIP(hipGetLastError());
-    *nsub_out = qres_lists ? 4 * p.nsub : p.nsub;       // the query-stationary kernel: four private lists per (row, slice)
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------
@@ -758,7 +629,6 @@ int launch_scan_f16(const void *dbh, int64_t n, int d, int64_t stride, const voi
 // per (row, db slice) -- one per owner lane -- instead of one list with an LDS counter): s_off[g] = keys of sub-lists
 // 0 .. g-1 (counts clamped to the sub-list capacity), s_off[nsub] = n, s_off[NSUB_MAX + 1] = some list overflowed.
 // Called by every thread of the workgroup (NT >= 256 threads); contains barriers.
-constexpr int NSUB_MAX = 256;
 template <int NT>
 __device__ __forceinline__ void sublist_offsets(const int *__restrict__ cnt_row, int nsub, int subcap, int *s_off, int *s_wt) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -792,9 +662,8 @@ __device__ __forceinline__ void sublist_offsets(const int *__restrict__ cnt_row,
     __syncthreads();
 }
 
-constexpr int SMALL_N = 4096;
 
-// Dense small shard with an fp32 copy (search.hip, search_small: n <= CAP, nq <= 32): the keys hold the dense pass's fp32
+// Dense small shard with an fp32 copy (search_plan.h, small_dense: n <= CAP, nq <= 32): the keys hold the dense pass's fp32
 // MFMA scores, a pre-filter for the canonical re-scoring.  Half-width of the re-scoring window, |MFMA score - canonical
 // score| <= eps: any fp32 summation order of d rounded products is within (d + 1) u sum|q_i x_i| of q.x (u = 2^-24;
 // doubled for an accumulator that does not round to nearest), the canonical one within (d/4 + 2) u; sum|q_i x_i| <=
@@ -1001,7 +870,6 @@ __global__ __launch_bounds__(256) void select_rescore_small_list_kernel(const un
 // lanes per candidate), same outputs; rows with more survivors or an overflowed sub-list are counted in overflow[2] and
 // left to select_rescore_small_kernel / select_rescore_kernel / the fallback.  mode 1 only (D, I out).
 // ------------------------------------------------------------------------------------
-constexpr int WAVE_N = 256;
 __global__ __launch_bounds__(256) void select_rescore_wave_kernel(const unsigned long long *__restrict__ keys,
                                                                   const int *__restrict__ cnt, int k,
                                                                   const float *__restrict__ eps, float *__restrict__ D,
@@ -1308,7 +1176,7 @@ __global__ __launch_bounds__(1024) void select_rescore_list_kernel(const unsigne
     }
 }
 
-// Dense small shard with an fp32 copy (search.hip, search_small: n <= CAP rows, every score of the dense MFMA pass kept, one
+// Dense small shard with an fp32 copy (search_plan.h, small_dense: n <= CAP rows, every score of the dense MFMA pass kept, one
 // list per row): the one select that applies, chosen on the host from n -- the 256-thread select for n <= SMALL_N, the
 // 1024-thread body otherwise -- re-scoring in the canonical order with eps computed in the kernel (dense_canon_eps).  One
 // launch, as the plain select of an fp32-only shard.
@@ -1327,25 +1195,7 @@ __global__ __launch_bounds__(1024) void select_dense_kernel(const unsigned long 
                         xnorm_max);
 }
 
-int launch_select_dense(SearchWorkspace &ws, int64_t nq, int64_t n, int k, float *D, int64_t *I, int64_t label_base, const float *q32,
-                        const float *db32, int d, float xnorm_max, hipStream_t s) {
-    if (n > CAP) { set_error("select_dense: %lld rows > %d", (long long)n, CAP); return -1; }
-    const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(ws.cl);
-    const float xn = xnorm_max > 0.f ? xnorm_max : 0.f;
-    ProfScope ps("topk_select_rescore", s);
-    if (n <= SMALL_N) {
-        PF_LAUNCH(select_dense_small_kernel, dim3((unsigned)nq), dim3(256), 0, s, keys, ws.cnt, k, D, I, label_base, ws.overflow,
-                  ws.row_ovf, q32, db32, d, xn);
-    } else {
-        if (ensure_dyn_lds((const void *)select_dense_kernel, CAP * 8)) return -1;
-        PF_LAUNCH(select_dense_kernel, dim3((unsigned)nq), dim3(1024), CAP * 8, s, keys, ws.cnt, k, D, I, label_base, ws.overflow,
-                  ws.row_ovf, q32, db32, d, xn);
-    }
-    PF_HIP(hipGetLastError());
-    return 0;
-}
-
-// Last launch of the small-batch search (search.hip, search_small): the rows select_rescore_small_kernel left (more than
+// Last launch of the folded small-batch search (search_plan.h, small_sampled_folded): the rows select_rescore_small_kernel left (more than
 // SMALL_N survivors; normally none: returns after one 4-byte read) and, behind it, the exact fallback for flagged rows
 // (normally none either) -- two launches' worth of "nothing to do" in one.  FB_ELT: element size of the fallback's rows.
 template <int FB_ELT>
@@ -1360,58 +1210,65 @@ __global__ __launch_bounds__(1024) void select_tail_kernel(const unsigned long l
     topk_fallback_body<FB_ELT, 1024>(blockIdx.x, row_ovf, q32, fb_rows, n, d, k, D, I, label_base);
 }
 
-int launch_select_tail(SearchWorkspace &ws, int64_t nq, int k, float *D, int64_t *I, int64_t label_base, const float *q32,
-                       const float *db32, const void *fb_rows, int fb_elt, int64_t n, int d, int nsub, int rescore, hipStream_t s) {
-    if (d > 1024) { set_error("search_topk: d=%d > 1024", d); return -1; }
-    const void *fn = fb_elt == 4 ? (const void *)select_tail_kernel<4> : (const void *)select_tail_kernel<2>;
-    if (ensure_dyn_lds(fn, CAP * 8)) return -1;
-    ProfScope ps("topk_select_tail", s);
-    if (fb_elt == 4)
-        PF_LAUNCH(select_tail_kernel<4>, dim3((unsigned)nq), dim3(1024), CAP * 8, s, reinterpret_cast<const unsigned long long *>(ws.cl),
-                  ws.cnt, k, ws.thr, ws.thr_adj, ws.eps, D, I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, rescore, fb_rows, n);
-    else
-        PF_LAUNCH(select_tail_kernel<2>, dim3((unsigned)nq), dim3(1024), CAP * 8, s, reinterpret_cast<const unsigned long long *>(ws.cl),
-                  ws.cnt, k, ws.thr, ws.thr_adj, ws.eps, D, I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, rescore, fb_rows, n);
-    PF_HIP(hipGetLastError());
-    return 0;
-}
-
-// small-batch path: ws.overflow[1] was zeroed by the group select; the rows this kernel leaves go to launch_select_tail
-int launch_select_rescore_small(SearchWorkspace &ws, int64_t nq, int k, float *D, int64_t *I, int64_t label_base,
-                                const float *q32, const float *db32, int d, int nsub, int rescore, hipStream_t s) {
-    ProfScope ps(rescore ? "topk_select_rescore" : "topk_select_radix", s);
-    PF_LAUNCH(select_rescore_small_kernel, dim3((unsigned)nq), dim3(256), 0, s,
-              reinterpret_cast<const unsigned long long *>(ws.cl), ws.cnt, k, 1, ws.thr, ws.thr_adj, ws.eps, D,
-              I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, rescore);
-    PF_HIP(hipGetLastError());
-    return 0;
-}
-
-// few_survivors: the caller expects a few dozen survivors per row (second phase of a sharded search): the wave-per-row
-// tier runs first and the workgroup kernels only see the rows it left
-int launch_select_rescore(SearchWorkspace &ws, int64_t nq, int k, int mode, float *D, int64_t *I, int64_t label_base,
-                          const float *q32, const float *db32, int d, int nsub, int rescore, hipStream_t s, bool few_survivors) {
-    if (ensure_dyn_lds((const void *)select_rescore_kernel, CAP * 8)) return -1;
-    ProfScope ps(rescore ? "topk_select_rescore" : "topk_select_radix", s);
-    PF_HIP(hipMemsetAsync(ws.overflow + 1, 0, 2 * sizeof(int), s));
-    static const bool no_wave = getenv("PFANN_NO_WAVE_SELECT") != nullptr;       // A/B aid
-    const bool wave_tier = few_survivors && mode == 1 && nsub <= NSUB_MAX && k <= WAVE_N && !no_wave;
+// The stages of the plan (search_plan.h) whose kernels live in this file.
+int launch_stage_f16(const SearchStage &st, const StageArgs &a) {
+    SearchWorkspace &ws = a.ws;
+    hipStream_t s = a.s;
+    const dim3 grid(st.grid), block(st.block);
     const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(ws.cl);
-    if (wave_tier) {
+    const float *db32 = a.db32(st);
+    switch (st.kernel) {
+#define X(id, ...) case K_##id: PF_LAUNCH((__VA_ARGS__), grid, block, st.lds, s, scan_params(st, a)); break;
+    PF_SCAN_F16_KERNELS(X)
+#undef X
+    case K_Q_PREP:
+        PF_LAUNCH(q_prep_kernel, grid, block, 0, s, a.q, a.nq, a.d, a.xnorm_max, reinterpret_cast<_Float16 *>(ws.qh), ws.eps, ws.row_ovf);
+        break;
+    case K_FILL_INT2: PF_LAUNCH(fill_int2_kernel, grid, block, 0, s, ws.cnt, st.fill, a.nq); break;
+    case K_SELECT_RESCORE_SMALL:
+        PF_LAUNCH(select_rescore_small_kernel, grid, block, 0, s, keys, ws.cnt, a.k, st.mode, ws.thr, ws.thr_adj, ws.eps, a.D, a.I,
+                  a.label_base, ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore);
+        break;
+    case K_SELECT_RESCORE:
+        if (ensure_dyn_lds((const void *)select_rescore_kernel, CAP * 8)) return -1;
+        PF_LAUNCH(select_rescore_kernel, grid, block, st.lds, s, keys, ws.cnt, a.k, st.mode, ws.thr, ws.thr_adj, ws.eps, a.D, a.I,
+                  a.label_base, ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore);
+        break;
+    case K_SELECT_RESCORE_WAVE:
+        PF_LAUNCH(select_rescore_wave_kernel, grid, block, 0, s, keys, ws.cnt, a.k, ws.eps, a.D, a.I, a.label_base, ws.overflow, a.q, db32,
+                  a.d, st.nsub, st.rescore, a.nq, ws.left);
+        break;
+    case K_SELECT_RESCORE_SMALL_LIST:
+        PF_LAUNCH(select_rescore_small_list_kernel, grid, block, 0, s, keys, ws.cnt, a.k, st.mode, ws.thr, ws.thr_adj, ws.eps, a.D, a.I,
+                  a.label_base, ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, ws.left);
+        break;
+    case K_SELECT_RESCORE_LIST:
         if (ensure_dyn_lds((const void *)select_rescore_list_kernel, CAP * 8)) return -1;
-        PF_LAUNCH(select_rescore_wave_kernel, dim3((unsigned)cdiv(nq, 4)), dim3(256), 0, s, keys, ws.cnt, k, ws.eps, D, I, label_base,
-                  ws.overflow, q32, db32, d, nsub, rescore, nq, ws.left);
-        PF_LAUNCH(select_rescore_small_list_kernel, dim3((unsigned)std::min<int64_t>(nq, 2048)), dim3(256), 0, s, keys, ws.cnt, k, mode,
-                  ws.thr, ws.thr_adj, ws.eps, D, I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, rescore, ws.left);
-        PF_LAUNCH(select_rescore_list_kernel, dim3((unsigned)std::min<int64_t>(nq, 512)), dim3(1024), CAP * 8, s, keys, ws.cnt, k, mode,
-                  ws.thr, ws.thr_adj, ws.eps, D, I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, rescore, ws.left);
-        PF_HIP(hipGetLastError());
-        return 0;
+        PF_LAUNCH(select_rescore_list_kernel, grid, block, st.lds, s, keys, ws.cnt, a.k, st.mode, ws.thr, ws.thr_adj, ws.eps, a.D, a.I,
+                  a.label_base, ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, ws.left);
+        break;
+    case K_SELECT_DENSE_SMALL:
+        PF_LAUNCH(select_dense_small_kernel, grid, block, 0, s, keys, ws.cnt, a.k, a.D, a.I, a.label_base, ws.overflow, ws.row_ovf, a.q, a.db,
+                  a.d, a.xnorm_max > 0.f ? a.xnorm_max : 0.f);
+        break;
+    case K_SELECT_DENSE:
+        if (ensure_dyn_lds((const void *)select_dense_kernel, CAP * 8)) return -1;
+        PF_LAUNCH(select_dense_kernel, grid, block, st.lds, s, keys, ws.cnt, a.k, a.D, a.I, a.label_base, ws.overflow, ws.row_ovf, a.q, a.db,
+                  a.d, a.xnorm_max > 0.f ? a.xnorm_max : 0.f);
+        break;
+    // the fallback inside the tail launch streams the exact rows: fp32 where the shard has them
+    case K_SELECT_TAIL_4:
+        if (ensure_dyn_lds((const void *)select_tail_kernel<4>, CAP * 8)) return -1;
+        PF_LAUNCH(select_tail_kernel<4>, grid, block, st.lds, s, keys, ws.cnt, a.k, ws.thr, ws.thr_adj, ws.eps, a.D, a.I, a.label_base,
+                  ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, (const void *)a.db, a.n);
+        break;
+    case K_SELECT_TAIL_2:
+        if (ensure_dyn_lds((const void *)select_tail_kernel<2>, CAP * 8)) return -1;
+        PF_LAUNCH(select_tail_kernel<2>, grid, block, st.lds, s, keys, ws.cnt, a.k, ws.thr, ws.thr_adj, ws.eps, a.D, a.I, a.label_base,
+                  ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, a.dbh, a.n);
+        break;
+    default: set_error("search: stage with unknown kernel %d", st.kernel); return -1;
     }
-    PF_LAUNCH(select_rescore_small_kernel, dim3((unsigned)nq), dim3(256), 0, s, keys, ws.cnt, k, mode, ws.thr, ws.thr_adj, ws.eps, D,
-              I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, rescore);
-    PF_LAUNCH(select_rescore_kernel, dim3((unsigned)nq), dim3(1024), CAP * 8, s, keys, ws.cnt, k, mode, ws.thr, ws.thr_adj, ws.eps, D,
-              I, label_base, ws.overflow, ws.row_ovf, q32, db32, d, nsub, rescore);
     PF_HIP(hipGetLastError());
     return 0;
 }

@@ -26,6 +26,22 @@ def song_pos_from_key(landmark_key):
     return np.pad(np.cumsum(np.asarray(landmark_key), dtype=np.int64), (1, 0))      # database.py:86
 
 
+def search_plan(n, d, nq, k, storage, phase=0, resume_with_lb=False, mtop=1):
+    """pfann_search_plan parsed: storage 0 = fp32 rows only, 1 = fp32 rows + fp16 copy, 2 = fp16-only -> (stages, flags)."""
+    lib = _l.load()
+    buf = ctypes.create_string_buffer(16384)
+    _l.check(lib.pfann_search_plan(n, d, nq, k, storage, phase, 1 if resume_with_lb else 0, mtop, buf, len(buf)),
+             "pfann_search_plan")
+    lines = buf.value.decode().splitlines()
+    stages = []
+    for ln in lines[:-1]:
+        name, rest = ln.rsplit(" grid=", 1)
+        g, b, l = (int(x.split("=")[-1]) for x in rest.replace("grid=", "").split(" "))
+        stages.append((name, g, b, l))
+    assert lines[-1].startswith("flags "), lines[-1]
+    return stages, dict(kv.split("=", 1) for kv in lines[-1].split(" ")[1:])
+
+
 class DeviceIndex:
     """One shard of fingerprints on one GPU + its search / match kernels."""
 
@@ -46,6 +62,7 @@ class DeviceIndex:
         self.label_base = 0
         self.n_songs = 0
         self._small_args = {}
+        self._prefilter = True
         self._host_res = None
 
     def __del__(self):
@@ -78,7 +95,19 @@ class DeviceIndex:
 
     def set_prefilter(self, on=True):
         """fp16 pre-filter of the batched scan (exact result either way) -> True if in use."""
+        self._prefilter = bool(on)
         return bool(self.lib.pfann_db_set_prefilter(self.handle, 1 if on else 0))
+
+    def search_plan(self, nq, k, phase=0, resume_with_lb=False, mtop=1):
+        """What search (phase 0), search_bound (1, mtop = its m) or search_bounded (2; resume_with_lb: behind the
+        search_bound of the same q) launches for nq query rows against this shard, from pfann_search_plan: ->
+        (stages, flags), stages = [(kernel, grid, block, dynamic LDS bytes)] in launch order, flags = the dict of the last
+        line (path, q_prep, fallback, canonical_scores, ...).  No GPU work."""
+        if self.storage == "f16":
+            storage = 2
+        else:
+            storage = 1 if self.lib.pfann_db_set_prefilter(self.handle, 1 if self._prefilter else 0) else 0
+        return search_plan(self.ntotal, self.d, nq, k, storage, phase, resume_with_lb, mtop)
 
     def _stream(self):
         return _l.current_stream_ptr(self.device)

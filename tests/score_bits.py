@@ -9,28 +9,35 @@ SMALL_MAX_ROWS = 8192         # CAP (csrc/search_common.h): the small path's den
 
 def rescoring_path(db, q, prefilter=True, storage="f32"):
     """True when search_topk (csrc/search.hip) answers this call through a path whose every score is re-computed in the
-    canonical order:
-      - the shard keeps fp32 rows AND an fp16 copy, and the pre-filter is on: pfann_db_set_prefilter (csrc/api.hip:685-687)
-        hands the copy to search_topk only when it is on; db_load (csrc/api.hip:742-753) makes the copy only for d % 8 == 0
-        and a largest row norm below 1e4;
-      - and then every path re-scores: nq > 32 (the fp16 scan, search_topk's generic ladder / group-maximum pass), nq <= 32
-        with d in {64, 128} (search_small: the fp16 pre-filter for n > CAP, the dense pass + canonical re-scoring for
-        n <= CAP).  nq <= 32 with any other d takes the fp32 MFMA ladder (launch_scan + launch_select): MFMA-order scores.
+    canonical order.  This is the INDEPENDENT statement of that fact: the library's own, the `canonical_scores` flag of its
+    launch plan (csrc/search_plan.h, pfann_search_plan), is asserted equal to it over a sweep of shapes on the CPU
+    (tests/test_search_plan.py) and in every GPU test that calls this.
+      - the shard keeps fp32 rows AND an fp16 copy, and the pre-filter is on: pfann_db_set_prefilter (csrc/api.hip) hands
+        the copy to search_topk only when it is on; pfann_db_load makes the copy only for d % 8 == 0 and a largest row norm
+        below 1e4;
+      - and then every path re-scores: nq > 32 (the fp16 scans: group-maximum pass or survivor ladder), nq <= 32 with d in
+        {64, 128} (the small path: the fp16 pre-filter for n > CAP, the dense pass + canonical re-scoring for n <= CAP).
+        nq <= 32 with any other d takes the fp32 MFMA ladder (scan_emit_kernel + select_kernel): MFMA-order scores.
     An empty shard returns no scores at all (False).  Two A/B switches of the library leave the default dispatch:
-    PFANN_NO_F16_PREFILTER (db_load makes no fp16 copy: the fp32 MFMA ladder everywhere) and PFANN_SMALL_F32 (nq <= 32 and
-    n > CAP stream the fp32 rows with MFMA scores final, search.hip search_topk: small_pre); with either set, the calls it
-    touches are not re-scoring paths."""
-    n, d = db.shape[0], q.shape[1]
-    if storage != "f32" or not prefilter or n == 0 or q.shape[0] == 0 or d % 8 != 0:
+    PFANN_NO_F16_PREFILTER (pfann_db_load makes no fp16 copy: the fp32 MFMA ladder everywhere) and PFANN_SMALL_F32 (nq <= 32
+    and n > CAP stream the fp32 rows with MFMA scores final); with either set, the calls it touches are not re-scoring
+    paths."""
+    n = db.shape[0]
+    xmax = float(np.sqrt((np.asarray(db, np.float64) ** 2).sum(1)).max()) if n and db.shape[1] % 8 == 0 else 0.0
+    return rescoring_path_of_shape(n, q.shape[1], q.shape[0], xmax, prefilter, storage)
+
+
+def rescoring_path_of_shape(n, d, nq, xmax, prefilter=True, storage="f32"):
+    """rescoring_path from the shapes and the largest row norm alone."""
+    if storage != "f32" or not prefilter or n == 0 or nq == 0 or d % 8 != 0:
         return False
     if os.environ.get("PFANN_NO_F16_PREFILTER") is not None:
         return False
-    if os.environ.get("PFANN_SMALL_F32") is not None and q.shape[0] <= 32 and n > SMALL_MAX_ROWS:
+    if os.environ.get("PFANN_SMALL_F32") is not None and nq <= 32 and n > SMALL_MAX_ROWS:
         return False
-    xmax = float(np.sqrt((np.asarray(db, np.float64) ** 2).sum(1)).max())
     if not xmax < 1e4:
         return False
-    return q.shape[0] > 32 or d in (64, 128)
+    return nq > 32 or d in (64, 128)
 
 
 def canonical_topk(q, db, k):

@@ -375,7 +375,7 @@ def test_missing_weights_fail_loudly(torch_cuda):
 
 
 # -------------------------------------------------------------------------------- search
-def _check_topk(torch, db, q, k, prefilter=True):
+def _check_topk(torch, db, q, k, prefilter=True, path=None, kernels=()):
     from oracle import search as osr
     from pfann_amd.database import DeviceIndex
     d = q.shape[1]
@@ -405,8 +405,13 @@ def _check_topk(torch, db, q, k, prefilter=True):
     # reported scores belong to the reported labels
     chk = np.einsum("qkd,qd->qk", db[I[:, :n].clip(0)], q)
     assert np.abs(chk - D[:, :n]).max() < 2e-6
-    # on a re-scoring path (tests/score_bits.py: rescoring_path follows search_topk's dispatch) the scores are the canonical
-    # fp32 bits and the labels the canonical top-k, ties included
+    # on a re-scoring path (tests/score_bits.py: rescoring_path states search_topk's dispatch independently of the library's
+    # own plan, csrc/search_plan.h, and the two must agree) the scores are the canonical fp32 bits and the labels the
+    # canonical top-k, ties included
+    stages, flags = idx.search_plan(q.shape[0], k)
+    assert rescoring_path(db, q, prefilter) == (flags["canonical_scores"] == "1"), flags
+    assert path is None or flags["path"] == path, flags
+    assert not [kn for kn in kernels if kn not in [s[0] for s in stages]], stages
     if rescoring_path(db, q, prefilter):
         assert_canonical_topk(D, I, q, db, k, what="n=%d d=%d nq=%d k=%d" % (db.shape[0], d, q.shape[0], k))
     return D, I
@@ -467,7 +472,10 @@ def test_search_topk_mid_batch_takes_the_query_stationary_kernels(torch_cuda, n,
     q = synth.unit_rows(52, "t/mbq%d" % n, nq, d)
     q[::2] = db[(np.arange(len(q[::2])) * 7919) % n] + 0.5 * q[::2]
     q /= np.linalg.norm(q, axis=1, keepdims=True)
-    _check_topk(torch_cuda, db.astype(np.float32), q.astype(np.float32), 100, True)
+    # (three tile buffers: at most 256 workgroups in the sampled pass, fewer than 768 in the full pass on 64-row db tiles)
+    kernels = {128: ["scan_f16_qres_kernel<8, true, 128, %d>" % (3 if nq <= 304 else 2), "scan_f16_qres_kernel<8, false, 64, 3>"],
+               64: ["scan_f16_qres_kernel<4, true, 128, 2>", "scan_f16_qres_kernel<4, false, 128, 2>"]}[d]
+    _check_topk(torch_cuda, db.astype(np.float32), q.astype(np.float32), 100, True, "gmax", kernels)
 
 
 @pytest.mark.parametrize("nq", [130, 2100])
@@ -1211,13 +1219,15 @@ def test_melspec_is_bit_stable_beside_a_batched_search(torch_cuda):
 
 
 AGGRESSORS = {
-    # name: (d, query rows, db rows) -> the scan-class kernels one search call of that shape launches (csrc/search.hip: search_topk)
-    "d64_qres": (64, 4085, 120000),         # scan_f16_qres_kernel<4,true> (sampled pass) + scan_f16_qres_kernel<4> (full pass)
+    # name: (d, query rows, db rows, the scan kernels one search call of that shape launches, in order: asserted from the
+    # plan, csrc/search_plan.h)
+    "d64_qres": (64, 4085, 120000, ["scan_f16_qres_kernel<4, true, 128, 2>", "scan_f16_qres_kernel<4, false, 128, 2>"]),   # sampled, full pass
     # d = 96 (neither 64 nor 128: no query-stationary kernel, no group-maximum pass at any nq): the survivor ladder on
-    # scan_f16_kernel<1> (dense coarsest level, sampled levels) and <4> (full pass).  (At d = 128 and 33 .. 1023 query rows
+    # scan_f16_kernel<1> (dense coarsest level, sampled level) and <4> (full pass).  (At d = 128 and 33 .. 1023 query rows
     # every thresholded pass takes scan_f16_qres_kernel since round 6, k > 128 included: only the dense level would be generic.)
-    "d96_generic": (96, 1000, 300000),
-    "d128_f16_storage": (128, 4085, 120000),  # fp16-only storage: scan_f16_qres_kernel<8,true,128> + <8,false,64>, s16 scores final
+    "d96_generic": (96, 1000, 300000, ["scan_f16_kernel<1>", "scan_f16_kernel<1>", "scan_f16_kernel<4>"]),
+    # fp16-only storage: s16 scores final
+    "d128_f16_storage": (128, 4085, 120000, ["scan_f16_qres_kernel<8, true, 128, 2>", "scan_f16_qres_kernel<8, false, 64, 2>"]),
 }
 
 
@@ -1234,7 +1244,7 @@ def test_melspec_is_bit_stable_beside_every_scan_class_kernel(torch_cuda, aggres
     params = cfg("default")
     if victim == "fft512":
         params.update(stft_n=512, stft_hop=128, n_mels=96)
-    d, nq, n = AGGRESSORS[aggressor]
+    d, nq, n, scans = AGGRESSORS[aggressor]
     eng = Engine(params, 0, max_batch=4096)
     g = torch.Generator(device="cuda")
     g.manual_seed(15)
@@ -1243,6 +1253,7 @@ def test_melspec_is_bit_stable_beside_every_scan_class_kernel(torch_cuda, aggres
     q = torch.nn.functional.normalize(db[:nq] + 0.3 * torch.randn((nq, d), device="cuda", generator=g), dim=1).contiguous()
     ix = DeviceIndex(d, 0, storage="f16") if aggressor == "d128_f16_storage" else DeviceIndex(d, 0)
     ix.load(db, np.array([0, n], np.int64), 0)
+    assert [s[0] for s in ix.search_plan(nq, 100)[0] if s[0].startswith("scan_")] == scans
     quiet = eng.melspec(segs).clone()
     ix.search(q, 100)
     side = torch.cuda.Stream()

@@ -36,9 +36,23 @@ def _search(torch, idx, q, k):
     return D.cpu().numpy(), I.cpu().numpy()
 
 
-def _check(torch, db, q, k, what):
-    assert rescoring_path(db, q)
-    D, I = _search(torch, _index(db), q, k)
+def _assert_plan(idx, nq, k, path, kernels, **phase):
+    """The call takes the path its test was written for: the plan's path and every kernel named (csrc/search_plan.h; the
+    plan itself is held against a kernel trace by tests/test_search_plan.py).  -> the stages' kernel names."""
+    stages, flags = idx.search_plan(nq, k, **phase)
+    names = [s[0] for s in stages]
+    assert flags["path"] == path and flags["error"] == "none", (flags, names)
+    missing = [kn for kn in kernels if kn not in names]
+    assert not missing, "the plan does not launch %s: %s" % (missing, names)
+    return names, flags
+
+
+def _check(torch, db, q, k, what, path, kernels, **want_flags):
+    idx = _index(db)
+    _, flags = _assert_plan(idx, q.shape[0], k, path, kernels)
+    assert rescoring_path(db, q) and flags["canonical_scores"] == "1"
+    assert {f: flags[f] for f in want_flags} == want_flags
+    D, I = _search(torch, idx, q, k)
     return D, I, assert_canonical_topk(D, I, q, db, k, what=what)
 
 
@@ -59,11 +73,15 @@ def _queries(seed, db, nq, mix=0.5):
 @pytest.mark.parametrize("nq", [33, 76, 304, 1000, 2100])
 def test_query_stationary_batches_select_small(torch_cuda, nq, d):
     """nq > 32 at d = 64 / 128 and k <= 128: the group-maximum pass, then the full pass on scan_f16_qres_kernel (nq >= 33 and
-    >= 16 db tiles, csrc/search_f16.hip launch_scan_f16), which leaves ~R k survivors per row (far below SMALL_N = 4096), so
+    >= 16 db tiles, csrc/search_plan.h gmax), which leaves ~R k survivors per row (far below SMALL_N = 4096), so
     every row is selected and re-scored by select_rescore_small_kernel.  One to seventeen query tiles, ragged last tiles."""
     db = _songs(300 + d, 60001, d)
     q = _queries(310 + d, db, nq)
-    _check(torch_cuda, db, q, 100, "query-stationary nq=%d d=%d" % (nq, d))
+    # d = 128: three tile buffers while the grid is at most one workgroup per CU (sampled pass: query tiles x slices <= 256)
+    # / less than one round of the 768 resident ones (full pass, 64-row db tiles)
+    full = "scan_f16_qres_kernel<8, false, 64, %d>" % (3 if nq <= 1000 else 2) if d == 128 else "scan_f16_qres_kernel<4, false, 128, 2>"
+    sampled = "scan_f16_qres_kernel<8, true, 128, %d>" % (3 if nq <= 304 else 2) if d == 128 else "scan_f16_qres_kernel<4, true, 128, 2>"
+    _check(torch_cuda, db, q, 100, "query-stationary nq=%d d=%d" % (nq, d), "gmax", [sampled, full, "select_rescore_small_kernel"])
 
 
 def _big_cluster_db(n=100000, d=128):
@@ -84,7 +102,7 @@ def test_more_than_4096_survivors_select_body(torch_cuda, nq):
     q = synth.unit_rows(53, "t/bigq", nq, 128)
     q[:5] = c + 0.05 * q[:5]
     q = _unit(q)
-    _check(torch_cuda, db, q, 100, "> 4096 survivors nq=%d" % nq)
+    _check(torch_cuda, db, q, 100, "> 4096 survivors nq=%d" % nq, "gmax", ["select_rescore_small_kernel", "select_rescore_kernel"])
 
 
 def test_sublist_overflow_fallback_fp32_rows(torch_cuda):
@@ -100,7 +118,7 @@ def test_sublist_overflow_fallback_fp32_rows(torch_cuda):
     db = _unit(db)
     q = synth.unit_rows(45, "t/ofq", nq, d)
     q[:3] = c + 0.05 * q[:3]
-    _check(torch_cuda, db, _unit(q), 300, "sub-list overflow")
+    _check(torch_cuda, db, _unit(q), 300, "sub-list overflow", "ladder_f16", ["scan_f16_qres_kernel<8, false, 64, 3>", "topk_fallback_kernel<4>"])
 
 
 def _small_path_db(seed, n, d):
@@ -122,7 +140,7 @@ def _small_path_db(seed, n, d):
 
 
 def test_folded_small_path_d128(torch_cuda):
-    """nq <= 32, d = 128, n > 8192: the folded small path (search_small<2>: query preparation in the group-maximum pass,
+    """nq <= 32, d = 128, n > 8192: the folded small path (csrc/search_plan.h small_sampled_folded: query preparation in the group-maximum pass,
     select_rescore_small_kernel, then select_tail_kernel).  Row 0 takes the select half of the tail launch (> 4096
     survivors), row 1 (exact ties overflowing every sub-list) and row 2 (one overflowing sub-list) its fallback half, and a
     query of norm 1e5 -- beyond fp16's range, flagged by the query preparation -- goes to the fallback too; the ordinary rows
@@ -130,39 +148,47 @@ def test_folded_small_path_d128(torch_cuda):
     db, q = _small_path_db(71, 600000, 128)
     q = np.concatenate([q, 1e5 * q[5:6]]).astype(np.float32)
     q[6:10] *= np.float32(7.5)
-    D, I, _ = _check(torch_cuda, db, q, 300, "folded small path")
+    D, I, _ = _check(torch_cuda, db, q, 300, "folded small path", "small_sampled_folded",
+                     ["scan_small_kernel<128, 2, 1>", "scan_small_kernel<128, 2, 0>", "select_rescore_small_kernel", "select_tail_kernel<4>"],
+                     q_prep="folded", fallback="tail")
     assert np.array_equal(I[1], np.arange(50000, 50300))
 
 
 def test_unfolded_small_path_d64(torch_cuda):
-    """nq <= 32, d = 64, n > 8192: the small path one launch per stage -- launch_select_rescore (select_rescore_small_kernel
-    + select_rescore_kernel for row 0's > 4096 survivors) and then launch_topk_fallback for the rows whose sub-lists
+    """nq <= 32, d = 64, n > 8192: the small path one launch per stage -- query preparation, then select_rescore_small_kernel
+    + select_rescore_kernel for row 0's > 4096 survivors, and then topk_fallback_kernel for the rows whose sub-lists
     overflowed (rows 1 and 2)."""
     db, q = _small_path_db(61, 1000000, 64)
-    D, I, _ = _check(torch_cuda, db, q, 300, "unfolded small path")
+    D, I, _ = _check(torch_cuda, db, q, 300, "unfolded small path", "small_sampled",
+                     ["q_prep_kernel", "scan_small_kernel<64, 2, 1>", "scan_small_kernel<64, 2, 0>", "select_rescore_small_kernel",
+                      "select_rescore_kernel", "topk_fallback_kernel<4>"])
     assert np.array_equal(I[1], np.arange(50000, 50300))
 
 
 @pytest.mark.parametrize("d,nq,k", [(128, 40, 300), (128, 70, 1000), (96, 100, 100), (96, 33, 20)])
 def test_generic_ladder(torch_cuda, d, nq, k):
-    """nq > 32 with k > 128 (no group-maximum pass: search_topk's survivor ladder of sampled levels, launch_select_rescore
-    mode 0 for the thresholds, mode 1 at the full pass), and d = 96 (d % 8 == 0 but neither 64 nor 128: the ladder on the
-    generic scan_f16_kernel at any k).  At nq <= 32 a d = 96 search takes the fp32 MFMA ladder instead (search.hip,
-    search_topk: `small` needs d in {64, 128}), which is not a re-scoring path."""
+    """nq > 32 with k > 128 (no group-maximum pass: the survivor ladder of sampled levels, the re-scoring selects in mode 0
+    for the thresholds, mode 1 at the full pass), and d = 96 (d % 8 == 0 but neither 64 nor 128: the ladder on the
+    generic scan_f16_kernel at any k).  At nq <= 32 a d = 96 search takes the fp32 MFMA ladder instead (csrc/search_plan.h:
+    `small` needs d in {64, 128}), which is not a re-scoring path."""
     db = _songs(400 + d + k, 50000, d)
     q = _queries(410 + d + k, db, nq)
-    _check(torch_cuda, db, q, k, "generic ladder d=%d nq=%d k=%d" % (d, nq, k))
+    _check(torch_cuda, db, q, k, "generic ladder d=%d nq=%d k=%d" % (d, nq, k), "ladder_f16",
+           ["fill_int2_kernel", "scan_f16_kernel<1>", "select_rescore_small_kernel"])
+    scans = [s for s in _index(db).search_plan(nq, k)[0] if s[0].startswith("scan_")]
+    assert len(scans) >= 2 and (d == 128 or all(s[0] == "scan_f16_kernel<1>" for s in scans))
 
 
 def test_dense_small_shard(torch_cuda):
     """nq <= 32, d in {64, 128}, n <= 8192 with an fp16 copy: the dense single pass scores every row with fp32 MFMA, and the
-    select re-scores every row within the MFMA-vs-canonical bound of the k-th score (search.hip, dense_canon_eps_kernel +
-    launch_select_rescore): canonical bits, as at every other shard size.  n <= 4096 takes select_rescore_small_kernel,
-    4096 < n <= 8192 with k near n select_rescore_kernel."""
+    select re-scores every row within the MFMA-vs-canonical bound of the k-th score, computed in the kernel
+    (csrc/search_f16.hip dense_canon_eps): canonical bits, as at every other shard size.  n <= 4096 takes
+    select_dense_small_kernel, 4096 < n <= 8192 select_dense_kernel."""
     for d, n, nq, k in [(128, 7, 19, 100), (128, 5000, 19, 100), (64, 8192, 5, 1), (128, 8192, 32, 1000), (64, 3000, 1, 20)]:
         db = _songs(500 + n + d, n, d, run=20)
         q = _queries(510 + n + d, db, nq)
-        _check(torch_cuda, db, q, k, "dense small shard n=%d d=%d nq=%d k=%d" % (n, d, nq, k))
+        _check(torch_cuda, db, q, k, "dense small shard n=%d d=%d nq=%d k=%d" % (n, d, nq, k), "small_dense",
+               ["scan_small_kernel<%d, 4, 2>" % d, "select_dense_small_kernel" if n <= 4096 else "select_dense_kernel"])
 
 
 def test_margin_non_unit_norms(torch_cuda):
@@ -179,7 +205,7 @@ def test_margin_non_unit_norms(torch_cuda):
     q /= np.linalg.norm(q, axis=1, keepdims=True)
     q *= 25.0
     q[50] *= 12000.0
-    _check(torch_cuda, base.astype(np.float32), q.astype(np.float32), 100, "margin")
+    _check(torch_cuda, base.astype(np.float32), q.astype(np.float32), 100, "margin", "gmax", ["topk_fallback_kernel<4>"])
 
 
 def _shards(db, cuts):
@@ -221,6 +247,9 @@ def test_bounded_second_phase(torch_cuda):
     q_t = torch.as_tensor(q).cuda()
     for j, (lo, hi) in enumerate(zip(cuts[:-1], cuts[1:])):
         ix, part = shards[j], db[lo:hi]
+        _assert_plan(ix, nq, k, "gmax", ["group_max_select_kernel"], phase=1, mtop=min(k, 2 * k // 3 + 8))
+        _assert_plan(ix, nq, k, "gmax", ["bound_in_kernel", "select_rescore_wave_kernel", "select_rescore_small_list_kernel",
+                                         "select_rescore_list_kernel"], phase=2, resume_with_lb=True)
         Dl, Il = _search(torch, ix, q, k)
         wl = canonical_topk(q, part, k)
         wl = (wl[0], np.where(wl[1] >= 0, wl[1] + lo, -1))
@@ -262,6 +291,9 @@ def test_one_row_same_bits_on_every_path(torch_cuda):
     others = _queries(92, db, 2100)
     want = canonical_topk(rows, db, k)
     whole = _index(db)
+    _assert_plan(whole, 1, k, "small_sampled_folded", ["select_tail_kernel<4>"])
+    for nq in (100, 2100):
+        _assert_plan(whole, nq, k, "gmax", ["scan_f16_qres_kernel<8, false, 64, %d>" % (3 if nq == 100 else 2)])
     runs = []
     for j in range(2):
         D, I = _search(torch, whole, rows[j:j + 1], k)
