@@ -309,6 +309,31 @@ int pfann_match(pfann_db *db, const float *q_dev, const int64_t *labels_dev, int
 #define PFANN_MATCH_ONLY_OWNED 1
 #define PFANN_MATCH_OWNED_BLOCK 2
 
+/* Ranked answers: the n best SONGS of every query, 1 <= n <= 64 (anything else: -1 with a message), selected on the
+ * device from the matcher's own candidate list -- no [nQ][n_songs] block exists.  Asynchronous on `stream`, never
+ * synchronises with the host.  top_dev[nQ][n]; n_found_dev[nQ] may be NULL.
+ *   Candidates, order and scores are exactly those of pfann_match for the same arguments.  mode 0: candidates ordered by
+ *     (shift, song, offset), score = fp32 dot / sub_len in double.  mode 1: ordered by (song, offset, shift), score = the
+ *     fp32 score, score_alpha honoured.  only_owned bit 0 restricts candidates to the shard's songs; bit 1
+ *     (PFANN_MATCH_OWNED_BLOCK) has no meaning here and is rejected (-1).
+ *   Per-song best: among a song's candidates the first one in candidate order with the largest score wins, compared with
+ *     a strict > in double -- the rule of the result argmax, not the float32 comparison of the per-song block.
+ *   Ranking: songs by score descending; ties go to the song whose best candidate comes first in candidate order.
+ *   Entry i of a query is the i-th song of that ranking: song, offset, shift and score of that song's best candidate;
+ *     n_cand = the number of distinct candidates of that song (how many alignments voted for it).
+ *   Entry 0 therefore equals pfann_match's result in song, offset, shift and score.
+ *   Padding: entries beyond the number of candidate songs are {song -1, offset 0, shift 0, n_cand 0, score -inf}.
+ *   n_found[j] = the number of distinct candidate songs of query j, not capped at n.
+ *   A query longer than max_qlen is refused: entry 0 gets song = -2 (and n_cand = -1, as in pfann_match), the rest are
+ *     padding, n_found = -1.
+ *   fp32 and fp16 storage are both supported, and -- as with pfann_match, whose launch plans and thresholds this call
+ *     shares -- a result's bits do not depend on which launch plan served the call. */
+int pfann_match_topn(pfann_db *db, const float *q_dev, const int64_t *labels_dev, int k,
+                     const int64_t *qstart_dev, const int32_t *qlen_dev, int64_t nQ, int max_qlen,
+                     int frame_shift_mul, float score_alpha, int mode, int only_owned, int n,
+                     pfann_match_result *top_dev /* [nQ][n] */, int32_t *n_found_dev /* [nQ], may be NULL */,
+                     void *stream);
+
 /* Monitor mode: the sequence matcher over EVERY window of nR long recordings, given the labels of all their rows.
  * Recording r owns rows [rstart[r], rstart[r]+rlen[r]) of q_dev / labels_dev[.][k].  Its windows start at rows 0, hop,
  * 2*hop, ... while w0 + window <= rlen[r]; a recording with 0 < rlen < window has exactly one window that covers all its

@@ -1,10 +1,14 @@
 #!/usr/bin/env python
-"""Drop-in for the reference's `python matcher.py <query list> <db dir> <result file>`."""
+"""Drop-in for the reference's `python matcher.py <query list> <db dir> <result file>` (optional: --top N, --no-bin)."""
 import sys
 
 from pfann_amd import launch, prewarm
 
 if __name__ == "__main__":
+    _err = launch.matcher_flags(sys.argv[4:])[2]       # a bad --top / --no-bin ends here, before anything is launched
+    if _err:
+        print(_err, file=sys.stderr)
+        sys.exit(2)
     _rc = launch.self_launch_if_asked(sys.argv)      # PFANN_GPUS=N: N ranks of this command, one per GPU (no torch import yet)
     if _rc is not None:
         sys.exit(_rc)

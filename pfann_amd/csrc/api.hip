@@ -838,9 +838,13 @@ int pfann_topk_merge_lists(pfann_db *db, const float *D_lists_dev, const int64_t
     return merge_lists(D_lists_dev, I_lists_dev, n_lists, nq, k, D_dev, I_dev, (hipStream_t)stream);
 }
 
-int pfann_match(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *qstart,
-                const int32_t *qlen, int64_t nQ, int max_qlen, int frame_shift_mul, float score_alpha, int mode,
-                int only_owned, pfann_match_result *results, float *song_scores, void *stream) {
+}  // extern "C"
+
+// pfann_match and pfann_match_topn: one set-up, one launch plan (topn == 0: the single answer and the per-song block)
+static int match_call(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *qstart,
+                      const int32_t *qlen, int64_t nQ, int max_qlen, int frame_shift_mul, float score_alpha, int mode,
+                      int only_owned, pfann_match_result *results, float *song_scores, int topn, pfann_match_result *top,
+                      int32_t *n_found, void *stream) {
     PF_HIP(hipSetDevice(db->device));
     // the contiguous scoring path reads rows as float4 / four halves (rerank.hip), like the search (search.hip: search_topk)
     if (db->d % 4 != 0) { set_error("match: d %% 4 != 0 (d=%d)", db->d); return -1; }
@@ -880,7 +884,28 @@ int pfann_match(pfann_db *db, const float *q, const int64_t *labels, int k, cons
         if (phased) { a.ncand = reinterpret_cast<int *>(a.gscore + (size_t)nQ * P); a.phase = 1; }
     }
     a.results = results; a.song_scores = song_scores;
+    a.topn = topn; a.top = top; a.n_found = n_found;
     return launch_match(a, (hipStream_t)stream);
+}
+
+extern "C" {
+
+int pfann_match(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *qstart,
+                const int32_t *qlen, int64_t nQ, int max_qlen, int frame_shift_mul, float score_alpha, int mode,
+                int only_owned, pfann_match_result *results, float *song_scores, void *stream) {
+    return match_call(db, q, labels, k, qstart, qlen, nQ, max_qlen, frame_shift_mul, score_alpha, mode, only_owned, results,
+                      song_scores, 0, nullptr, nullptr, stream);
+}
+
+int pfann_match_topn(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *qstart,
+                     const int32_t *qlen, int64_t nQ, int max_qlen, int frame_shift_mul, float score_alpha, int mode,
+                     int only_owned, int n, pfann_match_result *top, int32_t *n_found, void *stream) {
+    if (n < 1 || n > 64) { set_error("match_topn: n=%d outside 1..64", n); return -1; }
+    if (mode != 0 && mode != 1) { set_error("match_topn: unknown mode %d", mode); return -1; }
+    if (only_owned & ~1) { set_error("match_topn: only_owned=%d (the owned-songs score block has no meaning here)", only_owned); return -1; }
+    if (top == nullptr) { set_error("match_topn: top_dev is null"); return -1; }
+    return match_call(db, q, labels, k, qstart, qlen, nQ, max_qlen, frame_shift_mul, score_alpha, mode, only_owned, nullptr,
+                      nullptr, n, top, n_found, stream);
 }
 
 int pfann_match_windows(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart, const int32_t *rlen,

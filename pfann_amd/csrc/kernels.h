@@ -115,6 +115,8 @@ struct RerankArgs {
     int phase;              // 0: whole query in one workgroup; 1: candidates; 2: scores; 3: argmax (1-3 need gkeys)
     pfann_match_result *results; float *song_scores;
     int ss_lo, ss_n;        // the song_scores block of one query covers songs [ss_lo, ss_lo + ss_n): all, or the owned ones
+    // pfann_match_topn (topn > 0: results and song_scores are null): top[nQ][topn] ranked songs, n_found[nQ] or null
+    int topn = 0; pfann_match_result *top = nullptr; int *n_found = nullptr;
 };
 int launch_match(const RerankArgs &a, hipStream_t s);
 int launch_match_pack(const pfann_match_result *res, int64_t nQ, unsigned long long *keys, hipStream_t s);

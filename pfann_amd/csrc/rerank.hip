@@ -85,7 +85,9 @@ __global__ __launch_bounds__(NT) void match_rank_kernel(RerankArgs a) {
     const int SL = a.pmax / G;                    // slice length when P == pmax; shorter queries use fewer slices
     if (P > a.pmax) {
         if (tid == 0 && blockIdx.y == 0) {
-            pfann_match_result r; r.song = -2; r.offset = 0; r.shift = 0; r.n_cand = -1; r.score = -INFINITY; a.results[qi] = r;
+            if (a.results != nullptr) {           // (a top-N call has none: its phase 3 writes the refusal)
+                pfann_match_result r; r.song = -2; r.offset = 0; r.shift = 0; r.n_cand = -1; r.score = -INFINITY; a.results[qi] = r;
+            }
             a.ncand[qi] = -1;
         }
         return;
@@ -120,7 +122,122 @@ __global__ __launch_bounds__(NT) void match_rank_kernel(RerankArgs a) {
     if (blockIdx.y == 0 && tid == 0) a.ncand[qi] = s_cnt;
 }
 
+// ---- ranked top-N songs (pfann_match_topn): the selection stage that replaces the argmax ------------------------------
+// Same list, same scores, same candidate order as the argmax below.  Entry r is found by pass r of a block-wide first-wins
+// strict-> argmax (score as double, list index) over the candidates whose song no earlier pass selected: that candidate is
+// its song's best by the argmax's own rule, and a tie between two songs goes to the one whose best candidate comes first.
+// Pass r + 1 retires every candidate of the song pass r selected (a marker in its score slot -- a thread only ever reads and
+// writes the slots of its own candidates) and counts the distinct ones: the entry's n_cand.  A song that recurs once per
+// shift (mode 0, frame_shift_mul > 1) needs nothing extra: its runs are retired by song id, in parallel.  One barrier per
+// pass; n + 1 passes at most, fewer when the songs run out.  Pass 0's spare count is n_found (distinct songs).
+static constexpr unsigned TOPN_RETIRED = 0xFFFFFFFFu;      // a NaN: a slot that holds it by itself never wins either
+
+__device__ __forceinline__ int song_of_key(int mode, unsigned long long key) {
+    return mode == 0 ? (int)((key >> 28) & 0x3FFFFFFFull) : (int)(key >> 34);
+}
+__device__ __forceinline__ pfann_match_result topn_padding() {
+    pfann_match_result r; r.song = -1; r.offset = 0; r.shift = 0; r.n_cand = 0; r.score = -INFINITY;
+    return r;
+}
 template <int NT>
+__device__ void topn_refuse(const RerankArgs &a, int64_t qi, int tid) {
+    pfann_match_result *top = a.top + qi * a.topn;
+    for (int i = tid; i < a.topn; i += NT) {
+        pfann_match_result r = topn_padding();
+        if (i == 0) { r.song = -2; r.n_cand = -1; }       // entry 0 is pfann_match's refusal
+        top[i] = r;
+    }
+    if (tid == 0 && a.n_found != nullptr) a.n_found[qi] = -1;
+}
+// is list position c the first one of its song?  (sorted list sk[0..nc), possibly with repeated keys)
+__device__ __forceinline__ bool first_of_song(const RerankArgs &a, const unsigned long long *sk, int nc, int c, unsigned long long key) {
+    const int pre = a.mode == 0 ? 28 : 34;                  // key >> pre = (shift, song) / song: one run of the list
+    if (c > 0 && (sk[c - 1] >> pre) == (key >> pre)) return false;
+    if (a.mode != 0 || a.fsm == 1) return true;
+    // mode 0 orders by (shift, song, offset): the song may have a run under every smaller shift
+    const unsigned long long song = (key >> 28) & 0x3FFFFFFFull;
+    const int shift = (int)(key >> 58);
+    for (int s = 0; s < shift; ++s) {
+        const unsigned long long want = ((unsigned long long)s << 30) | song;       // (shift, song) of that run
+        int lo = 0, hi = nc;                                 // first position whose (shift, song) is >= want
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((sk[mid] >> 28) < want) lo = mid + 1; else hi = mid;
+        }
+        if (lo < nc && (sk[lo] >> 28) == want) return false;
+    }
+    return true;
+}
+template <int NT>
+__device__ void select_topn(const RerankArgs &a, int64_t qi, int qlen, const unsigned long long *sk, float *score, int nc, int tid) {
+    constexpr int NW = NT / 64;
+    __shared__ double s_best[2][NW];
+    __shared__ int s_besti[2][NW], s_cnt[2][NW];
+    const int lane = tid & 63, wave = tid >> 6;
+    pfann_match_result *top = a.top + qi * a.topn;
+    int last_song = -1, r = 0;
+    for (;; ++r) {
+        const bool want = r < a.topn;
+        double best = -INFINITY;
+        int besti = 0x7FFFFFFF, cnt = 0;
+        for (int c = tid; c < nc; c += NT) {
+            const unsigned long long key = sk[c];
+            const bool distinct = c == 0 || sk[c - 1] != key;       // (the rank-sorted list keeps its repeats)
+            if (r == 0) {
+                cnt += (distinct && first_of_song(a, sk, nc, c, key)) ? 1 : 0;
+            } else if (song_of_key(a.mode, key) == last_song) {
+                cnt += distinct ? 1 : 0;
+                score[c] = __uint_as_float(TOPN_RETIRED);
+                continue;
+            }
+            if (!want) continue;
+            const float sc = score[c];
+            if (__float_as_uint(sc) == TOPN_RETIRED) continue;
+            double sco;
+            if (a.mode == 0) {
+                const int shift = (int)(key >> 58);
+                const int sub_len = (qlen - shift + a.fsm - 1) / a.fsm;
+                sco = (double)sc / (double)sub_len;
+            } else {
+                sco = (double)sc;
+            }
+            if (sco > best) { best = sco; besti = c; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ob = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(besti, o, 64);
+            cnt += __shfl_xor(cnt, o, 64);
+            if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        }
+        const int b = r & 1;         // two buffers: pass r + 1 may write while a slow wave still reads pass r
+        if (lane == 0) { s_best[b][wave] = best; s_besti[b][wave] = besti; s_cnt[b][wave] = cnt; }
+        __syncthreads();
+        best = s_best[b][0]; besti = s_besti[b][0]; cnt = s_cnt[b][0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) {
+            const double ob = s_best[b][w];
+            const int oi = s_besti[b][w];
+            cnt += s_cnt[b][w];
+            if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        }
+        if (tid == 0) {
+            if (r > 0) top[r - 1].n_cand = cnt;
+            else if (a.n_found != nullptr) a.n_found[qi] = cnt;
+        }
+        if (!want || besti == 0x7FFFFFFF) break;
+        const Cand cd = unpack_cand(a.mode, sk[besti]);
+        if (tid == 0) {
+            pfann_match_result e;
+            e.song = cd.song; e.offset = cd.off; e.shift = cd.shift; e.n_cand = 0; e.score = best;
+            top[r] = e;
+        }
+        last_song = cd.song;
+    }
+    for (int i = r + tid; i < a.topn; i += NT) top[i] = topn_padding();
+}
+
+template <int NT, bool TOPN>
 __global__ __launch_bounds__(NT) void match_kernel(RerankArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long sk_lds[];   // [P] keys
     __shared__ int s_nc;
@@ -133,6 +250,10 @@ __global__ __launch_bounds__(NT) void match_kernel(RerankArgs a) {
     int P = 1;
     while (P < ntot) P <<= 1;
     if (P > a.pmax) {   // host sized the buffers for max_qlen: refuse rather than overrun
+        if constexpr (TOPN) {
+            if (a.phase != 2) topn_refuse<NT>(a, qi, tid);    // (phase 3 too: the rank-sorted phase 1 has no results[] to write)
+            if (tid == 0 && a.phase == 1) a.ncand[qi] = -1;
+        } else
         if (tid == 0 && a.phase <= 1) {
             pfann_match_result r; r.song = -2; r.offset = 0; r.shift = 0; r.n_cand = -1; r.score = -INFINITY; a.results[qi] = r;
             if (a.phase == 1) a.ncand[qi] = -1;
@@ -287,6 +408,10 @@ __global__ __launch_bounds__(NT) void match_kernel(RerankArgs a) {
     }
     if (a.phase == 2) return;
     __syncthreads();
+    if constexpr (TOPN) {
+        select_topn<NT>(a, qi, qlen, sk, score, nc, tid);
+        return;
+    }
     int n_unique = nc;
     if (a.phase == 3) {                  // the rank-sorted list of the phased launch keeps its duplicates: count the distinct keys
         if (tid == 0) s_nc = 0;
@@ -453,11 +578,14 @@ int launch_match_pick(const unsigned long long *keys, int G, int64_t nQ, pfann_m
     return 0;
 }
 
-int launch_match(const RerankArgs &a, hipStream_t s) {
+template <bool TOPN>
+static int launch_match_as(const RerankArgs &a, hipStream_t s) {
     if (a.nQ <= 0) return 0;
+    if (TOPN != (a.topn > 0) || (TOPN && (a.top == nullptr || a.topn > 64))) { set_error("match: top-N arguments (n=%d)", a.topn); return -1; }
     if (a.fsm < 1 || a.fsm > 32) { set_error("match: frame_shift_mul=%d outside 1..32", a.fsm); return -1; }
     if (a.n_songs >= (1 << 30)) { set_error("match: too many songs"); return -1; }
-    if (ensure_dyn_lds((const void *)match_kernel<1024>, MAXC * 12)) return -1;
+    constexpr auto kern = match_kernel<1024, TOPN>;
+    if (ensure_dyn_lds((const void *)kern, MAXC * 12)) return -1;
     if (a.pmax > MAXC && a.gkeys == nullptr) {
         set_error("match: max_qlen*top_k needs %d candidate slots > %d and no scratch was given", a.pmax, MAXC);
         return -1;
@@ -470,14 +598,14 @@ int launch_match(const RerankArgs &a, hipStream_t s) {
         RerankArgs b = a;
         { ProfScope p1("seq_match p1 candidates", s);
           if (rank_p1) PF_LAUNCH(match_rank_kernel<1024>, dim3((unsigned)a.nQ, 32), dim3(1024), (size_t)a.pmax * 8, s, b);
-          else PF_LAUNCH(match_kernel<1024>, dim3((unsigned)a.nQ), dim3(1024), a.pmax <= MAXC ? (size_t)a.pmax * 12 : 64, s, b); }
+          else PF_LAUNCH(kern, dim3((unsigned)a.nQ), dim3(1024), a.pmax <= MAXC ? (size_t)a.pmax * 12 : 64, s, b); }
         b.phase = 2;
         const unsigned chunks = (unsigned)std::min<int64_t>((a.pmax + 15) / 16, std::max<int64_t>(1, 2048 / a.nQ));
         { ProfScope p2("seq_match p2 scores", s);
-          PF_LAUNCH(match_kernel<1024>, dim3((unsigned)a.nQ, chunks), dim3(1024), 64, s, b); }
+          PF_LAUNCH(kern, dim3((unsigned)a.nQ, chunks), dim3(1024), 64, s, b); }
         b.phase = 3;
         { ProfScope p3("seq_match p3 argmax", s);
-          PF_LAUNCH(match_kernel<1024>, dim3((unsigned)a.nQ), dim3(1024), 64, s, b); }
+          PF_LAUNCH(kern, dim3((unsigned)a.nQ), dim3(1024), 64, s, b); }
         PF_HIP(hipGetLastError());
         return 0;
     }
@@ -487,25 +615,29 @@ int launch_match(const RerankArgs &a, hipStream_t s) {
         RerankArgs b = a;
         if (rank_p1) PF_LAUNCH(match_rank_kernel<1024>, dim3((unsigned)a.nQ, 32), dim3(1024), (size_t)a.pmax * 8, s, b);
         else
-        PF_LAUNCH(match_kernel<1024>, dim3((unsigned)a.nQ), dim3(1024), a.pmax <= MAXC ? (size_t)a.pmax * 12 : 64, s, b);
+        PF_LAUNCH(kern, dim3((unsigned)a.nQ), dim3(1024), a.pmax <= MAXC ? (size_t)a.pmax * 12 : 64, s, b);
         b.phase = 2;
         const unsigned chunks = (unsigned)std::min<int64_t>((a.pmax + 15) / 16, std::max<int64_t>(1, 2048 / a.nQ));
-        PF_LAUNCH(match_kernel<1024>, dim3((unsigned)a.nQ, chunks), dim3(1024), 64, s, b);
+        PF_LAUNCH(kern, dim3((unsigned)a.nQ, chunks), dim3(1024), 64, s, b);
         b.phase = 3;
-        PF_LAUNCH(match_kernel<1024>, dim3((unsigned)a.nQ), dim3(1024), 64, s, b);
+        PF_LAUNCH(kern, dim3((unsigned)a.nQ), dim3(1024), 64, s, b);
         PF_HIP(hipGetLastError());
         return 0;
     }
     if (a.gkeys != nullptr) {
-        PF_LAUNCH(match_kernel<1024>, dim3((unsigned)a.nQ), dim3(1024), 64, s, a);
+        PF_LAUNCH(kern, dim3((unsigned)a.nQ), dim3(1024), 64, s, a);
         PF_HIP(hipGetLastError());
         return 0;
     }
     // 16 waves per query: candidate scoring is a latency-bound gather (<= 19 dependent-free row loads
     // per candidate), so more waves in flight per query is what shortens it
-    PF_LAUNCH(match_kernel<1024>, dim3((unsigned)a.nQ), dim3(1024), (size_t)a.pmax * 12, s, a);
+    PF_LAUNCH(kern, dim3((unsigned)a.nQ), dim3(1024), (size_t)a.pmax * 12, s, a);
     PF_HIP(hipGetLastError());
     return 0;
+}
+
+int launch_match(const RerankArgs &a, hipStream_t s) {
+    return a.topn > 0 ? launch_match_as<true>(a, s) : launch_match_as<false>(a, s);
 }
 
 // pfann_prewarm: one empty launch per translation unit makes the runtime load this unit's code object now

@@ -288,6 +288,39 @@ class DeviceIndex:
             return out, ss
         return self.results_to_host(res), ss
 
+    def topn_to_host(self, top_dev, n_found_dev):
+        """device top-N lists (uint8 [nQ, n, 24]) and counts -> (structured array [nQ, n], int32 [nQ])"""
+        nQ, n = top_dev.shape[0], top_dev.shape[1]
+        out = np.frombuffer(top_dev.cpu().numpy().tobytes(), dtype=self.RESULT_DTYPE).reshape(nQ, n)
+        if (out["song"] == -2).any():
+            raise _l.PfannError("matcher refused a query (candidate buffer sizing error)")
+        return out, n_found_dev.cpu().numpy()
+
+    def match_topn(self, q, labels, qstart, qlen, n, fsm=1, alpha=0.0, mode=0, only_owned=False, to_host=True):
+        """Ranked answers (pfann_match_topn): the n best songs of each of nQ queries, selected on the device -- no per-song
+        block.  -> (structured array [nQ, n] of RESULT_DTYPE, n_found int32 [nQ]); entry [j, 0] is `match`'s answer,
+        entries past the candidate songs are song -1 / score -inf; with to_host=False the two device tensors (uint8
+        [nQ, n, 24], int32 [nQ]) that topn_to_host turns into the arrays later."""
+        q = q.to(self.device, torch.float32).contiguous()
+        labels = labels.to(self.device, torch.int64).contiguous()
+        qs_np = np.ascontiguousarray(qstart, dtype=np.int64)
+        ql_np = np.ascontiguousarray(qlen, dtype=np.int32)
+        nQ, n = int(ql_np.shape[0]), int(n)
+        if not 1 <= n <= 64:
+            raise _l.PfannError("match_topn: n=%d outside 1..64" % n)
+        qs = _l.upload_async(qs_np, self.device, np.int64)
+        ql = _l.upload_async(ql_np, self.device, np.int32)
+        top = torch.empty((nQ, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        n_found = torch.empty((nQ,), device=self.device, dtype=torch.int32)
+        if nQ:
+            _l.check(self.lib.pfann_match_topn(self.handle, q.data_ptr(), labels.data_ptr(), labels.shape[1], qs.data_ptr(),
+                                               ql.data_ptr(), nQ, int(ql_np.max()), int(fsm), float(alpha), int(mode),
+                                               1 if only_owned else 0, n, top.data_ptr(), n_found.data_ptr(), self._stream()),
+                     "pfann_match_topn")
+        if not to_host:
+            return top, n_found
+        return self.topn_to_host(top, n_found)
+
     def match_windows(self, q, labels, rstart, rlen, window, hop, fsm=1, alpha=0.0, mode=0, to_host=True):
         """Sequence matcher over every window of nR recordings (pfann_match_windows): recording r owns rows
         [rstart[r], rstart[r] + rlen[r]) of q / labels.  -> (results, wfirst): window i of recording r -- rows
@@ -440,7 +473,7 @@ class Database:
         if self.sharded is not None and self.sharded.xs is not None:
             engine.before_front_end = self.sharded.hold_front_end
 
-    def warmup(self, rows=19 * 64):
+    def warmup(self, rows=19 * 64, want_song_scores=True, topn=0):
         """throw-away queries through search + match: kernel code objects and scratch buffers exist afterwards.  rows: the
         largest number of query rows one launch group will bring (the matcher: PFANN_MAX_BATCH) -- the search workspace is
         sized by it, and growing it later means a hipFree, which waits for everything in flight: the first full group of
@@ -448,10 +481,14 @@ class Database:
         if int(self.song_pos[-1]):                   # (the WHOLE database: under ranks every rank must come along)
             q = torch.zeros((19, self.d), device=self.index.device)
             q[:, 0] = 1.0
-            self.query_finish(self.query_launch(q, [0], [19], want_song_scores=True))
+            self.query_finish(self.query_launch(q, [0], [19], want_song_scores=want_song_scores))
             nq = max(1, int(rows) // 19)
             big = torch.cat([q] * nq)                # (also loads torch's concatenation kernel, which the CLIs use per group)
-            self.query_finish(self.query_launch(big, np.arange(nq) * 19, [19] * nq, want_song_scores=True), reuse_buffers=True)
+            self.query_finish(self.query_launch(big, np.arange(nq) * 19, [19] * nq, want_song_scores=want_song_scores),
+                              reuse_buffers=True)
+            if topn:                                 # (matcher.py --top: the top-N instantiation of the matcher, both plans)
+                self.query_topn_batch(q, [0], [19], topn)
+                self.query_topn_batch(big, np.arange(nq) * 19, [19] * nq, topn)
 
     # ---- batched form ------------------------------------------------------------------
     def query_launch(self, emb, qstart, qlen, want_song_scores=False, mode=None):
@@ -560,6 +597,77 @@ class Database:
     def query_batch(self, emb, qstart, qlen, want_song_scores=False, mode=None):
         """emb: torch cuda [sum(qlen), d] unit-norm rows; -> list of (score, (song, time), song_score|None)."""
         return self.query_finish(self.query_launch(emb, qstart, qlen, want_song_scores, mode))
+
+    # ---- ranked answers: the n best songs per query, no per-song block --------------------------------
+    def query_topn_launch(self, emb, qstart, qlen, n, mode=None):
+        """First half of query_topn_batch: search + top-N sequence match (pfann_match_topn) launched asynchronously."""
+        if self.ranks is not None:
+            raise _l.PfannError("top-N over a sharded database is not supported")
+        if mode is None:
+            mode = 1 if cpp_accelerate else 0
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        D, I = self.index.search(emb, self.top_k)
+        ev[1].record()
+        top, n_found = self.index.match_topn(emb, I, qstart, qlen, n, self.frame_shift_mul, self.score_alpha, mode,
+                                             False, to_host=False)
+        ev[2].record()
+        return {"top": top, "n_found": n_found, "ev": ev, "nq": len(qlen), "keep": (emb, I), "dev": self.index.device,
+                "mode": mode}
+
+    def query_topn_again(self, p, qstart, qlen, n):
+        """the ranked lists of a launch query_launch made (p), from the labels its search left on the device: for a caller
+        that wants the per-song block AND the top-N (the matcher CLI with --top).  -> what query_topn_finish takes"""
+        if self.ranks is not None:
+            raise _l.PfannError("top-N over a sharded database is not supported")
+        emb, I = p["keep"]
+        top, n_found = self.index.match_topn(emb, I, qstart, qlen, n, self.frame_shift_mul, self.score_alpha, p["mode"],
+                                             False, to_host=False)
+        ev = torch.cuda.Event()
+        ev.record()
+        return {"top": top, "n_found": n_found, "ev": [ev], "nq": len(qlen), "keep": p["keep"], "dev": p["dev"], "mode": p["mode"]}
+
+    def query_topn_finish(self, p):
+        """Second half: -> per query a list of up to n (score, (song, time_s)), best first, by the formulas query_finish
+        applies to the winner in the same mode; entry 0 IS query_finish's answer (also when there is no candidate).  Native
+        path (mode 1): later entries whose float32 score is not > 0 are dropped -- the reference's per-song block never
+        records them."""
+        if getattr(self, "_copy_stream", None) is None:
+            self._copy_stream = torch.cuda.Stream(p["dev"])
+            self._pin = {}
+        with torch.cuda.stream(self._copy_stream):
+            self._copy_stream.wait_event(p["ev"][-1])
+            top, _ = self.index.topn_to_host(p["top"], p["n_found"])
+        if self.timer is not None and len(p["ev"]) == 3:
+            self.timer.mark_gpu("search", p["ev"][0], p["ev"][1])
+            self.timer.mark_gpu("rerank", p["ev"][1], p["ev"][2])
+            self.timer.resolve()
+        fsm = self.frame_shift_mul
+        out = []
+        for j in range(p["nq"]):
+            rows = []
+            for i, r in enumerate(top[j]):
+                if i and r["song"] < 0:
+                    break
+                if p["mode"] == 1:
+                    sc32 = float(np.float32(r["score"])) if r["song"] >= 0 else 0.0
+                    if r["song"] < 0 or not sc32 > 0.0:
+                        if i:
+                            continue
+                        rows.append((0.0, (int(r["song"]) if r["song"] >= 0 else -1, 0.0)))
+                    else:
+                        fine = float(np.float32(int(r["offset"]) * fsm - int(r["shift"])))
+                        rows.append((sc32, (int(r["song"]), fine * self.hop_size / fsm)))
+                elif self.index.ntotal == 0 or r["song"] < 0:
+                    rows.append((-1e999, (-1, 0)))
+                else:
+                    rows.append((float(r["score"]), (int(r["song"]), (int(r["offset"]) - int(r["shift"]) / fsm) * self.hop_size)))
+            out.append(rows)
+        return out
+
+    def query_topn_batch(self, emb, qstart, qlen, n, mode=None):
+        """emb: torch cuda [sum(qlen), d] unit-norm rows; -> per query the ranked list of (score, (song, time_s))."""
+        return self.query_topn_finish(self.query_topn_launch(emb, qstart, qlen, n, mode))
 
     # ---- monitor mode: every window of long recordings ----------------------------------------------
     def monitor_launch(self, emb, rstart, rlen, window, hop, edge_window=0):

@@ -89,3 +89,27 @@ def self_launch_if_asked(argv):
     finally:
         for sg, h in old.items():
             signal.signal(sg, h)
+
+
+def matcher_flags(args):
+    """matcher.py's optional arguments after the three positional ones -> (top or 0, no_bin, error message or None).  Lives
+    here because the check runs before anything heavy is imported or launched: a bad value, or either flag in a song-sharded
+    multi-GPU run (PFANN_GPUS / WORLD_SIZE > 1), ends the command with status 2."""
+    top, no_bin, i = 0, False, 0
+    while i < len(args):
+        a = args[i]
+        if a == "--no-bin":
+            no_bin = True
+        elif a == "--top" or a.startswith("--top="):
+            val = a[6:] if a.startswith("--top=") else (args[i + 1] if i + 1 < len(args) else "")
+            i += 0 if a.startswith("--top=") else 1
+            try:
+                top = int(val)
+            except ValueError:
+                top = 0
+            if not 1 <= top <= 64:
+                return 0, no_bin, "matcher: --top takes a number of songs from 1 to 64 (got %r)" % val
+        i += 1
+    if (top or no_bin) and (int(os.environ.get("PFANN_GPUS", "1") or 1) > 1 or int(os.environ.get("WORLD_SIZE", "1") or 1) > 1):
+        return top, no_bin, "matcher: --top and --no-bin are not supported by a song-sharded multi-GPU run (unset PFANN_GPUS)"
+    return top, no_bin, None

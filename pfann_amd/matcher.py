@@ -1,11 +1,18 @@
 """Matcher CLI, drop-in for the reference's matcher.py:
-    python matcher.py <query list> <database dir> <result file>
+    python matcher.py <query list> <database dir> <result file> [--top N] [--no-bin]
 
 Same argv and outputs (matcher.py:34-42,84,158-163): `<result>` TSV "query\\tanswer",
 `<result-stem>_detail.csv` with header query,answer,score,time,part_scores, and
 `<result>.bin` with one float32[n_songs,2] (score, time) block per query; load errors give
 an "error" row with -inf score and a zero block (matcher.py:94-107).  Queries are embedded,
 searched (exact flat IP top-k) and sequence-matched on the MI355X, many queries per launch.
+
+Two optional flags after the three positional arguments (without them every output is what it always was):
+  --top N    (1..64) also write `<result-stem>_top.csv`, header query,rank,answer,score,time: up to N ranked songs per
+             query, rank from 1, selected on the GPU (pfann_match_topn); an unreadable query gets one row name,1,error,-inf,0
+  --no-bin   do not write `<result>.bin` and do not compute the per-song block; with --top no n_queries x n_songs array
+             exists anywhere
+Neither is supported by a song-sharded multi-GPU run (PFANN_GPUS / WORLD_SIZE > 1): exit status 2.
 """
 import csv
 import ctypes
@@ -21,6 +28,7 @@ import torch
 from .builder import embed_file_batches, gather_round
 from .database import Database
 from .dist import finish_ranks, init_ranks, self_launch_if_asked
+from .launch import matcher_flags
 from .engine import Engine
 from .musicdata import MusicDataset
 from .utils import StageTimer, StartupClock, get_logger, init_logger, read_config
@@ -34,8 +42,10 @@ class ResultWriter:
     query's block in place (pwrite) -- the shards' score blocks never travel to another rank, and the file ends up
     byte-identical to the one a single process appends (error rows stay the zeros the file was created with)."""
 
-    def __init__(self, result_file, n_songs, ranks=None, n_queries=0, song_range=None):
+    def __init__(self, result_file, n_songs, ranks=None, n_queries=0, song_range=None, top=False, no_bin=False):
         self.n_songs = n_songs
+        self.no_bin = no_bin
+        self.ftop = None
         self.sharded = ranks is not None and ranks.sharded
         self.text = ranks is None or ranks.rank == 0
         self._run = None            # [address, bytes, arrays kept alive] of the pending run of score blocks
@@ -44,7 +54,13 @@ class ResultWriter:
             self.fout2 = open(os.path.splitext(result_file)[0] + "_detail.csv", "w", encoding="utf8", newline="\n")
             self.detail = csv.writer(self.fout2)
             self.detail.writerow(["query", "answer", "score", "time", "part_scores"])
-        if not self.sharded:
+        if top:
+            self.ftop = open(os.path.splitext(result_file)[0] + "_top.csv", "w", encoding="utf8", newline="\n")
+            self.top = csv.writer(self.ftop)
+            self.top.writerow(["query", "rank", "answer", "score", "time"])
+        if no_bin:
+            pass
+        elif not self.sharded:
             self.fout_score = open(result_file + ".bin", "wb")
         else:
             if ranks.rank == 0:
@@ -58,6 +74,8 @@ class ResultWriter:
         if self.text:
             self.fout.write("%s\t%s\n" % (name, ans))
             self.detail.writerow([name, ans, sco, tim])
+        if self.no_bin:
+            return
         if self.sharded:
             if self.hi > self.lo:                   # this shard's columns of query qi's block
                 blk = memoryview(np.ascontiguousarray(song_score, dtype=np.float32)).cast("B")
@@ -83,8 +101,15 @@ class ResultWriter:
                 self.fout_score.write((ctypes.c_char * nb).from_address(ptr))
             self._run = None
 
+    def write_top(self, name, rows):
+        """rows: ranked (answer, score, time), best first"""
+        for rank, (ans, sco, tim) in enumerate(rows, 1):
+            self.top.writerow([name, rank, ans, sco, tim])
+
     def write_error(self, name, qi=None):
-        if self.sharded:                            # the block is already zero
+        if self.ftop is not None:
+            self.write_top(name, [("error", -1e999, 0)])
+        if self.sharded or self.no_bin:             # (sharded: the block is already zero)
             if self.text:
                 self.fout.write("%s\t%s\n" % (name, "error"))
                 self.detail.writerow([name, "error", -1e999, 0])
@@ -96,13 +121,19 @@ class ResultWriter:
         if self.text:
             self.fout.flush()
             self.fout2.flush()
+        if self.ftop is not None:
+            self.ftop.flush()
 
     def close(self):
         self._flush_run()
         if self.text:
             self.fout.close()
             self.fout2.close()
-        if self.sharded:
+        if self.ftop is not None:
+            self.ftop.close()
+        if self.no_bin:
+            pass
+        elif self.sharded:
             os.close(self.fd)
         else:
             self.fout_score.close()
@@ -113,6 +144,10 @@ def main(argv=None):
     if len(argv) < 4:
         print("Usage: python %s <query list> <database dir> <result file>" % argv[0])
         return 1
+    top_n, no_bin, err = matcher_flags(argv[4:])
+    if err:
+        print(err, file=sys.stderr)
+        return 2
     rc = self_launch_if_asked(argv)         # PFANN_GPUS=N: N ranks of this command, one per GPU
     if rc is not None:
         return rc
@@ -165,13 +200,17 @@ def main(argv=None):
     db = db_box[0]
     db.attach_engine(engine)
     clock.lap("database (rest of its load after the engine was ready)")
-    db.warmup(rows=warm * (ranks.world if multi else 1))
+    if top_n or no_bin:
+        db.warmup(rows=warm, want_song_scores=not no_bin, topn=top_n)
+    else:
+        db.warmup(rows=warm * (ranks.world if multi else 1))
     clock.lap("database warm-up")
     say("database loaded")
     timer = StageTimer()
     db.timer = timer
     tm_0 = time.time()
-    out = ResultWriter(result_file, len(db.songList), ranks=ranks, n_queries=len(dataset), song_range=db.song_range)
+    out = ResultWriter(result_file, len(db.songList), ranks=ranks, n_queries=len(dataset), song_range=db.song_range,
+                       top=top_n > 0, no_bin=no_bin)
 
     def launch(items):
         """items: one launch group of (index, n_seg, emb) in list order -> search + match in flight."""
@@ -181,7 +220,10 @@ def main(argv=None):
             emb = torch.cat([e for _, _, e in good])
             qlen = [n for _, n, _ in good]
             qstart = np.concatenate([[0], np.cumsum(qlen)[:-1]])
-            ps = db.query_launch_chunks(emb, qstart, qlen, want_song_scores=True)
+            if top_n and no_bin:                 # search + top-N match: no per-song block, so nothing to cut into chunks
+                ps = [(0, len(good), db.query_topn_launch(emb, qstart, qlen, top_n))]
+            else:
+                ps = db.query_launch_chunks(emb, qstart, qlen, want_song_scores=not no_bin)
         return items, good, ps
 
     def finish(launched):
@@ -189,8 +231,17 @@ def main(argv=None):
         it = iter(items)
         for j0, j1, p in ps:
             results = {}
-            for (i, _, _), r in zip(good[j0:j1], db.query_finish(p, reuse_buffers=True)):
-                results[i] = r
+            if top_n and no_bin:
+                for (i, _, _), rows in zip(good[j0:j1], db.query_topn_finish(p)):
+                    results[i] = rows[0] + (None, rows)
+            else:
+                tops = [None] * (j1 - j0)
+                if top_n:                        # the ranked lists of this chunk, from the labels its search left behind
+                    qlen = [n for _, n, _ in good[j0:j1]]
+                    tp = db.query_topn_again(p, np.concatenate([[0], np.cumsum(qlen)[:-1]]), qlen, top_n)
+                    tops = db.query_topn_finish(tp)
+                for (i, _, _), r, rows in zip(good[j0:j1], db.query_finish(p, reuse_buffers=True), tops):
+                    results[i] = r + (rows,)
             last = good[j1 - 1][0]
             with timer.stage("output answer"):
                 for i, n, _ in it:                                        # list order, error rows in their places
@@ -208,8 +259,10 @@ def main(argv=None):
         if n == 0:                                                        # matcher.py:94-107
             out.write_error(name, qi=i)
         else:
-            sco, (sid, tim), song_score = results[i]
+            sco, (sid, tim), song_score, rows = results[i]
             out.write(name, db.songList[sid], sco, tim, song_score, qi=i)   # sid == -1 -> last song (matcher.py:138)
+            if rows is not None:
+                out.write_top(name, [(db.songList[s], sc, t) for sc, (s, t) in rows])
 
     # matcher.py:120-126 asks the model for norm=False and L2-normalises on the CPU; the same formula runs inside the
     # projection kernel here.  One launch group = PFANN_MAX_BATCH windows (512 ten-second queries): enough 128x128
