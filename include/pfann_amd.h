@@ -233,6 +233,28 @@ int pfann_db_set_prefilter(pfann_db *db, int on);
 int pfann_search_topk(pfann_db *db, const float *q_dev, int64_t nq, int k, float *D_dev,
                       int64_t *I_dev, void *stream);
 
+/* pfann_search_topk with one range of rows left out per query row (self-match: a song queried against its own database
+ * leaves its own rows out).  excl_lo_dev / excl_hi_dev: int64 [nq] on the device, in the space of I_dev (row + label_base).
+ *   - Row m gets the exact top-k over the shard's rows whose label is not in [excl_lo[m], excl_hi[m]).
+ *   - Ranges are clipped to the shard; lo >= hi excludes nothing.  They are independent per query row (they may differ
+ *     inside one 128-row query tile), and a row's result does not depend on the other rows' ranges.
+ *   - Everything else is pfann_search_topk's contract: descending output with ties to the lower row; D = -FLT_MAX, I = -1
+ *     padding when fewer than k rows remain (also when the range covers the whole shard); fully asynchronous on `stream`, no
+ *     host synchronisation (one exception, as for the fp16 query buffer of pfann_search_topk: a call with more query
+ *     rows than any before it on this handle frees and regrows the range buffers, and waits for `stream` before it
+ *     does); rows whose survivor lists overflow are recomputed by the device fallback, which leaves the
+ *     same rows out; nq > 16384 is walked in chunks; where pfann_search_topk returns the canonical fp32 scores
+ *     (canonical_scores of the plan) so does this call, bit for bit.
+ *   - With both pointers NULL (the call then IS pfann_search_topk), or every range empty, D and I are bit for bit those of
+ *     pfann_search_topk.  One pointer NULL and the other not: -1.
+ *   - fp32 rows, fp32 rows with their fp16 copy and fp16-only storage are all served, on every path of the plan
+ *     (pfann_search_plan_excl prints it).  The excluded rows never reach a group maximum, a threshold or a survivor list,
+ *     so thresholds come from rows that count: this is NOT a post-filter of pfann_search_topk's answer, which would come
+ *     back with fewer than k rows whenever the range holds some of the k best.
+ *   - The sharded halves (pfann_search_bound / _bounded) have no such form. */
+int pfann_search_topk_excl(pfann_db *db, const float *q_dev, int64_t nq, int k, const int64_t *excl_lo_dev,
+                           const int64_t *excl_hi_dev, float *D_dev, int64_t *I_dev, void *stream);
+
 /* The same search split around ONE collective, for a database sharded over several GPUs (pfann_amd/dist.py; the
  * reference has no counterpart: database.py:101-104 replicates the index).  nq <= 16384 per call.
  *   pfann_search_bound        : query preparation + the sampled pass only; lb_dev[nq][m] = for every query row the m
@@ -261,6 +283,10 @@ int pfann_search_topk_bounded(pfann_db *db, const float *q_dev, int64_t nq, int 
  * len - 1 characters of it), -1 for an unknown storage or phase. */
 int pfann_search_plan(int64_t n, int d, int64_t nq, int k, int storage, int phase, int resume_with_lb, int mtop,
                       char *buf, int len);
+/* ... and what pfann_search_topk_excl (with ranges) launches for it: the same path on the masked kernels.  An export of
+ * its own beside pfann_search_plan, whose signature and text stay as they are: new ABI surface, there so that a test can
+ * assert the path a masked shape takes.  Same text format and return value; phase 0 only. */
+int pfann_search_plan_excl(int64_t n, int d, int64_t nq, int k, int storage, char *buf, int len);
 
 /* Exact top-k of arbitrary (score,label) lists: in[nq][m] -> out[nq][k] (merging per-shard
  * top-k lists after an all-gather).  Entries with label<0 are ignored. */

@@ -678,6 +678,7 @@ void pfann_db_destroy(pfann_db *db) {
     if (db->ws.qh) (void)hipFree(db->ws.qh);
     if (db->ws.row_ovf) (void)hipFree(db->ws.row_ovf);
     if (db->ws.left) (void)hipFree(db->ws.left);
+    if (db->ws.excl) (void)hipFree(db->ws.excl);        // (excl_tile lies in the same allocation)
     if (db->match_scratch) (void)hipFree(db->match_scratch);
     if (db->win_scratch) (void)hipFree(db->win_scratch);
     if (db->seq_scratch) (void)hipFree(db->seq_scratch);
@@ -793,6 +794,22 @@ int pfann_search_topk(pfann_db *db, const float *q, int64_t nq, int k, float *D,
     return 0;
 }
 
+int pfann_search_topk_excl(pfann_db *db, const float *q, int64_t nq, int k, const int64_t *excl_lo, const int64_t *excl_hi, float *D,
+                           int64_t *I, void *stream) {
+    if (excl_lo == nullptr && excl_hi == nullptr) return pfann_search_topk(db, q, nq, k, D, I, stream);
+    if (excl_lo == nullptr || excl_hi == nullptr) { set_error("pfann_search_topk_excl: one of excl_lo / excl_hi is NULL"); return -1; }
+    PF_HIP(hipSetDevice(db->device));
+    const int64_t chunk = 16384;
+    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+        const int64_t n = std::min(chunk, nq - q0);
+        const int rc = search_topk(db->emb, (db->prefilter || db->emb == nullptr) ? db->emb_h : nullptr, db->xnorm_max, db->n, db->d,
+                                   db->label_base, q + q0 * db->d, n, k, D + q0 * k, I + q0 * k, db->ws,
+                                   (hipStream_t)stream, 0, nullptr, 1, excl_lo + q0, excl_hi + q0);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 int pfann_search_bound(pfann_db *db, const float *q, int64_t nq, int k, int m, float *lb, void *stream) {
     PF_HIP(hipSetDevice(db->device));
     if (nq > 16384) { set_error("pfann_search_bound: at most 16384 query rows per call (got %lld)", (long long)nq); return -1; }
@@ -818,6 +835,16 @@ int pfann_search_plan(int64_t n, int d, int64_t nq, int k, int storage, int phas
     sh.n = n; sh.d = d; sh.nq = nq; sh.k = k; sh.storage = storage; sh.phase = phase; sh.mtop = mtop;
     sh.resume = phase == 2 && resume_with_lb != 0;
     sh.has_lb = phase == 2;
+    return print_search_plan(plan_search(sh, search_tuning()), buf, len);
+}
+
+int pfann_search_plan_excl(int64_t n, int d, int64_t nq, int k, int storage, char *buf, int len) {
+    if (storage < STORE_F32 || storage > STORE_F16 || (buf == nullptr && len > 0)) {
+        set_error("pfann_search_plan_excl: storage=%d", storage);
+        return -1;
+    }
+    SearchShape sh;
+    sh.n = n; sh.d = d; sh.nq = nq; sh.k = k; sh.storage = storage; sh.excl = true;
     return print_search_plan(plan_search(sh, search_tuning()), buf, len);
 }
 

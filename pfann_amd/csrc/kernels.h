@@ -73,6 +73,10 @@ struct SearchWorkspace {
     float *eps = nullptr;      // [cap_q] per-row bound of |s16 - s|
     void *qh = nullptr;        // [cap_q][d] fp16 query rows
     int64_t qh_elems = 0;
+    // masked search (pfann_search_topk_excl; written by excl_prep_kernel, allocated on first use)
+    uint2 *excl = nullptr;       // [cap_q] row range every query row leaves out
+    uint2 *excl_tile = nullptr;  // [cap_q / 128 + 1] span of the union of each 128-row query tile's ranges (= excl + cap_q: one allocation)
+    int64_t excl_cap = 0;
     // two-phase search of a song-sharded job (search_topk phase 1 -> all-reduce MAX of the bounds -> phase 2): what
     // phase 1 left behind, valid for exactly this (q, nq, k)
     const float *bound_q = nullptr;
@@ -94,7 +98,8 @@ struct SearchWorkspace {
 //            merge of the shards' lists is still the exact global top-k.
 int search_topk(const float *db, const void *dbh, float xnorm_max, int64_t n, int d, int64_t label_base,
                 const float *q, int64_t nq, int k, float *D, int64_t *I, SearchWorkspace &ws, hipStream_t s,
-                int phase = 0, float *lb = nullptr, int mtop = 1);
+                int phase = 0, float *lb = nullptr, int mtop = 1, const int64_t *excl_lo = nullptr,
+                const int64_t *excl_hi = nullptr);
 int topk_merge(const float *S, const int64_t *L, int64_t nq, int m, int k, float *D, int64_t *I,
                hipStream_t s);
 // one wavefront per query row (search.hip): k-th largest of the gathered bound candidates; merge of G sorted shard lists

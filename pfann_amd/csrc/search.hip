@@ -27,7 +27,10 @@ namespace pfann {
 // single software pipeline: tile (q, kt+1) -- or (q+1, 0) -- is prefetched while (q, kt) is on the
 // matrix cores, so with K = d = 128 (4 K-tiles) the exposed first load and the pipeline drain are
 // paid once per QT*4 K-tiles instead of once per 4.  The db tile is re-read from L1/L2 (64 KB).
-template <int BM, int BN, int WM, int WN, int QT>
+// EXCL (the masked search, DESIGN.md "Self-match"): a score of a row inside its query row's range p.excl[m] becomes -inf
+// before the filter, on the db tiles that meet the span of the query tile's ranges (p.excl_tile) only; the dense level
+// appends like the thresholded ones (its counters start at 0), so an excluded row is absent from the list.
+template <int BM, int BN, int WM, int WN, int QT, bool EXCL = false>
 __global__ __launch_bounds__(256, 2) void scan_emit_kernel(ScanParams p) {
     constexpr int BK = 32, LDK = BK + 4;
     constexpr int WAVES_N = BN / WN;
@@ -52,6 +55,8 @@ __global__ __launch_bounds__(256, 2) void scan_emit_kernel(ScanParams p) {
     for (int i = tid; i < QT * BM; i += 256) {
         const int64_t m = (int64_t)mt0 * BM + i;
         thr_s[i] = (p.thr != nullptr && m < p.nq) ? p.thr[m] : -INFINITY;
+        // masked scores are -inf: never at or above a threshold (fewer than k rows left: the sampled threshold is -inf)
+        if (EXCL) thr_s[i] = fmaxf(thr_s[i], -3.4028234663852886e38f);
     }
 
     // bounds-checked buffer loads (OOB lanes read 0); windows start at this block's first rows
@@ -151,6 +156,21 @@ __global__ __launch_bounds__(256, 2) void scan_emit_kernel(ScanParams p) {
         // are rare (~1.6e-3 per score), so survival is tested per GROUP of 4 slots (one branch),
         // and only groups with a survivor fall into the per-slot append code.
         const float *thr_c = thr_s + q * BM;
+        if constexpr (EXCL) {
+            // block-uniform: this db tile meets the ranges of the query tile (in self-match: the tiles of one to three songs)
+            if (excl_span_hit(p.excl_tile[m0 >> 7], n0 * p.row_stride, (n0 + BN - 1) * p.row_stride)) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int64_t m = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
+                        const uint2 ex = m < p.nq ? p.excl[m] : make_uint2(0u, 0u);
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+                            if (excl_hit(ex, (unsigned)((n0 + wn * WN + j * 32 + l31) * p.row_stride))) acc[i][j][r] = -INFINITY;
+                    }
+            }
+        }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int64_t n = n0 + wn * WN + j * 32 + l31;
@@ -158,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void scan_emit_kernel(ScanParams p) {
             const unsigned row = (unsigned)(n * p.row_stride);
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                if (p.thr == nullptr) {          // top sampling level: nrows <= CAP, no filter, no atomics
+                if (!EXCL && p.thr == nullptr) {          // top sampling level: nrows <= CAP, no filter, no atomics
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int64_t m = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
@@ -225,7 +245,10 @@ __global__ __launch_bounds__(256, 2) void scan_emit_kernel(ScanParams p) {
 //         replace the two sampled scan+sort levels of the generic ladder;
 // MODE 2: dense (nrows <= CAP): every score is written at slot = row.
 // ------------------------------------------------------------------------------------
-template <int D, int ELT, int MODE>
+// EXCL (the masked search, DESIGN.md "Self-match"): on the pieces that meet the span of the ranges (p.excl_tile[0]: one
+// query tile) a score of a row inside its query row's range p.excl[m] becomes -inf before it meets the group maximum
+// (MODE 1) or the threshold (MODE 0); MODE 2 appends the rows that remain (counters start at 0) instead of writing slot = row.
+template <int D, int ELT, int MODE, bool EXCL = false>
 __global__ __launch_bounds__(256, 2) void scan_small_kernel(ScanParams p) {
     constexpr int RB = D * ELT;               // bytes per row
     constexpr int NP = RB / 32;               // 32-byte K pieces per row
@@ -281,10 +304,13 @@ __global__ __launch_bounds__(256, 2) void scan_small_kernel(ScanParams p) {
     }
     load_tile(0);                              // the stream starts before anything else is fetched
     if (MODE == 0) {
-        if (tid < 32) { thr_s[tid] = tid < p.nq ? p.thr[tid] : INFINITY; l_hist[tid] = 0; }
+        // (EXCL: masked scores are -inf and never reach a threshold, also when fewer than k groups were left and it is -inf)
+        if (tid < 32) { thr_s[tid] = tid < p.nq ? (EXCL ? fmaxf(p.thr[tid], -3.4028234663852886e38f) : p.thr[tid]) : INFINITY; l_hist[tid] = 0; }
         if (tid == 0) l_n = 0;
         __syncthreads();
     }
+    uint2 ex_span = make_uint2(0xFFFFFFFFu, 0u);
+    if constexpr (EXCL) ex_span = p.excl_tile[0];
     f32x4 qa[NP];
     if (MODE == 1 && ELT == 2 && p.q32 != nullptr) {
         // query preparation folded in (q_prep_kernel's job, one launch less): fp16 image of the fp32 query rows -- this lane's
@@ -348,11 +374,25 @@ __global__ __launch_bounds__(256, 2) void scan_small_kernel(ScanParams p) {
         const int64_t n = r0 + l31;
         const bool nok = n < r_hi;
         const unsigned row = (unsigned)(n * p.row_stride);
+        unsigned masked = 0u;                  // EXCL: bit r = acc[r] is an excluded row's score
+        if constexpr (EXCL) {
+            if (excl_span_hit(ex_span, r0 * p.row_stride, (r_hi - 1) * p.row_stride)) {        // wave-uniform, rare
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = (r & 3) + 8 * (r >> 2) + 4 * lhalf;
+                    const uint2 ex = m < p.nq ? p.excl[m] : make_uint2(0u, 0u);
+                    if (excl_hit(ex, row)) { acc[r] = -INFINITY; masked |= 1u << r; }
+                    __builtin_amdgcn_sched_barrier(0);     // one range in flight at a time: the branch is rare, registers are not
+                }
+            }
+        }
         if (MODE == 2) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = (r & 3) + 8 * (r >> 2) + 4 * lhalf;
-                if (nok && m < p.nq) p.keys[(int64_t)m * CAP + n] = pack_key(acc[r], row);
+                if (EXCL) {
+                    if (nok && m < p.nq && !((masked >> r) & 1u)) p.keys[(int64_t)m * CAP + atomicAdd(&p.cnt[m], 1)] = pack_key(acc[r], row);
+                } else if (nok && m < p.nq) p.keys[(int64_t)m * CAP + n] = pack_key(acc[r], row);
             }
         } else if (MODE == 1) {
 #pragma unroll
@@ -605,12 +645,39 @@ __global__ __launch_bounds__(256) void group_max_select_wave_kernel(const float 
 // pfann_search_topk never synchronises, never retries and cannot fail with "lists keep overflowing".
 // Unflagged rows cost one 4-byte read.  ELT = 4: fp32 rows; ELT = 2: fp16 rows, query rounded to fp16.
 // ------------------------------------------------------------------------------------
-template <int ELT>
+template <int ELT, bool EXCL = false>
 __global__ __launch_bounds__(256) void topk_fallback_kernel(int *__restrict__ row_ovf, const float *__restrict__ q,
                                                             const void *__restrict__ dbv, int64_t n, int d, int k,
                                                             float *__restrict__ D, int64_t *__restrict__ I,
-                                                            int64_t label_base) {
-    topk_fallback_body<ELT, 256>(blockIdx.x, row_ovf, q, dbv, n, d, k, D, I, label_base);
+                                                            int64_t label_base, const uint2 *__restrict__ excl) {
+    topk_fallback_body<ELT, 256, EXCL>(blockIdx.x, row_ovf, q, dbv, n, d, k, D, I, label_base, excl);
+}
+
+// The masked search's ranges, once per call: label ranges [lo[m], hi[m]) -> rows of this shard (clipped; lo >= hi: nothing;
+// nullptr: nothing), and per 128-row query tile the span of the union of its ranges -- what the masked scans test a db tile
+// against before they look at single rows.  One workgroup of 128 threads per query tile.
+__global__ __launch_bounds__(128) void excl_prep_kernel(const int64_t *__restrict__ lo, const int64_t *__restrict__ hi, int64_t nq,
+                                                        int64_t n, int64_t label_base, uint2 *__restrict__ excl,
+                                                        uint2 *__restrict__ excl_tile) {
+    __shared__ unsigned s_lo[2], s_hi[2];
+    const int tid = threadIdx.x;
+    const int64_t m = (int64_t)blockIdx.x * 128 + tid;
+    unsigned a = 0u, b = 0u;
+    if (m < nq && lo != nullptr && hi != nullptr) {
+        const int64_t l = lo[m] <= label_base ? 0 : (lo[m] - label_base < n ? lo[m] - label_base : n);
+        const int64_t h = hi[m] <= label_base ? 0 : (hi[m] - label_base < n ? hi[m] - label_base : n);
+        if (l < h) { a = (unsigned)l; b = (unsigned)h; }             // (n < 2^32: search_plan.h)
+    }
+    if (m < nq) excl[m] = make_uint2(a, b);
+    unsigned ulo = a < b ? a : 0xFFFFFFFFu, uhi = b;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ulo = min(ulo, (unsigned)__shfl_xor((int)ulo, o, 64));
+        uhi = max(uhi, (unsigned)__shfl_xor((int)uhi, o, 64));
+    }
+    if ((tid & 63) == 0) { s_lo[tid >> 6] = ulo; s_hi[tid >> 6] = uhi; }
+    __syncthreads();
+    if (tid == 0) excl_tile[blockIdx.x] = make_uint2(min(s_lo[0], s_lo[1]), max(s_hi[0], s_hi[1]));
 }
 
 // ------------------------------------------------------------------------------------
@@ -733,8 +800,11 @@ static int launch_stage(const SearchStage &st, const StageArgs &a) {
     int *zero_me = st.zero_me ? ws.overflow + 1 : nullptr;       // the select's overflow counter (one memset less)
     switch (st.kernel) {
 #define X(id, ...) case K_##id: PF_LAUNCH((__VA_ARGS__), grid, block, st.lds, s, scan_params(st, a)); break;
-    PF_SCAN_KERNELS(X)
+    PF_SCAN_KERNELS(X) PF_SCAN_EXCL_KERNELS(X)
 #undef X
+    case K_EXCL_PREP:
+        PF_LAUNCH(excl_prep_kernel, grid, block, 0, s, a.excl_lo, a.excl_hi, a.nq, a.n, a.label_base, ws.excl, ws.excl_tile);
+        break;
     case K_FILL_EMPTY: PF_LAUNCH(fill_empty_kernel, grid, block, 0, s, a.D, a.I, a.nq * a.k); break;
     case K_BOUND_NONE: PF_LAUNCH(bound_none_kernel, grid, block, 0, s, a.lb, a.nq * a.mtop); break;
     case K_BOUND_IN: PF_LAUNCH(bound_in_kernel, grid, block, 0, s, ws.thr_adj, ws.eps, st.margin, a.lb, a.nq); break;
@@ -757,10 +827,20 @@ static int launch_stage(const SearchStage &st, const StageArgs &a) {
                   a.D, a.I, a.label_base, ws.row_ovf, st.nsub);
         break;
     case K_FALLBACK_4:
-        PF_LAUNCH(topk_fallback_kernel<4>, grid, block, 0, s, ws.row_ovf, a.q, (const void *)a.db, a.n, a.d, a.k, a.D, a.I, a.label_base);
+        PF_LAUNCH(topk_fallback_kernel<4>, grid, block, 0, s, ws.row_ovf, a.q, (const void *)a.db, a.n, a.d, a.k, a.D, a.I, a.label_base,
+                  (const uint2 *)nullptr);
+        break;
+    case K_FALLBACK_4_EXCL:
+        PF_LAUNCH((topk_fallback_kernel<4, true>), grid, block, 0, s, ws.row_ovf, a.q, (const void *)a.db, a.n, a.d, a.k, a.D, a.I,
+                  a.label_base, (const uint2 *)ws.excl);
+        break;
+    case K_FALLBACK_2_EXCL:
+        PF_LAUNCH((topk_fallback_kernel<2, true>), grid, block, 0, s, ws.row_ovf, a.q, a.dbh, a.n, a.d, a.k, a.D, a.I, a.label_base,
+                  (const uint2 *)ws.excl);
         break;
     case K_FALLBACK_2:
-        PF_LAUNCH(topk_fallback_kernel<2>, grid, block, 0, s, ws.row_ovf, a.q, a.dbh, a.n, a.d, a.k, a.D, a.I, a.label_base);
+        PF_LAUNCH(topk_fallback_kernel<2>, grid, block, 0, s, ws.row_ovf, a.q, a.dbh, a.n, a.d, a.k, a.D, a.I, a.label_base,
+                  (const uint2 *)nullptr);
         break;
     default: return launch_stage_f16(st, a);
     }
@@ -771,13 +851,14 @@ static int launch_stage(const SearchStage &st, const StageArgs &a) {
 // Validate, size the workspace, plan (search_plan.h: every choice of kernel, grid and threshold is made there), run the stages.
 int search_topk(const float *db, const void *dbh, float xnorm_max, int64_t n, int d, int64_t label_base,
                 const float *q, int64_t nq, int k, float *D, int64_t *I, SearchWorkspace &ws, hipStream_t s,
-                int phase, float *lb, int mtop) {
+                int phase, float *lb, int mtop, const int64_t *excl_lo, const int64_t *excl_hi) {
     if (nq <= 0) return 0;
     SearchShape sh;
     sh.n = n; sh.d = d; sh.nq = nq; sh.k = k; sh.phase = phase; sh.mtop = mtop;
     sh.storage = db == nullptr ? STORE_F16 : (dbh != nullptr ? STORE_F32_COPY : STORE_F32);
     sh.resume = phase == 2 && ws.bound_valid && ws.bound_q == q && ws.bound_nq == nq && ws.bound_k == k;
     sh.has_lb = lb != nullptr;
+    sh.excl = excl_lo != nullptr && excl_hi != nullptr;
     if (!sh.resume) ws.bound_valid = false;
     const SearchPlan plan = plan_search(sh, search_tuning());
     if (plan.error != PLAN_OK) { set_error("%s", plan.error_msg); return -1; }
@@ -790,8 +871,18 @@ int search_topk(const float *db, const void *dbh, float xnorm_max, int64_t n, in
             PF_HIP(hipMalloc(&ws.qh, (size_t)nq * d * 2));
             ws.qh_elems = nq * d;
         }
+        if (sh.excl && ws.excl_cap < nq) {
+            // (grows like ws.qh above: the one place this call waits for the stream, and only when the batch got larger)
+            if (ws.excl) { PF_HIP(hipStreamSynchronize(s)); (void)hipFree(ws.excl); }
+            ws.excl = ws.excl_tile = nullptr; ws.excl_cap = 0;
+            const int64_t cap = nq < 64 ? 64 : nq;
+            // one allocation for both: the ranges, and behind them the spans of the query tiles
+            PF_HIP(hipMalloc(&ws.excl, sizeof(uint2) * (cap + cap / 128 + 1)));
+            ws.excl_tile = ws.excl + cap;
+            ws.excl_cap = cap;
+        }
     }
-    const StageArgs a{db, dbh, xnorm_max, n, d, label_base, q, nq, k, D, I, lb, mtop, ws, s};
+    const StageArgs a{db, dbh, xnorm_max, n, d, label_base, q, nq, k, D, I, lb, mtop, excl_lo, excl_hi, ws, s};
     for (int i = 0; i < plan.n_stages;) {
         const SearchStage &st = plan.stages[i];
         if (st.zero_cnt) PF_HIP(hipMemsetAsync(ws.cnt, 0, sizeof(int) * nq, s));

@@ -40,7 +40,18 @@ struct ScanParams {
     void *qh_out = nullptr;  // [nq][d] fp16 query rows
     float *eps = nullptr;    // [nq]
     int *row_ovf = nullptr;
+    // the masked twins (EXCL = true; excl_prep_kernel writes both): query row m leaves rows [excl[m].x, excl[m].y) of the
+    // shard out (row space, clipped; empty = (0, 0)); excl_tile[m / 128] = the span of the union of a 128-row query tile's
+    // ranges ((0xFFFFFFFF, 0) when all are empty): a db tile outside it runs the unmasked epilogue
+    const uint2 *excl = nullptr, *excl_tile = nullptr;
 };
+// row in [lo, hi) of an exclusion range
+// (one unsigned compare: row - lo wraps above every length when row < lo; an empty range has length 0)
+__device__ __forceinline__ bool excl_hit(uint2 r, unsigned row) { return row - r.x < r.y - r.x; }
+// rows [first, last] meet the span of a query tile's ranges
+__device__ __forceinline__ bool excl_span_hit(uint2 span, int64_t first, int64_t last) {
+    return first < (int64_t)span.y && last >= (int64_t)span.x;
+}
 
 
 // The canonical fp32 score of a row, computed by the four adjacent lanes 4 c .. 4 c + 3 of a candidate:
@@ -92,9 +103,11 @@ __device__ inline void bitonic_sort_u64(unsigned long long *s, int P, int tid, i
 }
 
 // Exact fallback for a flagged row (body of topk_fallback_kernel; NT threads).  Returns at once when row_ovf[m] == 0.
-template <int ELT, int NT>
+// EXCL: rows of excl[m] are left out (the masked search: search_plan.h, SearchShape.excl).
+template <int ELT, int NT, bool EXCL = false>
 __device__ inline void topk_fallback_body(int64_t m, int *row_ovf, const float *__restrict__ q, const void *__restrict__ dbv,
-                                          int64_t n, int d, int k, float *D, int64_t *I, int64_t label_base) {
+                                          int64_t n, int d, int k, float *D, int64_t *I, int64_t label_base,
+                                          const uint2 *__restrict__ excl = nullptr) {
     constexpr int FB = 2048, RPP = NT / 2;        // buffer slots; rows per pass (NT / 4 row groups x 2)
     __shared__ unsigned long long buf[FB];
     __shared__ __attribute__((aligned(16))) float qs[1024];
@@ -107,6 +120,8 @@ __device__ inline void topk_fallback_body(int64_t m, int *row_ovf, const float *
     const int tid = threadIdx.x, sub = tid & 3, grp = tid >> 2;
     for (int e = tid; e < d; e += NT) qs[e] = ELT == 4 ? q[m * d + e] : (float)(_Float16)q[m * d + e];
     if (tid == 0) { s_cnt = 0; s_T = ~0ull; }
+    uint2 ex = make_uint2(0u, 0u);
+    if constexpr (EXCL) ex = excl[m];
     __syncthreads();
     for (int64_t base = 0; base < n; base += RPP) {
         const unsigned long long T = s_T;
@@ -119,7 +134,7 @@ __device__ inline void topk_fallback_body(int64_t m, int *row_ovf, const float *
                 else part = canon_part(reinterpret_cast<const _Float16 *>(dbv) + row * d, qs, d, sub);
             }
             part = canon_sum(part);
-            if (sub == 0 && row < n) {
+            if (sub == 0 && row < n && !(EXCL && excl_hit(ex, (unsigned)row))) {
                 const unsigned long long key = pack_key(part, (unsigned)row);
                 if (key < T) buf[atomicAdd(&s_cnt, 1)] = key;       // s_cnt <= FB - RPP before the pass
             }
@@ -158,6 +173,7 @@ struct StageArgs {
     const float *q; int64_t nq; int k;
     float *D; int64_t *I;
     float *lb; int mtop;
+    const int64_t *excl_lo, *excl_hi;    // [nq] label ranges of the masked search (nullptr: none)
     SearchWorkspace &ws;
     hipStream_t s;
     // the rows a re-scoring select reads: the fp32 rows where the fp16 ones were only a pre-filter
@@ -173,6 +189,7 @@ inline ScanParams scan_params(const SearchStage &st, const StageArgs &a) {
     p.cnt = a.ws.cnt; p.keys = reinterpret_cast<unsigned long long *>(a.ws.cl);
     p.n_tiles_m = st.n_tiles_m; p.nsub = st.nsub;
     p.gmax = st.gmax ? reinterpret_cast<float *>(a.ws.cl) : nullptr;       // [nq][groups] floats; the keys come after tau is known
+    if (st.excl) { p.excl = a.ws.excl; p.excl_tile = a.ws.excl_tile; }
     if (st.fold_prep) { p.q32 = a.q; p.xnorm_max = a.xnorm_max; p.qh_out = a.ws.qh; p.eps = a.ws.eps; p.row_ovf = a.ws.row_ovf; }
     return p;
 }

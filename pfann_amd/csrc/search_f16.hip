@@ -83,7 +83,9 @@ __global__ void q_prep_kernel(const float *__restrict__ q, int64_t nq, int d, fl
 // lane reads feeds ONE v_mfma_f32_32x32x16_f16 (lane half h holds k = 8h..8h+7 of the 16-step).
 // p.q / p.db point to fp16 rows, p.thr holds tau - eps (or nullptr on the dense top level).
 // ------------------------------------------------------------------------------------
-template <int QT>
+// EXCL (the masked search, DESIGN.md "Self-match"): as in scan_emit_kernel -- on the db tiles that meet the span of the query
+// tile's ranges a masked accumulator becomes -inf (never >= 0), and the dense level appends the rows that remain.
+template <int QT, bool EXCL = false>
 __global__ __launch_bounds__(256, 2) void scan_f16_kernel(ScanParams p) {
     constexpr int BM = 128, BN = 128, WM = 64, WN = 64;
     constexpr int LDK = 36;                   // LDS row pitch in dwords (128 B of k + 16 B pad)
@@ -105,6 +107,7 @@ __global__ __launch_bounds__(256, 2) void scan_f16_kernel(ScanParams p) {
 
     // thr_s = -(tau - eps): the accumulators START there, so the MFMA chain yields s16 - (tau - eps) and
     // "survivor" is a sign test; query rows past nq start at -inf and never qualify
+    // (EXCL: a masked accumulator is SET to -inf after the chain, so it fails the sign test whatever the threshold was)
     const bool dense = p.thr == nullptr;
     for (int i = tid; i < QT * BM; i += 256) {
         const int64_t m = (int64_t)mt0 * BM + i;
@@ -205,6 +208,21 @@ __global__ __launch_bounds__(256, 2) void scan_f16_kernel(ScanParams p) {
             }
             __syncthreads();
         }
+        if constexpr (EXCL) {
+            // block-uniform: this db tile meets the ranges of the query tile (in self-match: the tiles of one to three songs)
+            if (excl_span_hit(p.excl_tile[m0 >> 7], n0 * p.row_stride, (n0 + BN - 1) * p.row_stride)) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int64_t m = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
+                        const uint2 ex = m < p.nq ? p.excl[m] : make_uint2(0u, 0u);
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+                            if (excl_hit(ex, (unsigned)((n0 + wn * WN + j * 32 + l31) * p.row_stride))) acc[i][j][r] = -INFINITY;
+                    }
+            }
+        }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int64_t n = n0 + wn * WN + j * 32 + l31;
@@ -212,7 +230,15 @@ __global__ __launch_bounds__(256, 2) void scan_f16_kernel(ScanParams p) {
             const unsigned row = (unsigned)(n * p.row_stride);
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                if (dense) {
+                if (EXCL && dense) {
+                    // the rows that remain, appended (the counters start at 0): an excluded row is absent, not last
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int64_t m = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
+                        if (nok && m < p.nq && acc[i][j][r] != -INFINITY)
+                            p.keys[m * CAP + atomicAdd(&p.cnt[m], 1)] = pack_key(acc[i][j][r], row);
+                    }
+                } else if (dense) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int64_t m = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
@@ -284,7 +310,12 @@ __device__ unsigned g_scan_trace_cap = 0;
 // (256 query rows per workgroup -- 128 per wave, two waves per SIMD, every 16 KB db tile feeding twice the MFMAs -- measured
 // the same 2.56 ms as this 128-row form in round 6, profiles/r6/scan_bm256_ab.txt: the step is not bound by its per-tile
 // costs but by what it pays per MFMA: the LDS-latency-bound fragment loop and the survivor epilogue.)
-template <int KS, bool GMAX = false, int DBR = 128, int NBUF = 2>
+// EXCL (the masked search, DESIGN.md "Self-match"): a lane owns one query row per accumulator block, so the row's range
+// p.excl[m] is lane-local too.  A db tile that meets the span of the query tile's ranges (p.excl_tile: workgroup-uniform, in
+// self-match the tiles of one to three songs) loads the ranges and turns the masked accumulators into -inf before the
+// group maxima / the survivor test; every other tile runs the step as it is.  The ranges are read inside that branch, not
+// kept in registers: the full pass has none to spare.
+template <int KS, bool GMAX = false, int DBR = 128, int NBUF = 2, bool EXCL = false>
 __global__ __launch_bounds__(256, DBR == 64 ? 3 : (NBUF == 3 ? 1 : 2)) void scan_f16_qres_kernel(ScanParams p) {
     constexpr int BM = 128, WM = 64, WN = DBR / 2, TM = 2, TN = WN / 32;
     constexpr bool BAL = !GMAX;                   // balanced row -> owner mapping of the survivor-emitting passes (see `frag`)
@@ -321,6 +352,8 @@ __global__ __launch_bounds__(256, DBR == 64 ? 3 : (NBUF == 3 ? 1 : 2)) void scan
 #pragma unroll
     for (int i = 0; i < TM; ++i) posr[i] = 0;
     const char *qb = reinterpret_cast<const char *>(p.q), *dbb = reinterpret_cast<const char *>(p.db);
+    uint2 ex_span = make_uint2(0xFFFFFFFFu, 0u);
+    if constexpr (EXCL) ex_span = p.excl_tile[mt];
 
     // ---- query fragments: lane (l31, lhalf) holds k = 16*kk + 8*lhalf .. +7 of query row m0 + wm*64 + i*32 + l31.
     // They are the MFMA's SECOND operand (the db rows the first), so the result tile comes out transposed: a lane owns
@@ -340,6 +373,10 @@ __global__ __launch_bounds__(256, DBR == 64 ? 3 : (NBUF == 3 ? 1 : 2)) void scan
     for (int i = 0; i < TM; ++i) {
         const int64_t m = m0 + wm * WM + i * 32 + l31;
         th[i] = GMAX ? 0.f : (m < p.nq ? p.thr[m] : INFINITY);
+        // EXCL: the survivor test is `v >= th`, so a threshold of -inf would emit the masked (-inf) rows.  The selects that
+        // write thr_adj floor it at -1000 eps (finite), so this never happens today; the clamp keeps the masked pass
+        // right on its own should that floor ever change (scan_emit_kernel and scan_small_kernel clamp the same way).
+        if (EXCL && !GMAX) th[i] = fmaxf(th[i], -3.4028234663852886e38f);
     }
     // GMAX: one running maximum per (query row, tile-row position): register r of sub-tile (wn, j) is its own group, fed
     // by that row position of every tile of the slice (rows 128*S*stride apart; the two lane halves are merged at the
@@ -466,6 +503,34 @@ __global__ __launch_bounds__(256, DBR == 64 ? 3 : (NBUF == 3 ? 1 : 2)) void scan
 #pragma unroll
                         for (int i = 0; i < TM; ++i) acc[i][j][r] = -INFINITY;
                     }
+        }
+        if constexpr (EXCL) {
+            if (excl_span_hit(ex_span, t * DBR * rstride, ((t + 1) * DBR - 1) * rstride)) {      // (uniform, rare)
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    const int64_t m = m0 + wm * WM + i * 32 + l31;
+                    const uint2 ex = m < p.nq ? p.excl[m] : make_uint2(0u, 0u);
+                    // 32-bit row arithmetic (n < 2^32; a row past the end may wrap: it is -inf already): this lane's first
+                    // tile row relative to the range, then one add and one unsigned compare per accumulator
+                    unsigned rs = (unsigned)rstride;
+                    const unsigned len = ex.y - ex.x;
+                    unsigned b0 = (unsigned)(t * DBR) * rs + (unsigned)(BAL ? 8 * lhalf + 4 * wn : wn * WN + 4 * lhalf) * rs - ex.x;
+                    if constexpr (GMAX) {
+                        // the sampled pass has no register to spare (64 accumulators, 64 running maxima, the query fragments):
+                        // opaque to the optimiser, the step and the base stay INSIDE this rare branch -- left visible, the 32
+                        // loop-invariant products tr * rs were hoisted out of the tile loop and spilled on every tile
+                        asm volatile("" : "+s"(rs));
+                        asm volatile("" : "+v"(b0));
+                    }
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int tr = BAL ? j * 64 + 16 * (r >> 2) + (r & 3) : j * 32 + 8 * (r >> 2) + (r & 3);
+                            if (b0 + (unsigned)tr * rs < len) acc[i][j][r] = -INFINITY;
+                        }
+                }
+            }
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j)
@@ -1198,16 +1263,17 @@ __global__ __launch_bounds__(1024) void select_dense_kernel(const unsigned long 
 // Last launch of the folded small-batch search (search_plan.h, small_sampled_folded): the rows select_rescore_small_kernel left (more than
 // SMALL_N survivors; normally none: returns after one 4-byte read) and, behind it, the exact fallback for flagged rows
 // (normally none either) -- two launches' worth of "nothing to do" in one.  FB_ELT: element size of the fallback's rows.
-template <int FB_ELT>
+template <int FB_ELT, bool EXCL = false>
 __global__ __launch_bounds__(1024) void select_tail_kernel(const unsigned long long *__restrict__ keys, const int *__restrict__ cnt, int k,
                                                            float *__restrict__ thr, float *__restrict__ thr_adj,
                                                            const float *__restrict__ eps, float *D, int64_t *I, int64_t label_base,
                                                            int *overflow, int *row_ovf, const float *__restrict__ q32,
                                                            const float *__restrict__ db32, int d, int nsub, int rescore,
-                                                           const void *__restrict__ fb_rows, int64_t n) {
+                                                           const void *__restrict__ fb_rows, int64_t n,
+                                                           const uint2 *__restrict__ excl) {
     select_rescore_body(keys, cnt, k, 1, thr, thr_adj, eps, D, I, label_base, overflow, row_ovf, q32, db32, d, nsub, rescore);
     __syncthreads();
-    topk_fallback_body<FB_ELT, 1024>(blockIdx.x, row_ovf, q32, fb_rows, n, d, k, D, I, label_base);
+    topk_fallback_body<FB_ELT, 1024, EXCL>(blockIdx.x, row_ovf, q32, fb_rows, n, d, k, D, I, label_base, excl);
 }
 
 // The stages of the plan (search_plan.h) whose kernels live in this file.
@@ -1219,7 +1285,7 @@ int launch_stage_f16(const SearchStage &st, const StageArgs &a) {
     const float *db32 = a.db32(st);
     switch (st.kernel) {
 #define X(id, ...) case K_##id: PF_LAUNCH((__VA_ARGS__), grid, block, st.lds, s, scan_params(st, a)); break;
-    PF_SCAN_F16_KERNELS(X)
+    PF_SCAN_F16_KERNELS(X) PF_SCAN_F16_EXCL_KERNELS(X)
 #undef X
     case K_Q_PREP:
         PF_LAUNCH(q_prep_kernel, grid, block, 0, s, a.q, a.nq, a.d, a.xnorm_max, reinterpret_cast<_Float16 *>(ws.qh), ws.eps, ws.row_ovf);
@@ -1260,12 +1326,22 @@ int launch_stage_f16(const SearchStage &st, const StageArgs &a) {
     case K_SELECT_TAIL_4:
         if (ensure_dyn_lds((const void *)select_tail_kernel<4>, CAP * 8)) return -1;
         PF_LAUNCH(select_tail_kernel<4>, grid, block, st.lds, s, keys, ws.cnt, a.k, ws.thr, ws.thr_adj, ws.eps, a.D, a.I, a.label_base,
-                  ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, (const void *)a.db, a.n);
+                  ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, (const void *)a.db, a.n, (const uint2 *)nullptr);
+        break;
+    case K_SELECT_TAIL_4_EXCL:
+        if (ensure_dyn_lds((const void *)select_tail_kernel<4, true>, CAP * 8)) return -1;
+        PF_LAUNCH((select_tail_kernel<4, true>), grid, block, st.lds, s, keys, ws.cnt, a.k, ws.thr, ws.thr_adj, ws.eps, a.D, a.I, a.label_base,
+                  ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, (const void *)a.db, a.n, (const uint2 *)ws.excl);
+        break;
+    case K_SELECT_TAIL_2_EXCL:
+        if (ensure_dyn_lds((const void *)select_tail_kernel<2, true>, CAP * 8)) return -1;
+        PF_LAUNCH((select_tail_kernel<2, true>), grid, block, st.lds, s, keys, ws.cnt, a.k, ws.thr, ws.thr_adj, ws.eps, a.D, a.I, a.label_base,
+                  ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, a.dbh, a.n, (const uint2 *)ws.excl);
         break;
     case K_SELECT_TAIL_2:
         if (ensure_dyn_lds((const void *)select_tail_kernel<2>, CAP * 8)) return -1;
         PF_LAUNCH(select_tail_kernel<2>, grid, block, st.lds, s, keys, ws.cnt, a.k, ws.thr, ws.thr_adj, ws.eps, a.D, a.I, a.label_base,
-                  ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, a.dbh, a.n);
+                  ws.overflow, ws.row_ovf, a.q, db32, a.d, st.nsub, st.rescore, a.dbh, a.n, (const uint2 *)nullptr);
         break;
     default: set_error("search: stage with unknown kernel %d", st.kernel); return -1;
     }

@@ -20,6 +20,11 @@
 //                followed by a select with re-scoring (mode 0 = threshold only); scan_f16_qres_kernel where the
 //                query-stationary kernel applies, scan_f16_kernel<QT> otherwise.
 //   ladder_f32   fp32 rows only: the same ladder on scan_emit_kernel + select_kernel.
+// SearchShape.excl (pfann_search_topk_excl: every query row leaves one row range out): the same paths on the masked twins of
+// the scans and of the fallback (the last template argument; DESIGN.md, "Self-match"), behind one excl_prep_kernel.  A masked
+// row never reaches a group maximum, a threshold or a survivor list, so the selects run as they are; the dense levels
+// append with a counter that starts at 0 instead of writing slot = row under a counter preset to n, because an excluded
+// row must be absent, not last.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -88,16 +93,58 @@ static_assert(64 * QRES_S_MAX <= GROUPS_MAX, "the sampled pass gives 64 groups p
     X(FALLBACK_4, topk_fallback_kernel<4>)                      \
     X(FALLBACK_2, topk_fallback_kernel<2>)
 
+// The masked twins (SearchShape.excl), in lists of their own and in the order of their unmasked kernels: the three lists
+// above are, name for name, the kernels of the recorded trace of the unmasked search (tests/test_search_plan.py).  The twin
+// of scan kernel K_x is K_x_EXCL = K_x + (K_SCAN_SMALL_128_4_0_EXCL - K_SCAN_SMALL_128_4_0): excl_twin().
+#define PF_SCAN_EXCL_KERNELS(Y)                                     \
+    Y(SCAN_SMALL_128_4_0_EXCL, scan_small_kernel<128, 4, 0, true>)  \
+    Y(SCAN_SMALL_128_4_1_EXCL, scan_small_kernel<128, 4, 1, true>)  \
+    Y(SCAN_SMALL_128_4_2_EXCL, scan_small_kernel<128, 4, 2, true>)  \
+    Y(SCAN_SMALL_128_2_0_EXCL, scan_small_kernel<128, 2, 0, true>)  \
+    Y(SCAN_SMALL_128_2_1_EXCL, scan_small_kernel<128, 2, 1, true>)  \
+    Y(SCAN_SMALL_128_2_2_EXCL, scan_small_kernel<128, 2, 2, true>)  \
+    Y(SCAN_SMALL_64_4_0_EXCL, scan_small_kernel<64, 4, 0, true>)    \
+    Y(SCAN_SMALL_64_4_1_EXCL, scan_small_kernel<64, 4, 1, true>)    \
+    Y(SCAN_SMALL_64_4_2_EXCL, scan_small_kernel<64, 4, 2, true>)    \
+    Y(SCAN_SMALL_64_2_0_EXCL, scan_small_kernel<64, 2, 0, true>)    \
+    Y(SCAN_SMALL_64_2_1_EXCL, scan_small_kernel<64, 2, 1, true>)    \
+    Y(SCAN_SMALL_64_2_2_EXCL, scan_small_kernel<64, 2, 2, true>)    \
+    Y(SCAN_EMIT_32_EXCL, scan_emit_kernel<32, 128, 32, 32, 1, true>)       \
+    Y(SCAN_EMIT_64_EXCL, scan_emit_kernel<64, 64, 32, 32, 1, true>)        \
+    Y(SCAN_EMIT_128_QT4_EXCL, scan_emit_kernel<128, 128, 64, 64, 4, true>) \
+    Y(SCAN_EMIT_128_QT1_EXCL, scan_emit_kernel<128, 128, 64, 64, 1, true>)
+#define PF_SCAN_F16_EXCL_KERNELS(Y)                                            \
+    Y(SCAN_F16_QT4_EXCL, scan_f16_kernel<4, true>)                             \
+    Y(SCAN_F16_QT1_EXCL, scan_f16_kernel<1, true>)                             \
+    Y(QRES_GMAX_8_NBUF3_EXCL, scan_f16_qres_kernel<8, true, 128, 3, true>)     \
+    Y(QRES_GMAX_8_EXCL, scan_f16_qres_kernel<8, true, 128, 2, true>)           \
+    Y(QRES_GMAX_4_EXCL, scan_f16_qres_kernel<4, true, 128, 2, true>)           \
+    Y(QRES_8_DBR64_NBUF3_EXCL, scan_f16_qres_kernel<8, false, 64, 3, true>)    \
+    Y(QRES_8_DBR64_EXCL, scan_f16_qres_kernel<8, false, 64, 2, true>)          \
+    Y(QRES_8_EXCL, scan_f16_qres_kernel<8, false, 128, 2, true>)               \
+    Y(QRES_4_EXCL, scan_f16_qres_kernel<4, false, 128, 2, true>)
+#define PF_AUX_EXCL_KERNELS(Y)                                  \
+    Y(EXCL_PREP, excl_prep_kernel)                              \
+    Y(SELECT_TAIL_4_EXCL, select_tail_kernel<4, true>)          \
+    Y(SELECT_TAIL_2_EXCL, select_tail_kernel<2, true>)          \
+    Y(FALLBACK_4_EXCL, topk_fallback_kernel<4, true>)           \
+    Y(FALLBACK_2_EXCL, topk_fallback_kernel<2, true>)
+
+#define PF_ALL_SEARCH_KERNELS(X) \
+    PF_SCAN_KERNELS(X) PF_SCAN_F16_KERNELS(X) PF_AUX_KERNELS(X) PF_SCAN_EXCL_KERNELS(X) PF_SCAN_F16_EXCL_KERNELS(X) PF_AUX_EXCL_KERNELS(X)
 enum SearchKernel {
 #define X(id, ...) K_##id,
-    PF_SCAN_KERNELS(X) PF_SCAN_F16_KERNELS(X) PF_AUX_KERNELS(X)
+    PF_ALL_SEARCH_KERNELS(X)
 #undef X
     K_COUNT
 };
+static_assert(K_QRES_4_EXCL - K_QRES_4 == K_SCAN_SMALL_128_4_0_EXCL - K_SCAN_SMALL_128_4_0, "the masked scans mirror the scan lists");
+// the masked twin of a scan kernel of the first two lists
+inline int excl_twin(int scan_kernel) { return scan_kernel + (K_SCAN_SMALL_128_4_0_EXCL - K_SCAN_SMALL_128_4_0); }
 inline const char *search_kernel_name(int kernel) {
     static const char *const names[K_COUNT] = {
 #define X(id, ...) #__VA_ARGS__,
-        PF_SCAN_KERNELS(X) PF_SCAN_F16_KERNELS(X) PF_AUX_KERNELS(X)
+        PF_ALL_SEARCH_KERNELS(X)
 #undef X
     };
     return kernel >= 0 && kernel < K_COUNT ? names[kernel] : "?";
@@ -114,6 +161,7 @@ struct SearchShape {
     bool resume = false;     // phase 2 behind a phase 1 of the same (q, nq, k): thresholds and fp16 query rows are in place
     bool has_lb = false;     // phase 2 was given the global bound
     int mtop = 1;            // phase 1: bounds per query row
+    bool excl = false;       // phase 0 only: every query row leaves one row range out (pfann_search_topk_excl)
 };
 
 // Every A/B switch of the search.  Set (to anything) = on; read once per process (search_tuning()).
@@ -180,17 +228,18 @@ struct SearchStage {
     bool few_survivors = false;
     int fb_elt = 4;                      // fallback / tail: element size of the rows it streams
     int fill = 0;                        // FILL_INT*: dense counter initialisation, cnt[0 .. nq) = fill
+    bool excl = false;                   // a masked scan / fallback / tail: reads the row ranges excl_prep_kernel left
 };
 
 enum { QPREP_NONE = 0, QPREP_LAUNCH = 1, QPREP_FOLDED = 2 };
 enum { FB_NONE = 0, FB_LAUNCH = 1, FB_TAIL = 2 };
 enum {
     PLAN_OK = 0, PLAN_ERR_K, PLAN_ERR_D4, PLAN_ERR_ROWS, PLAN_ERR_D1024, PLAN_ERR_DENSE_CAP, PLAN_ERR_STRIDE_WINDOW, PLAN_ERR_GROUPS,
-    PLAN_ERR_STAGES
+    PLAN_ERR_STAGES, PLAN_ERR_EXCL_PHASE
 };
 inline const char *plan_error_name(int e) {
-    static const char *const names[] = {"none", "k", "d%4", "n>=2^32", "d>1024", "dense>CAP", "stride_window", "groups", "stages"};
-    return e >= 0 && e <= PLAN_ERR_STAGES ? names[e] : "?";
+    static const char *const names[] = {"none", "k", "d%4", "n>=2^32", "d>1024", "dense>CAP", "stride_window", "groups", "stages", "excl_phase"};
+    return e >= 0 && e <= PLAN_ERR_EXCL_PHASE ? names[e] : "?";
 }
 
 struct SearchPlan {
@@ -225,6 +274,13 @@ inline bool qres_ok(const SearchShape &sh, const SearchTuning &t, int64_t db_til
 
 struct Builder {
     SearchPlan &p;
+    bool excl = false;
+    // a scan of the first two lists: its masked twin when the shape excludes rows
+    SearchStage &add_scan(int kernel, int64_t grid, const char *tag, double work) {
+        SearchStage &st = add(excl ? excl_twin(kernel) : kernel, grid, 256, 0, tag, work);
+        st.excl = excl;
+        return st;
+    }
     SearchStage &add(int kernel, int64_t grid, unsigned block = 256, unsigned lds = 0, const char *tag = nullptr, double work = 0.0) {
         if (p.n_stages == SearchPlan::MAX_STAGES) { fail(PLAN_ERR_STAGES, "search plan: more than %lld stages", SearchPlan::MAX_STAGES, 0); --p.n_stages; }
         SearchStage &st = p.stages[p.n_stages++];
@@ -250,6 +306,8 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
     if (k < 1 || k > 1024) { b.fail(PLAN_ERR_K, "search_topk: k=%lld outside 1..1024", k, 0); return plan; }
     if (d % 4 != 0) { b.fail(PLAN_ERR_D4, "search_topk: d=%lld must be a multiple of 4", d, 0); return plan; }
     if (n >= (1ll << 32)) { b.fail(PLAN_ERR_ROWS, "search_topk: shard rows %lld >= 2^32", n, 0); return plan; }
+    if (sh.excl && sh.phase != 0) { b.fail(PLAN_ERR_EXCL_PHASE, "search_topk: row exclusion with phase %lld (the sharded halves have none)", sh.phase, 0); return plan; }
+    b.excl = sh.excl && n > 0;
     auto no_bound = [&]() { b.add(K_BOUND_NONE, cdiv64(nq * sh.mtop, 256)); };     // phase 1 without a sampled threshold
     if (n == 0) {
         plan.path = "empty";
@@ -260,6 +318,8 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
     // the fallback keeps a query row in LDS (standalone launch or inside the tail launch)
     if (d > 1024) { b.fail(PLAN_ERR_D1024, "search_topk: d=%lld > 1024", d, 0); return plan; }
     const bool half_only = sh.storage == STORE_F16, has_copy = sh.storage == STORE_F32_COPY;
+    // the ranges in row space, clipped to the shard, and their union per 128-row query tile (the scans' per-tile test)
+    if (b.excl) b.add(K_EXCL_PREP, cdiv64(nq, 128), 128);
     const bool small = nq <= 32 && (d == 128 || d == 64);
     // <= 32 query rows against fp32 rows with an fp16 copy: stream the copy (half the bytes) as a pre-filter and re-score
     const bool small_pre = small && has_copy && n > CAP && !t.small_f32;
@@ -271,7 +331,8 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
     }
     auto fallback = [&]() {
         plan.fallback = FB_LAUNCH;
-        b.add(half_only ? K_FALLBACK_2 : K_FALLBACK_4, nq, 256, 0, "topk_fallback");
+        const int kern = half_only ? K_FALLBACK_2 : K_FALLBACK_4;
+        b.add(b.excl ? kern + (K_FALLBACK_4_EXCL - K_FALLBACK_4) : kern, nq, 256, 0, "topk_fallback").excl = b.excl;
     };
     auto group_select = [&](int G, int ncnt, bool with_eps, float margin) -> SearchStage & {
         if (G < 1 || G > GROUPS_MAX) b.fail(PLAN_ERR_GROUPS, "group select: %lld groups (the kernel's LDS array holds %lld)", G, GROUPS_MAX);
@@ -310,14 +371,18 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
         const double bytes_per_row = (double)d * elt;
         if (n <= CAP) {
             plan.path = "small_dense";
-            b.add(K_FILL_INT, cdiv64(nq, 256)).fill = (int)n;
-            SearchStage &sc = b.add(k0 + 2, cdiv64(n, 128) < 512 ? cdiv64(n, 128) : 512, 256, 0, "scan_topk", n * bytes_per_row);
+            b.add(K_FILL_INT, cdiv64(nq, 256)).fill = b.excl ? 0 : (int)n;        // (masked: the dense pass appends)
+            SearchStage &sc = b.add_scan(k0 + 2, cdiv64(n, 128) < 512 ? cdiv64(n, 128) : 512, "scan_topk", n * bytes_per_row);
             sc.elt = elt; sc.nrows = n;
             if (has_copy) {
                 // the MFMA scores are a pre-filter, the select re-scores in the canonical order
                 plan.canonical_scores = true;
-                if (n <= SMALL_N) b.add(K_SELECT_DENSE_SMALL, nq, 256, 0, "topk_select_rescore");
-                else b.add(K_SELECT_DENSE, nq, 1024, CAP * 8, "topk_select_rescore");
+                // (masked: the rows that remain may be SMALL_N or fewer although n is not -- each select leaves the other's rows)
+                // With both, the small select counts the rows it leaves in overflow[1]; the dense select does not read it, but
+                // the counter is zeroed first all the same, so that it holds this call's count and never a sum over calls.
+                if (n <= SMALL_N || b.excl)
+                    b.add(K_SELECT_DENSE_SMALL, nq, 256, 0, "topk_select_rescore").zero_overflow = b.excl && n > SMALL_N;
+                if (n > SMALL_N) b.add(K_SELECT_DENSE, nq, 1024, CAP * 8, "topk_select_rescore");
             } else {
                 b.add(K_SELECT, nq, 1024, CAP * 8, "topk_select");
             }
@@ -329,10 +394,10 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
         const int GRID = 512, W = GRID * 4;            // persistent: 2 workgroups per CU; W groups in the sampled pass
         int64_t R = sample_ratio(k);
         if (R > n / W) R = n / W;                      // at least one sampled row per group (n > CAP = 4 W)
-        SearchStage &sm = b.add(k0 + 1, GRID, 256, 0, "scan_topk_sample", cdiv64(n, R) * bytes_per_row);
+        SearchStage &sm = b.add_scan(k0 + 1, GRID, "scan_topk_sample", cdiv64(n, R) * bytes_per_row);
         sm.elt = elt; sm.stride = R; sm.nrows = cdiv64(n, R); sm.gmax = true; sm.fold_prep = folded && elt == 2;
         group_select(W, 32, small_pre, small_pre ? 2.f : 0.f).zero_me = folded;
-        SearchStage &sc = b.add(k0, GRID, 256, 0, "scan_topk", n * bytes_per_row);
+        SearchStage &sc = b.add_scan(k0, GRID, "scan_topk", n * bytes_per_row);
         sc.elt = elt; sc.nrows = n; sc.nsub = 32; sc.thr = small_pre ? THR_ADJ : THR_EXACT;
         if (!folded) {
             select_rescore(1, 32, small_pre ? 1 : 0, false);
@@ -343,7 +408,9 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
         // the exact fallback of flagged rows -- both normally idle -- in one launch
         SearchStage &s1 = b.add(K_SELECT_RESCORE_SMALL, nq, 256, 0, small_pre ? "topk_select_rescore" : "topk_select_radix");
         s1.nsub = 32; s1.rescore = small_pre ? 1 : 0;
-        SearchStage &tl = b.add(half_only ? K_SELECT_TAIL_2 : K_SELECT_TAIL_4, nq, 1024, CAP * 8, "topk_select_tail");
+        const int tail = half_only ? K_SELECT_TAIL_2 : K_SELECT_TAIL_4;
+        SearchStage &tl = b.add(b.excl ? tail + (K_SELECT_TAIL_4_EXCL - K_SELECT_TAIL_4) : tail, nq, 1024, CAP * 8, "topk_select_tail");
+        tl.excl = b.excl;
         tl.nsub = 32; tl.rescore = s1.rescore; tl.fb_elt = half_only ? 2 : 4;
         plan.fallback = FB_TAIL;
         return plan;
@@ -360,7 +427,7 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
     auto dense_or_zero = [&](int fill_kernel, int64_t nrows, bool dense) {      // counters of a scan level; true = zero_cnt
         if (!dense) return true;
         if (nrows > CAP) b.fail(PLAN_ERR_DENSE_CAP, "scan: dense level with %lld rows > %lld", nrows, CAP);
-        b.add(fill_kernel, cdiv64(nq, 256)).fill = (int)nrows;
+        b.add(fill_kernel, cdiv64(nq, 256)).fill = b.excl ? 0 : (int)nrows;       // (masked: the dense level appends)
         return false;
     };
 
@@ -399,14 +466,14 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
                 // less than one round of the resident slots: nobody covers a tile's round trip -> three tile buffers
                 const int kern = dbr64 ? ((n_tiles_m * S < 768 || t.scan_nbuf3) ? K_QRES_8_DBR64_NBUF3 : K_QRES_8_DBR64)
                                        : (d == 128 ? K_QRES_8 : K_QRES_4);
-                sc = &b.add(kern, (int64_t)n_tiles_m * S, 256, 0, tag, work);
+                sc = &b.add_scan(kern, (int64_t)n_tiles_m * S, tag, work);
                 sc->nsub = S;
                 nsub_out = 4 * S;                  // four private lists per (row, slice), one per owner lane
             } else if (db_tiles * cdiv64(n_tiles_m, 4) >= 4096) {
                 // long runs of query tiles per block only when the grid still fills the chip many times over
-                sc = &b.add(K_SCAN_F16_QT4, db_tiles * cdiv64(n_tiles_m, 4), 256, 0, tag, work);
+                sc = &b.add_scan(K_SCAN_F16_QT4, db_tiles * cdiv64(n_tiles_m, 4), tag, work);
             } else {
-                sc = &b.add(K_SCAN_F16_QT1, db_tiles * n_tiles_m, 256, 0, tag, work);
+                sc = &b.add_scan(K_SCAN_F16_QT1, db_tiles * n_tiles_m, tag, work);
             }
             sc->elt = 2; sc->stride = st_; sc->nrows = nrows; sc->n_tiles_m = n_tiles_m; sc->zero_cnt = zero;
             sc->thr = dense ? THR_NONE : THR_ADJ;
@@ -444,7 +511,7 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
                 const int64_t nrows = cdiv64(n, gs_found);
                 // at most one workgroup per CU: nobody covers a tile's round trip -> three tile buffers (96 KB)
                 const int kern = d == 128 ? (n_tiles_m * S_found <= 256 ? K_QRES_GMAX_8_NBUF3 : K_QRES_GMAX_8) : K_QRES_GMAX_4;
-                SearchStage &sm = b.add(kern, (int64_t)n_tiles_m * S_found, 256, 0, "scan_topk_f16_sample", 2.0 * (double)nq * nrows * d);
+                SearchStage &sm = b.add_scan(kern, (int64_t)n_tiles_m * S_found, "scan_topk_f16_sample", 2.0 * (double)nq * nrows * d);
                 sm.elt = 2; sm.stride = gs_found; sm.nrows = nrows; sm.n_tiles_m = n_tiles_m; sm.nsub = S_found; sm.gmax = true;
                 SearchStage &g = group_select(plan.G, 0, true, rescore ? 2.f : 0.f);
                 g.topm = sh.phase == 1; g.margin_out = rescore ? 1.f : 0.f;
@@ -485,10 +552,10 @@ inline SearchPlan plan_search(const SearchShape &sh, const SearchTuning &t) {
         const char *tag = stride == 1 ? "scan_topk" : "scan_topk_sample";
         const double work = 2.0 * (double)nq * nrows * d;
         SearchStage *sc;
-        if (nq <= 32) sc = &b.add(K_SCAN_EMIT_32, db_tiles, 256, 0, tag, work);
-        else if (nq <= 64) sc = &b.add(K_SCAN_EMIT_64, cdiv64(nrows, 64), 256, 0, tag, work);
-        else if (db_tiles * cdiv64(n_tiles_m, 4) >= 4096) sc = &b.add(K_SCAN_EMIT_128_QT4, db_tiles * cdiv64(n_tiles_m, 4), 256, 0, tag, work);
-        else sc = &b.add(K_SCAN_EMIT_128_QT1, db_tiles * n_tiles_m, 256, 0, tag, work);
+        if (nq <= 32) sc = &b.add_scan(K_SCAN_EMIT_32, db_tiles, tag, work);
+        else if (nq <= 64) sc = &b.add_scan(K_SCAN_EMIT_64, cdiv64(nrows, 64), tag, work);
+        else if (db_tiles * cdiv64(n_tiles_m, 4) >= 4096) sc = &b.add_scan(K_SCAN_EMIT_128_QT4, db_tiles * cdiv64(n_tiles_m, 4), tag, work);
+        else sc = &b.add_scan(K_SCAN_EMIT_128_QT1, db_tiles * n_tiles_m, tag, work);
         sc->stride = stride; sc->nrows = nrows; sc->n_tiles_m = nq <= 64 ? 1 : n_tiles_m; sc->zero_cnt = zero;
         sc->thr = dense ? THR_NONE : THR_EXACT;
         b.add(K_SELECT, nq, 1024, CAP * 8, "topk_select").mode = lev == 0 ? 1 : 0;

@@ -26,12 +26,18 @@ def song_pos_from_key(landmark_key):
     return np.pad(np.cumsum(np.asarray(landmark_key), dtype=np.int64), (1, 0))      # database.py:86
 
 
-def search_plan(n, d, nq, k, storage, phase=0, resume_with_lb=False, mtop=1):
-    """pfann_search_plan parsed: storage 0 = fp32 rows only, 1 = fp32 rows + fp16 copy, 2 = fp16-only -> (stages, flags)."""
+def search_plan(n, d, nq, k, storage, phase=0, resume_with_lb=False, mtop=1, excl=False):
+    """pfann_search_plan parsed: storage 0 = fp32 rows only, 1 = fp32 rows + fp16 copy, 2 = fp16-only -> (stages, flags).
+    excl: the plan of the search with a row range left out per query row (pfann_search_plan_excl; phase 0 only)."""
     lib = _l.load()
     buf = ctypes.create_string_buffer(16384)
-    _l.check(lib.pfann_search_plan(n, d, nq, k, storage, phase, 1 if resume_with_lb else 0, mtop, buf, len(buf)),
-             "pfann_search_plan")
+    if excl:
+        if phase != 0:
+            raise ValueError("search_plan: the masked search has no sharded halves (phase %r)" % (phase,))
+        _l.check(lib.pfann_search_plan_excl(n, d, nq, k, storage, buf, len(buf)), "pfann_search_plan_excl")
+    else:
+        _l.check(lib.pfann_search_plan(n, d, nq, k, storage, phase, 1 if resume_with_lb else 0, mtop, buf, len(buf)),
+                 "pfann_search_plan")
     lines = buf.value.decode().splitlines()
     stages = []
     for ln in lines[:-1]:
@@ -98,7 +104,7 @@ class DeviceIndex:
         self._prefilter = bool(on)
         return bool(self.lib.pfann_db_set_prefilter(self.handle, 1 if on else 0))
 
-    def search_plan(self, nq, k, phase=0, resume_with_lb=False, mtop=1):
+    def search_plan(self, nq, k, phase=0, resume_with_lb=False, mtop=1, excl=False):
         """What search (phase 0), search_bound (1, mtop = its m) or search_bounded (2; resume_with_lb: behind the
         search_bound of the same q) launches for nq query rows against this shard, from pfann_search_plan: ->
         (stages, flags), stages = [(kernel, grid, block, dynamic LDS bytes)] in launch order, flags = the dict of the last
@@ -107,17 +113,28 @@ class DeviceIndex:
             storage = 2
         else:
             storage = 1 if self.lib.pfann_db_set_prefilter(self.handle, 1 if self._prefilter else 0) else 0
-        return search_plan(self.ntotal, self.d, nq, k, storage, phase, resume_with_lb, mtop)
+        return search_plan(self.ntotal, self.d, nq, k, storage, phase, resume_with_lb, mtop, excl)
 
     def _stream(self):
         return _l.current_stream_ptr(self.device)
 
-    def search(self, q, k):
-        """index.search(q, k): q torch cuda [nq, d] -> (D [nq,k] f32 desc, I [nq,k] int64) on device."""
+    def search(self, q, k, exclude=None):
+        """index.search(q, k): q torch cuda [nq, d] -> (D [nq,k] f32 desc, I [nq,k] int64) on device.
+        exclude = (lo, hi), two int64 tensors or arrays of length nq: query row m is answered over the rows whose label is
+        not in [lo[m], hi[m]) (pfann_search_topk_excl: exact, not a post-filter; lo >= hi excludes nothing)."""
         q = q.to(self.device, torch.float32).contiguous()
         nq = q.shape[0]
         D = torch.empty((nq, k), device=self.device, dtype=torch.float32)
         I = torch.empty((nq, k), device=self.device, dtype=torch.int64)
+        if exclude is not None:
+            lo, hi = (x.to(self.device, torch.int64).contiguous() if isinstance(x, torch.Tensor)
+                      else _l.upload_async(np.asarray(x), self.device, np.int64) for x in exclude)
+            if lo.shape != (nq,) or hi.shape != (nq,):
+                raise ValueError("search: exclude wants two arrays of %d rows (got %r, %r)" % (nq, tuple(lo.shape), tuple(hi.shape)))
+            if nq:
+                _l.check(self.lib.pfann_search_topk_excl(self.handle, q.data_ptr(), nq, k, lo.data_ptr(), hi.data_ptr(),
+                                                         D.data_ptr(), I.data_ptr(), self._stream()), "pfann_search_topk_excl")
+            return D, I
         if nq:
             _l.check(self.lib.pfann_search_topk(self.handle, q.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(),
                                                 self._stream()), "pfann_search_topk")
@@ -353,6 +370,28 @@ def window_counts(rlen, window, hop):
     one window over all rows when 0 < L < window; none when L == 0"""
     L = np.asarray(rlen, dtype=np.int64)
     return np.where(L <= 0, 0, np.where(L < window, 1, (L - window) // hop + 1)).astype(np.int64)
+
+
+def self_match_ranges(song_pos, song_lo, song_hi):
+    """Self-match of the songs [song_lo, song_hi) -> (rstart, rlen, lo, hi): song s is recording s - song_lo, rows
+    [rstart, rstart + rlen) of the group's rows (rstart counts from the group's first row); lo / hi [rows]: the label
+    range every row leaves out, its own song's [song_pos[s], song_pos[s + 1]).  Songs without rows have rlen 0."""
+    pos = np.asarray(song_pos, dtype=np.int64)[song_lo:song_hi + 1]
+    rlen = np.diff(pos)
+    return (pos[:-1] - pos[0]).astype(np.int64), rlen.astype(np.int32), np.repeat(pos[:-1], rlen), np.repeat(pos[1:], rlen)
+
+
+def self_match_groups(song_pos, song_lo, song_hi, max_rows):
+    """[(a, b)]: consecutive song ranges covering [song_lo, song_hi), each with at most max_rows rows unless it is one song"""
+    pos = np.asarray(song_pos, dtype=np.int64)
+    out, a = [], song_lo
+    while a < song_hi:
+        b = a + 1
+        while b < song_hi and pos[b + 1] - pos[a] <= max_rows:
+            b += 1
+        out.append((a, b))
+        a = b
+    return out
 
 
 def _fine_to_time(fine, fsm, hop_size):
@@ -712,8 +751,8 @@ class Database:
                 p["edge_rows"] = self._monitor_rows(self.index.results_to_host(p["fine"][0]), p["fine"][1], 1, p["mode"])
         return out
 
-    def _monitor_rows(self, res, wfirst, hop, mode):
-        fsm = self.frame_shift_mul
+    def _monitor_rows(self, res, wfirst, hop, mode, fsm=None):
+        fsm = self.frame_shift_mul if fsm is None else fsm
         out = []
         for r in range(len(wfirst) - 1):
             rr = res[wfirst[r]:wfirst[r + 1]]
@@ -734,6 +773,72 @@ class Database:
                 rows["time_s"] = np.where(ok, (off - shift / fsm) * self.hop_size, 0.0)
             out.append(rows)
         return out
+
+    # ---- self-match: the database asked about itself ------------------------------------------------
+    def _embeddings_map(self):
+        """the `embeddings` file of the database directory, memory-mapped [rows, d] (builder.py writes it)"""
+        if getattr(self, "_emb_map", None) is None:
+            path = os.path.join(self.dir_for_db, "embeddings")
+            n_rows = int(self.song_pos[-1])
+            if not os.path.exists(path) or os.path.getsize(path) != n_rows * self.d * 4:
+                raise _l.PfannError("self-match reads the query rows from %s: missing, or not %d x %d float32" % (path, n_rows, self.d))
+            self._emb_map = np.memmap(path, dtype=np.float32, mode="r", shape=(n_rows, self.d)) if n_rows else np.zeros((0, self.d), np.float32)
+        return self._emb_map
+
+    def self_match_launch(self, song_lo, song_hi, window, hop, k=None, emb=None):
+        """One launch group of self-match, asynchronous like monitor_launch: the rows of the songs [song_lo, song_hi) are the
+        recordings (song s: rows [song_pos[s], song_pos[s + 1]) of `emb`, by default the memory-mapped `embeddings` file),
+        every row is searched with its own song's rows left out (pfann_search_topk_excl: exact, the own rows are never
+        nominated), and the windowed matcher answers every window of `window` rows, `hop` apart.  The rows are database
+        rows, one per hop_size, so the matcher runs with frame_shift_mul 1.  Songs without rows give no windows."""
+        if self.sharded is not None:
+            raise _l.PfannError("self-match is not song-sharded: the whole database sits on one handle (run without "
+                                "PFANN_GPUS / ranks)")
+        song_lo, song_hi = int(song_lo), int(song_hi)
+        if not 0 <= song_lo <= song_hi <= len(self.songList):
+            raise ValueError("self_match: songs [%d, %d) outside 0..%d" % (song_lo, song_hi, len(self.songList)))
+        emb = self._embeddings_map() if emb is None else emb
+        rstart, rlen, lo, hi = self_match_ranges(self.song_pos, song_lo, song_hi)
+        r0, r1 = int(self.song_pos[song_lo]), int(self.song_pos[song_hi])
+        dev = self.index.device
+        q = _l.upload_async(np.array(emb[r0:r1], dtype=np.float32).reshape(-1, self.d), dev, np.float32)
+        mode = 1 if cpp_accelerate else 0
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        D, I = self.index.search(q, self.top_k if k is None else int(k), exclude=(lo, hi))
+        ev[1].record()
+        res, wfirst = self.index.match_windows(q, I, rstart, rlen, window, hop, 1, self.score_alpha, mode, to_host=False)
+        ev[2].record()
+        return {"res": res, "wfirst": wfirst, "ev": ev, "hop": int(hop), "keep": (q, I), "dev": dev, "mode": mode,
+                "songs": (song_lo, song_hi)}
+
+    def self_match_finish(self, p):
+        """-> per song of the group a structured array (w0, score, song, time_s), one entry per window, as monitor_finish"""
+        if getattr(self, "_copy_stream", None) is None:
+            self._copy_stream = torch.cuda.Stream(p["dev"])
+            self._pin = {}
+        with torch.cuda.stream(self._copy_stream):
+            self._copy_stream.wait_event(p["ev"][-1])
+            res = self.index.results_to_host(p["res"])
+        if self.timer is not None:
+            self.timer.mark_gpu("search", p["ev"][0], p["ev"][1])
+            self.timer.mark_gpu("rerank", p["ev"][1], p["ev"][2])
+            self.timer.resolve()
+        return self._monitor_rows(res, p["wfirst"], p["hop"], p["mode"], fsm=1)
+
+    def self_match(self, song_lo, song_hi, window, hop, k=None, emb=None, max_rows=None):
+        """Self-match of the songs [song_lo, song_hi): yields (song, rows) in song order, rows as monitor_finish gives them.
+        The songs are cut into launch groups of at most max_rows rows (default PFANN_MAX_BATCH, 9728; a longer song is a
+        group of its own) and group g + 1 is launched before group g is read back, as the monitor does."""
+        max_rows = int(os.environ.get("PFANN_MAX_BATCH", "9728")) if max_rows is None else int(max_rows)
+        in_flight = None
+        for a, b in self_match_groups(self.song_pos, int(song_lo), int(song_hi), max_rows):
+            nxt = self.self_match_launch(a, b, window, hop, k, emb)
+            if in_flight is not None:
+                yield from zip(range(*in_flight["songs"]), self.self_match_finish(in_flight))
+            in_flight = nxt
+        if in_flight is not None:
+            yield from zip(range(*in_flight["songs"]), self.self_match_finish(in_flight))
 
     # ---- the reference's per-query contract ---------------------------------------------
     def query_embeddings(self, query):
