@@ -9,6 +9,7 @@ contract, python-path semantics (cpp_accelerate=False, database.py:12).
 """
 import contextlib
 import ctypes
+import itertools
 import json
 import os
 import struct
@@ -213,12 +214,21 @@ class DeviceIndex:
 
     RESULT_DTYPE = np.dtype([("song", "<i4"), ("offset", "<i4"), ("shift", "<i4"), ("n_cand", "<i4"), ("score", "<f8")])
 
-    def results_to_host(self, res_dev):
-        """device results (uint8 [nQ, 24]) -> structured numpy array: the ONE device-to-host copy of a step."""
-        out = np.frombuffer(res_dev.cpu().numpy().tobytes(), dtype=self.RESULT_DTYPE)
+    @classmethod
+    def decode_results(cls, raw, shape=-1):
+        """Result bytes -> RESULT_DTYPE array, the ONE place that reads them: a tensor of 24-byte results ([..., 24] uint8, on
+        the device -- then this is the one device-to-host copy of a step -- or the pinned buffer the kernel wrote into) gives
+        the shape of its leading dimensions, host bytes give `shape`.  A song of -2 is the matcher's refusal."""
+        if isinstance(raw, torch.Tensor):
+            raw, shape = raw.cpu().numpy().tobytes(), tuple(raw.shape[:-1])
+        out = np.frombuffer(raw, dtype=cls.RESULT_DTYPE).reshape(shape)
         if (out["song"] == -2).any():
             raise _l.PfannError("matcher refused a query (candidate buffer sizing error)")
         return out
+
+    def results_to_host(self, res_dev):
+        """device results (uint8 [nQ, 24]) -> structured numpy array: the ONE device-to-host copy of a step."""
+        return self.decode_results(res_dev)
 
     def pack_winner_keys(self, res_dev):
         """-> int64 [nQ, 2] device tensor of 128-bit keys (bit patterns of two uint64), see pfann_match_pack."""
@@ -250,15 +260,20 @@ class DeviceIndex:
                      "pfann_song_scores_to_seconds")
         return ss
 
+    def _match_args(self, q, labels, start, length):
+        """the matchers' shared arguments -> (q float32, labels int64 on the device; start int64, length int32 host arrays)"""
+        return (q.to(self.device, torch.float32).contiguous(), labels.to(self.device, torch.int64).contiguous(),
+                np.ascontiguousarray(start, dtype=np.int64), np.ascontiguousarray(length, dtype=np.int32))
+
+    def _upload_ranges(self, start_np, length_np):
+        return _l.upload_async(start_np, self.device, np.int64), _l.upload_async(length_np, self.device, np.int32)
+
     def match(self, q, labels, qstart, qlen, fsm=1, alpha=0.0, mode=0, only_owned=False, want_song_scores=False,
               to_host=True, owned_block=False):
         """Sequence matcher for nQ queries.  Returns (results structured array -- or, with to_host=False, the device
         tensor of results --, song_scores or None).  owned_block (with only_owned): song_scores is [nQ, owned songs, 2],
         this shard's columns of the score matrix, instead of [nQ, n_songs, 2]."""
-        q = q.to(self.device, torch.float32).contiguous()
-        labels = labels.to(self.device, torch.int64).contiguous()
-        qs_np = np.ascontiguousarray(qstart, dtype=np.int64)
-        ql_np = np.ascontiguousarray(qlen, dtype=np.int32)
+        q, labels, qs_np, ql_np = self._match_args(q, labels, qstart, qlen)
         nQ = int(ql_np.shape[0])
         if nQ <= 4:
             # the one-query regime calls with the same tiny (qstart, qlen) over and over: keep their device copies
@@ -267,12 +282,10 @@ class DeviceIndex:
             if hit is None:
                 if len(self._small_args) > 64:
                     self._small_args.clear()
-                hit = (_l.upload_async(qs_np, self.device, np.int64), _l.upload_async(ql_np, self.device, np.int32))
-                self._small_args[key] = hit
+                hit = self._small_args[key] = self._upload_ranges(qs_np, ql_np)
             qs, ql = hit
         else:
-            qs = _l.upload_async(qs_np, self.device, np.int64)
-            ql = _l.upload_async(ql_np, self.device, np.int32)
+            qs, ql = self._upload_ranges(qs_np, ql_np)
         k = labels.shape[1]
         rsz = ctypes.sizeof(_l.MatchResult)
         host_res = None
@@ -299,34 +312,23 @@ class DeviceIndex:
             return res, ss
         if host_res is not None:
             torch.cuda.current_stream(self.device).synchronize()
-            out = np.frombuffer(host_res.numpy().tobytes(), dtype=self.RESULT_DTYPE)
-            if (out["song"] == -2).any():
-                raise _l.PfannError("matcher refused a query (candidate buffer sizing error)")
-            return out, ss
+            return self.decode_results(host_res), ss
         return self.results_to_host(res), ss
 
     def topn_to_host(self, top_dev, n_found_dev):
         """device top-N lists (uint8 [nQ, n, 24]) and counts -> (structured array [nQ, n], int32 [nQ])"""
-        nQ, n = top_dev.shape[0], top_dev.shape[1]
-        out = np.frombuffer(top_dev.cpu().numpy().tobytes(), dtype=self.RESULT_DTYPE).reshape(nQ, n)
-        if (out["song"] == -2).any():
-            raise _l.PfannError("matcher refused a query (candidate buffer sizing error)")
-        return out, n_found_dev.cpu().numpy()
+        return self.decode_results(top_dev), n_found_dev.cpu().numpy()
 
     def match_topn(self, q, labels, qstart, qlen, n, fsm=1, alpha=0.0, mode=0, only_owned=False, to_host=True):
         """Ranked answers (pfann_match_topn): the n best songs of each of nQ queries, selected on the device -- no per-song
         block.  -> (structured array [nQ, n] of RESULT_DTYPE, n_found int32 [nQ]); entry [j, 0] is `match`'s answer,
         entries past the candidate songs are song -1 / score -inf; with to_host=False the two device tensors (uint8
         [nQ, n, 24], int32 [nQ]) that topn_to_host turns into the arrays later."""
-        q = q.to(self.device, torch.float32).contiguous()
-        labels = labels.to(self.device, torch.int64).contiguous()
-        qs_np = np.ascontiguousarray(qstart, dtype=np.int64)
-        ql_np = np.ascontiguousarray(qlen, dtype=np.int32)
+        q, labels, qs_np, ql_np = self._match_args(q, labels, qstart, qlen)
         nQ, n = int(ql_np.shape[0]), int(n)
         if not 1 <= n <= 64:
             raise _l.PfannError("match_topn: n=%d outside 1..64" % n)
-        qs = _l.upload_async(qs_np, self.device, np.int64)
-        ql = _l.upload_async(ql_np, self.device, np.int32)
+        qs, ql = self._upload_ranges(qs_np, ql_np)
         top = torch.empty((nQ, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
         n_found = torch.empty((nQ,), device=self.device, dtype=torch.int32)
         if nQ:
@@ -346,18 +348,14 @@ class DeviceIndex:
         window, hop = int(window), int(hop)
         if window < 1 or hop < 1:
             raise ValueError("match_windows: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
-        q = q.to(self.device, torch.float32).contiguous()
-        labels = labels.to(self.device, torch.int64).contiguous()
-        rs_np = np.ascontiguousarray(rstart, dtype=np.int64)
-        rl_np = np.ascontiguousarray(rlen, dtype=np.int32)
+        q, labels, rs_np, rl_np = self._match_args(q, labels, rstart, rlen)
         nR = int(rl_np.shape[0])
         assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
         wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
         nW = int(wfirst[-1])
         res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
         if nW:
-            rs = _l.upload_async(rs_np, self.device, np.int64)
-            rl = _l.upload_async(rl_np, self.device, np.int32)
+            rs, rl = self._upload_ranges(rs_np, rl_np)
             wf = _l.upload_async(wfirst, self.device, np.int64)
             _l.check(self.lib.pfann_match_windows(self.handle, q.data_ptr(), labels.data_ptr(), labels.shape[1], rs.data_ptr(),
                                                   rl.data_ptr(), nR, window, hop, int(fsm), float(alpha), int(mode),
@@ -408,32 +406,103 @@ def _fine_to_time(fine, fsm, hop_size):
 cpp_accelerate = os.environ.get("PFANN_CPP_ACCELERATE", "0") not in ("0", "")
 
 
+def default_mode(mode=None):
+    """the matcher mode of a launch that names none: the module switch above"""
+    return (1 if cpp_accelerate else 0) if mode is None else mode
+
+
+MONITOR_DTYPE = np.dtype([("w0", "<i8"), ("score", "<f8"), ("song", "<i8"), ("time_s", "<f8")])
+
+
+def format_results(res, mode, fsm, hop_size, empty_db=False):
+    """RESULT_DTYPE array of any shape -> (score float64, song int64, time_s float64) of that shape: the ONE statement of
+    how a 24-byte match result becomes an answer, for every query form.
+    mode 0, query_embeddings_base (database.py:148): (score, song, (offset - shift / fsm) * hop_size); no candidate
+    (song < 0) or an empty database: (-inf, -1, 0).
+    mode 1, query_embeddings_cpp (database.py:166-195), reads score and time back from the per-song block, which holds
+    float32 and only ever records scores > 0: (float32 score, song, float32(offset * fsm - shift) * hop_size / fsm); no
+    candidate or a float32 score that is not > 0: (0, song or -1, 0)."""
+    song = res["song"].astype(np.int64)
+    off, shift = res["offset"].astype(np.int64), res["shift"].astype(np.int64)
+    if mode == 1:
+        sc = res["score"].astype(np.float32)
+        ok = (song >= 0) & (sc > 0)
+        fine = (off * fsm - shift).astype(np.float32).astype(np.float64)
+        return np.where(ok, sc.astype(np.float64), 0.0), np.where(song >= 0, song, -1), np.where(ok, fine * hop_size / fsm, 0.0)
+    ok = (song >= 0) & (not empty_db)
+    return np.where(ok, res["score"], -np.inf), np.where(ok, song, -1), np.where(ok, (off - shift / fsm) * hop_size, 0.0)
+
+
+def _as_tuples(score, song, time_s, mode):
+    """flat format_results arrays as the reference's Python objects: [(score, (song, time_s))], floats and ints; the mode-0
+    answer without a candidate is (-1e999, (-1, 0)) with the reference's int 0"""
+    times = time_s.tolist()
+    if mode != 1:
+        for j in np.flatnonzero(song < 0):
+            times[j] = 0
+    return list(zip(score.tolist(), zip(song.tolist(), times)))
+
+
+def result_tuples(res, mode, fsm, hop_size, empty_db=False):
+    """RESULT_DTYPE [n] -> [(score, (song, time_s))]: what query_finish answers per query, before the per-song block"""
+    return _as_tuples(*format_results(res, mode, fsm, hop_size, empty_db), mode)
+
+
+def topn_tuples(top, mode, fsm, hop_size, empty_db=False):
+    """RESULT_DTYPE [nQ, n] ranked lists -> per query the list of result_tuples entries that count: entry 0 always (it is
+    the query's answer, also without a candidate), later entries up to the first song < 0, and in mode 1 only those with
+    a float32 score > 0 -- the reference's per-song block never records the others."""
+    nq, n = top.shape
+    score, song, time_s = format_results(top, mode, fsm, hop_size, empty_db)
+    keep = np.ones((nq, n), dtype=bool)
+    keep[:, 1:] = np.logical_and.accumulate(top["song"][:, 1:] >= 0, axis=1)
+    if mode == 1:
+        keep[:, 1:] &= score[:, 1:] > 0
+    flat = _as_tuples(score.ravel(), song.ravel(), time_s.ravel(), mode)
+    return [[flat[i] for i in np.flatnonzero(row) + j * n] for j, row in enumerate(keep)]
+
+
+def monitor_rows(res, wfirst, hop, mode, fsm, hop_size):
+    """windowed results -> per recording a MONITOR_DTYPE array (w0, score, song, time_s): recording r's windows are
+    res[wfirst[r]:wfirst[r + 1]], `hop` rows apart"""
+    score, song, time_s = format_results(res, mode, fsm, hop_size)
+    out = []
+    for a, b in zip(wfirst[:-1], wfirst[1:]):
+        rows = np.zeros(b - a, dtype=MONITOR_DTYPE)
+        rows["w0"] = np.arange(b - a, dtype=np.int64) * hop
+        rows["score"], rows["song"], rows["time_s"] = score[a:b], song[a:b], time_s[a:b]
+        out.append(rows)
+    return out
+
+
+def launch_ahead(items, launch):
+    """-> iterator of launch(item) in order, one launch ahead of its consumer: the first launch is made at once, and item
+    g + 1 is launched before item g's launch is handed out to be read back, so the GPU has work while the host reads."""
+    items = iter(items)
+
+    def hand_out(cur):
+        while cur:
+            nxt = [launch(x) for x in itertools.islice(items, 1)]
+            yield cur[0]
+            cur = nxt
+    return hand_out([launch(x) for x in itertools.islice(items, 1)])
+
+
 class LazyLaunches:
     """[(j0, j1)] cuts + launch(j0, j1) -> iterable of (j0, j1, launch result) with the first launch made at once and
-    every later one made when its predecessor is handed out (so: one ahead of what the consumer is reading back)."""
+    every later one made when its predecessor is handed out (launch_ahead)."""
 
     def __init__(self, cuts, launch):
-        self._cuts, self._launch, self._next, self._ready = list(cuts), launch, 0, []
-        self.max_in_flight = 0                       # (for the tests: launched and not yet handed out + the one handed out)
-        if self._cuts:
-            self._start_one()
-
-    def _start_one(self):
-        j0, j1 = self._cuts[self._next]
-        self._next += 1
-        self._ready.append((j0, j1, self._launch(j0, j1)))
+        self._cuts = list(cuts)
+        self._it = launch_ahead(self._cuts, lambda c: (c[0], c[1], launch(*c)))
+        self.max_in_flight = 0                       # (for the tests: the one handed out + its successor, when it has one)
 
     def __len__(self):
         return len(self._cuts)
 
     def __iter__(self):
-        while self._ready or self._next < len(self._cuts):
-            if not self._ready:
-                self._start_one()
-            cur = self._ready.pop(0)
-            if self._next < len(self._cuts):
-                self._start_one()                    # the successor is in flight before `cur` is read back
-            self.max_in_flight = max(self.max_in_flight, 1 + len(self._ready))
+        for g, cur in enumerate(self._it, 1):
+            self.max_in_flight = max(self.max_in_flight, 1 + (g < len(self._cuts)))
             yield cur
 
 
@@ -453,6 +522,8 @@ class Database:
         self.hop_size = hop_size
         self.score_alpha = self.params.get("score_alpha", 0)
         self.timer = None          # a utils.StageTimer: query_batch then reports 'search' and 'rerank' separately
+        self._copy_stream = None   # the side stream results are read back on (_read_back makes it at the first read)
+        self._pin = {}             # pinned landing buffers of _pinned, by dtype
 
         self.songList = read_file_list(os.path.join(dir_for_db, "songList.txt"))
         key = np.fromfile(os.path.join(dir_for_db, "landmarkKey"), dtype=np.int32)
@@ -533,9 +604,7 @@ class Database:
     def query_launch(self, emb, qstart, qlen, want_song_scores=False, mode=None):
         """First half of query_batch: search + sequence match launched asynchronously, nothing read back.  The CLIs launch
         group g+1 before they finish group g, so the GPU never idles while the host formats and writes results."""
-        dev = self.index.device
-        if mode is None:
-            mode = 1 if cpp_accelerate else 0
+        mode = default_mode(mode)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] + [torch.cuda.Event()]
         # song-sharded, PFANN_EXCHANGE_STREAM=1: search, collectives, matcher and winner pick run on the exchange stream
         # (dist.ShardedIndex.exchange), so the next group's encoder does not queue behind the collectives
@@ -557,7 +626,7 @@ class Database:
             # with fine = t*fsm - shift, in double like the reference's Python floats, stored as float32
             self.index.song_scores_to_seconds(ss, self.frame_shift_mul, self.hop_size, native_path=mode == 1)
             ev[3].record()              # (the block is complete HERE, not at ev[2]: query_finish copies it after this one)
-        return {"res": res, "ss": ss, "ev": ev, "nq": len(qlen), "keep": (emb, I), "dev": dev, "mode": mode}
+        return {"res": res, "ss": ss, "ev": ev, "keep": (emb, I), "mode": mode}
 
     def query_launch_chunks(self, emb, qstart, qlen, want_song_scores=False, mode=None):
         """query_launch over as many sub-launches as the score-block budget asks for (PFANN_SCORE_BLOCK_MB, default
@@ -590,48 +659,54 @@ class Database:
             self._pin[key] = buf
         return buf[:n].view(shape)
 
-    def query_finish(self, p, reuse_buffers=False):
-        """Second half: wait for that group only (a side stream copies its results; later groups keep running) and
-        return the list of (score, (song, time), song_score|None).  reuse_buffers: the song_score blocks are views of a
-        pinned buffer that the NEXT query_finish overwrites (the CLIs write them out at once)."""
-        if getattr(self, "_copy_stream", None) is None:
-            self._copy_stream = torch.cuda.Stream(p["dev"])
-            self._pin = {}
+    def _launch(self, emb, match, mode=None, k=None, exclude=None):
+        """The single-GPU launch skeleton: timed event, search, timed event, match(labels, mode) -> dict of what it left on
+        the device, timed event; nothing is read back.  -> that dict + the keys every finish half reads."""
+        mode = default_mode(mode)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        D, I = self.index.search(emb, self.top_k if k is None else int(k), exclude=exclude)
+        ev[1].record()
+        out = match(I, mode)
+        ev[2].record()
+        return dict(out, ev=ev, keep=(emb, I), mode=mode)
+
+    def _read_back(self, p):
+        """The one read-back of a launch p: on the copy stream, behind its last event (a side stream copies that group's
+        results; later groups keep running), p["res"] -> RESULT_DTYPE array and the per-song block p["ss"] -> a view of
+        the reused pinned buffer (or None).  A launch that carries the three timed events (every one but
+        query_topn_again's) gives the timer its stage split, as database.py:165 logs it."""
+        ev, ss = p["ev"], p.get("ss")
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(self.index.device)
+        land = None
         with torch.cuda.stream(self._copy_stream):
-            self._copy_stream.wait_event(p["ev"][-1])
-            ss_np = None
-            if p["ss"] is not None:
-                land = self._pinned(p["ss"].shape, torch.float32)
-                land.copy_(p["ss"], non_blocking=True)
-            res = self.index.results_to_host(p["res"])    # synchronises the copy stream: `land` is complete too
-            if p["ss"] is not None:
+            self._copy_stream.wait_event(ev[-1])
+            if ss is not None:
+                land = self._pinned(ss.shape, torch.float32)
+                land.copy_(ss, non_blocking=True)
+            out = self.index.decode_results(p["res"])     # synchronises the copy stream: `land` is complete too
+            if ss is not None:
                 self._copy_stream.synchronize()
-                ss_np = land.numpy() if reuse_buffers else land.numpy().copy()
-        if self.timer is not None:                        # stage split as database.py:165 logs it, from events
-            self.timer.mark_gpu("search", p["ev"][0], p["ev"][1])
-            self.timer.mark_gpu("rerank", p["ev"][1], p["ev"][2])
+        if self.timer is not None and len(ev) >= 3:
+            self.timer.mark_gpu("search", ev[0], ev[1])
+            self.timer.mark_gpu("rerank", ev[1], ev[2])
             self.timer.resolve()
-        out = []
-        fsm = self.frame_shift_mul
-        for j in range(p["nq"]):
-            r = res[j]
-            song_score = ss_np[j] if ss_np is not None else None
-            if p.get("mode", 0) == 1:
-                # query_embeddings_cpp (database.py:166-195) reads score and time back from the per-song block, which only
-                # ever records scores > 0 (no candidate: song_score[-1], the last song's untouched row)
-                sc32 = float(np.float32(r["score"])) if r["song"] >= 0 else 0.0
-                if r["song"] < 0 or not sc32 > 0.0:
-                    out.append((0.0, (int(r["song"]) if r["song"] >= 0 else -1, 0.0), song_score))
-                else:
-                    fine = float(np.float32(int(r["offset"]) * fsm - int(r["shift"])))
-                    out.append((sc32, (int(r["song"]), fine * self.hop_size / fsm), song_score))
-                continue
-            if self.index.ntotal == 0 or r["song"] < 0:
-                out.append((-1e999, (-1, 0), song_score))
-                continue
-            real_time = (int(r["offset"]) - int(r["shift"]) / fsm) * self.hop_size
-            out.append((float(r["score"]), (int(r["song"]), real_time), song_score))
-        return out
+        return out, land
+
+    def _answers(self, res, mode, tuples=result_tuples):
+        return tuples(res, mode, self.frame_shift_mul, self.hop_size, empty_db=self.index.ntotal == 0)
+
+    def query_finish(self, p, reuse_buffers=False):
+        """Second half: wait for that group only and return the list of (score, (song, time), song_score|None).
+        reuse_buffers: the song_score blocks are views of a pinned buffer that the NEXT query_finish overwrites (the CLIs
+        write them out at once)."""
+        res, land = self._read_back(p)
+        if land is None:
+            blocks = [None] * len(res)
+        else:
+            blocks = land.numpy() if reuse_buffers else land.numpy().copy()
+        return [r + (b,) for r, b in zip(self._answers(res, p["mode"]), blocks)]
 
     def query_batch(self, emb, qstart, qlen, want_song_scores=False, mode=None):
         """emb: torch cuda [sum(qlen), d] unit-norm rows; -> list of (score, (song, time), song_score|None)."""
@@ -642,67 +717,28 @@ class Database:
         """First half of query_topn_batch: search + top-N sequence match (pfann_match_topn) launched asynchronously."""
         if self.ranks is not None:
             raise _l.PfannError("top-N over a sharded database is not supported")
-        if mode is None:
-            mode = 1 if cpp_accelerate else 0
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
-        D, I = self.index.search(emb, self.top_k)
-        ev[1].record()
-        top, n_found = self.index.match_topn(emb, I, qstart, qlen, n, self.frame_shift_mul, self.score_alpha, mode,
-                                             False, to_host=False)
-        ev[2].record()
-        return {"top": top, "n_found": n_found, "ev": ev, "nq": len(qlen), "keep": (emb, I), "dev": self.index.device,
-                "mode": mode}
+        return self._launch(emb, lambda I, mode: self._match_topn(emb, I, qstart, qlen, n, mode), mode)
+
+    def _match_topn(self, emb, I, qstart, qlen, n, mode):
+        top, n_found = self.index.match_topn(emb, I, qstart, qlen, n, self.frame_shift_mul, self.score_alpha, mode, False,
+                                             to_host=False)
+        return {"res": top, "n_found": n_found}
 
     def query_topn_again(self, p, qstart, qlen, n):
         """the ranked lists of a launch query_launch made (p), from the labels its search left on the device: for a caller
         that wants the per-song block AND the top-N (the matcher CLI with --top).  -> what query_topn_finish takes"""
         if self.ranks is not None:
             raise _l.PfannError("top-N over a sharded database is not supported")
-        emb, I = p["keep"]
-        top, n_found = self.index.match_topn(emb, I, qstart, qlen, n, self.frame_shift_mul, self.score_alpha, p["mode"],
-                                             False, to_host=False)
+        out = self._match_topn(*p["keep"], qstart, qlen, n, p["mode"])
         ev = torch.cuda.Event()
         ev.record()
-        return {"top": top, "n_found": n_found, "ev": [ev], "nq": len(qlen), "keep": p["keep"], "dev": p["dev"], "mode": p["mode"]}
+        return dict(out, ev=[ev], keep=p["keep"], mode=p["mode"])
 
     def query_topn_finish(self, p):
         """Second half: -> per query a list of up to n (score, (song, time_s)), best first, by the formulas query_finish
         applies to the winner in the same mode; entry 0 IS query_finish's answer (also when there is no candidate).  Native
-        path (mode 1): later entries whose float32 score is not > 0 are dropped -- the reference's per-song block never
-        records them."""
-        if getattr(self, "_copy_stream", None) is None:
-            self._copy_stream = torch.cuda.Stream(p["dev"])
-            self._pin = {}
-        with torch.cuda.stream(self._copy_stream):
-            self._copy_stream.wait_event(p["ev"][-1])
-            top, _ = self.index.topn_to_host(p["top"], p["n_found"])
-        if self.timer is not None and len(p["ev"]) == 3:
-            self.timer.mark_gpu("search", p["ev"][0], p["ev"][1])
-            self.timer.mark_gpu("rerank", p["ev"][1], p["ev"][2])
-            self.timer.resolve()
-        fsm = self.frame_shift_mul
-        out = []
-        for j in range(p["nq"]):
-            rows = []
-            for i, r in enumerate(top[j]):
-                if i and r["song"] < 0:
-                    break
-                if p["mode"] == 1:
-                    sc32 = float(np.float32(r["score"])) if r["song"] >= 0 else 0.0
-                    if r["song"] < 0 or not sc32 > 0.0:
-                        if i:
-                            continue
-                        rows.append((0.0, (int(r["song"]) if r["song"] >= 0 else -1, 0.0)))
-                    else:
-                        fine = float(np.float32(int(r["offset"]) * fsm - int(r["shift"])))
-                        rows.append((sc32, (int(r["song"]), fine * self.hop_size / fsm)))
-                elif self.index.ntotal == 0 or r["song"] < 0:
-                    rows.append((-1e999, (-1, 0)))
-                else:
-                    rows.append((float(r["score"]), (int(r["song"]), (int(r["offset"]) - int(r["shift"]) / fsm) * self.hop_size)))
-            out.append(rows)
-        return out
+        path (mode 1): later entries whose float32 score is not > 0 are dropped (topn_tuples)."""
+        return self._answers(self._read_back(p)[0], p["mode"], topn_tuples)
 
     def query_topn_batch(self, emb, qstart, qlen, n, mode=None):
         """emb: torch cuda [sum(qlen), d] unit-norm rows; -> per query the ranked list of (score, (song, time_s))."""
@@ -718,60 +754,25 @@ class Database:
         if self.sharded is not None:
             raise _l.PfannError("monitor mode is not song-sharded: a recording is matched on one GPU against the whole "
                                 "database (run without PFANN_GPUS / ranks)")
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
-        D, I = self.index.search(emb, self.top_k)
-        ev[1].record()
-        res, wfirst = self.index.match_windows(emb, I, rstart, rlen, window, hop, self.frame_shift_mul, self.score_alpha,
-                                               1 if cpp_accelerate else 0, to_host=False)
-        fine = self.index.match_windows(emb, I, rstart, rlen, edge_window, 1, self.frame_shift_mul, self.score_alpha,
-                                        1 if cpp_accelerate else 0, to_host=False) if edge_window > 0 else None
-        ev[2].record()
-        return {"res": res, "wfirst": wfirst, "fine": fine, "ev": ev, "hop": int(hop), "keep": (emb, I), "dev": self.index.device,
-                "mode": 1 if cpp_accelerate else 0}
 
-    MONITOR_DTYPE = np.dtype([("w0", "<i8"), ("score", "<f8"), ("song", "<i8"), ("time_s", "<f8")])
+        def match(I, mode):
+            windows = lambda w, h: self.index.match_windows(emb, I, rstart, rlen, w, h, self.frame_shift_mul, self.score_alpha,
+                                                            mode, to_host=False)
+            res, wfirst = windows(window, hop)
+            return {"res": res, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None, "hop": int(hop)}
+        return self._launch(emb, match)
 
     def monitor_finish(self, p):
         """Second half: -> per recording a structured array (w0, score, song, time_s), one entry per window: its first
         row, and score / song / time exactly as query_finish reports them for that slice (no candidate: -inf, -1, 0)."""
-        if getattr(self, "_copy_stream", None) is None:
-            self._copy_stream = torch.cuda.Stream(p["dev"])
-            self._pin = {}
-        with torch.cuda.stream(self._copy_stream):
-            self._copy_stream.wait_event(p["ev"][-1])
-            res = self.index.results_to_host(p["res"])
-        if self.timer is not None:
-            self.timer.mark_gpu("search", p["ev"][0], p["ev"][1])
-            self.timer.mark_gpu("rerank", p["ev"][1], p["ev"][2])
-            self.timer.resolve()
-        out = self._monitor_rows(res, p["wfirst"], p["hop"], p["mode"])
-        if p.get("fine") is not None:
-            with torch.cuda.stream(self._copy_stream):
-                p["edge_rows"] = self._monitor_rows(self.index.results_to_host(p["fine"][0]), p["fine"][1], 1, p["mode"])
-        return out
+        return self._windows_finish(p, self.frame_shift_mul)
 
-    def _monitor_rows(self, res, wfirst, hop, mode, fsm=None):
-        fsm = self.frame_shift_mul if fsm is None else fsm
-        out = []
-        for r in range(len(wfirst) - 1):
-            rr = res[wfirst[r]:wfirst[r + 1]]
-            rows = np.zeros(rr.shape[0], dtype=self.MONITOR_DTYPE)
-            rows["w0"] = np.arange(rr.shape[0], dtype=np.int64) * hop
-            off, shift = rr["offset"].astype(np.int64), rr["shift"].astype(np.int64)
-            if mode == 1:                            # query_embeddings_cpp: float32 score and fine-frame time, > 0 only
-                sc = rr["score"].astype(np.float32)
-                ok = (rr["song"] >= 0) & (sc > 0)
-                fine = (off * fsm - shift).astype(np.float32).astype(np.float64)
-                rows["score"] = np.where(ok, sc.astype(np.float64), 0.0)
-                rows["song"] = np.where(rr["song"] >= 0, rr["song"], -1)
-                rows["time_s"] = np.where(ok, fine * self.hop_size / fsm, 0.0)
-            else:
-                ok = rr["song"] >= 0
-                rows["score"] = np.where(ok, rr["score"], -np.inf)
-                rows["song"] = np.where(ok, rr["song"], -1)
-                rows["time_s"] = np.where(ok, (off - shift / fsm) * self.hop_size, 0.0)
-            out.append(rows)
+    def _windows_finish(self, p, fsm):
+        out = monitor_rows(self._read_back(p)[0], p["wfirst"], p["hop"], p["mode"], fsm, self.hop_size)
+        if p.get("fine") is not None:                    # (complete behind the same event; the timer has its split already)
+            edge, efirst = p["fine"]
+            edge = self._read_back({"res": edge, "ev": p["ev"][-1:]})[0]
+            p["edge_rows"] = monitor_rows(edge, efirst, 1, p["mode"], fsm, self.hop_size)
         return out
 
     # ---- self-match: the database asked about itself ------------------------------------------------
@@ -800,45 +801,25 @@ class Database:
         emb = self._embeddings_map() if emb is None else emb
         rstart, rlen, lo, hi = self_match_ranges(self.song_pos, song_lo, song_hi)
         r0, r1 = int(self.song_pos[song_lo]), int(self.song_pos[song_hi])
-        dev = self.index.device
-        q = _l.upload_async(np.array(emb[r0:r1], dtype=np.float32).reshape(-1, self.d), dev, np.float32)
-        mode = 1 if cpp_accelerate else 0
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
-        D, I = self.index.search(q, self.top_k if k is None else int(k), exclude=(lo, hi))
-        ev[1].record()
-        res, wfirst = self.index.match_windows(q, I, rstart, rlen, window, hop, 1, self.score_alpha, mode, to_host=False)
-        ev[2].record()
-        return {"res": res, "wfirst": wfirst, "ev": ev, "hop": int(hop), "keep": (q, I), "dev": dev, "mode": mode,
-                "songs": (song_lo, song_hi)}
+        q = _l.upload_async(np.array(emb[r0:r1], dtype=np.float32).reshape(-1, self.d), self.index.device, np.float32)
+
+        def match(I, mode):
+            res, wfirst = self.index.match_windows(q, I, rstart, rlen, window, hop, 1, self.score_alpha, mode, to_host=False)
+            return {"res": res, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
+        return self._launch(q, match, k=k, exclude=(lo, hi))
 
     def self_match_finish(self, p):
         """-> per song of the group a structured array (w0, score, song, time_s), one entry per window, as monitor_finish"""
-        if getattr(self, "_copy_stream", None) is None:
-            self._copy_stream = torch.cuda.Stream(p["dev"])
-            self._pin = {}
-        with torch.cuda.stream(self._copy_stream):
-            self._copy_stream.wait_event(p["ev"][-1])
-            res = self.index.results_to_host(p["res"])
-        if self.timer is not None:
-            self.timer.mark_gpu("search", p["ev"][0], p["ev"][1])
-            self.timer.mark_gpu("rerank", p["ev"][1], p["ev"][2])
-            self.timer.resolve()
-        return self._monitor_rows(res, p["wfirst"], p["hop"], p["mode"], fsm=1)
+        return self._windows_finish(p, 1)
 
     def self_match(self, song_lo, song_hi, window, hop, k=None, emb=None, max_rows=None):
         """Self-match of the songs [song_lo, song_hi): yields (song, rows) in song order, rows as monitor_finish gives them.
         The songs are cut into launch groups of at most max_rows rows (default PFANN_MAX_BATCH, 9728; a longer song is a
         group of its own) and group g + 1 is launched before group g is read back, as the monitor does."""
         max_rows = int(os.environ.get("PFANN_MAX_BATCH", "9728")) if max_rows is None else int(max_rows)
-        in_flight = None
-        for a, b in self_match_groups(self.song_pos, int(song_lo), int(song_hi), max_rows):
-            nxt = self.self_match_launch(a, b, window, hop, k, emb)
-            if in_flight is not None:
-                yield from zip(range(*in_flight["songs"]), self.self_match_finish(in_flight))
-            in_flight = nxt
-        if in_flight is not None:
-            yield from zip(range(*in_flight["songs"]), self.self_match_finish(in_flight))
+        groups = self_match_groups(self.song_pos, int(song_lo), int(song_hi), max_rows)
+        for p in launch_ahead(groups, lambda g: self.self_match_launch(g[0], g[1], window, hop, k, emb)):
+            yield from zip(range(*p["songs"]), self.self_match_finish(p))
 
     # ---- the reference's per-query contract ---------------------------------------------
     def query_embeddings(self, query):

@@ -134,7 +134,7 @@ def main(argv=None):
         return 2
     import torch
     from .builder import embed_file_batches
-    from .database import Database
+    from .database import Database, launch_ahead
     from .engine import Engine
     from .musicdata import MusicDataset
     from .utils import StageTimer, init_logger, read_config
@@ -193,14 +193,8 @@ def main(argv=None):
                     fout.write("%s\t%.3f\t%.3f\t%s\t%.3f\t%.6f\t%.6f\t%d\n" % (name, d0, d1, db.songList[song], s0, mean, best, nw))
                     n_det += 1
 
-        in_flight = None
-        for items in embed_file_batches(engine, dataset, dataset.hop, batch_windows=max_batch, timer=timer):
-            nxt = launch(items)
-            if in_flight is not None:
-                finish(in_flight)
-            in_flight = nxt
-        if in_flight is not None:
-            finish(in_flight)
+        for launched in launch_ahead(embed_file_batches(engine, dataset, dataset.hop, batch_windows=max_batch, timer=timer), launch):
+            finish(launched)
     timer.resolve(wait=True)
     for name, secs in timer.t.items():
         print("%s %.6fs" % (name, secs))
