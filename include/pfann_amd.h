@@ -93,6 +93,12 @@ int pfann_weights_missing(pfann_ctx *ctx);
 int pfann_melspec(pfann_ctx *ctx, const float *segs_dev, int64_t B, int64_t seg_stride,
                   int remove_mean, float *out_dev, void *stream);
 
+/* The launch pfann_melspec (and the front end of pfann_segment_embed*) gives a call of B windows, without launching:
+ * out = {group_out, parts, lds_bytes, radix8}: frames per output group (0: the whole [n_mels][T] tile leaves at once),
+ * workgroups per window, dynamic LDS bytes, 1 if the 8x8x8 register FFT runs (stft_n == 1024) and 0 for the radix-2 FFT
+ * in LDS.  PFANN_MEL_GROUP is honoured as in the launch.  Needs the mel bank (its nonzero count sizes the LDS).  0 / <0. */
+int pfann_melspec_plan(pfann_ctx *ctx, int64_t B, int out[4]);
+
 /* FpNetwork.forward(x, norm): mel_dev[B][n_mels][T] -> emb_dev[B][d]. */
 int pfann_encode(pfann_ctx *ctx, const float *mel_dev, int64_t B, float *emb_dev,
                  int normalize, void *stream);

@@ -7,7 +7,7 @@ Each module restates, in numpy / torch-CPU / plain C, what one stage of the refe
 computes, citing the reference file:line it follows (paths relative to /root/reference):
 
   segmenter.py   datautil/musicdata.py:21-93       (a1)  pinned by golden vectors
-  melspec.py     datautil/melspec.py:19-50          (a2)  PARITY UNPINNED against torchaudio
+  melspec.py     datautil/melspec.py:19-50          (a2)  PARITY UNPINNED against torchaudio (fp32 and float64 forms of every mode)
   encoder.py     model.py:14-153                    (a3-a5) pinned by golden vectors
   search.py      database.py:121 (faiss IndexFlatIP semantics) (a7) definitional
   seqscore.py    database.py:117-166                (a8-a9) pinned by golden vectors

@@ -125,44 +125,88 @@ def melspec(x, params, bank=None):
     return mel.numpy()
 
 
-def melspec_f64(x, params, bank=None):
-    """Independent float64 check of the default mode (explicit frame gather + numpy rfft);
-    used only to size the fp32 error of melspec() and of the HIP kernel."""
+def _f64_modes(params):
+    """(naf, eps, power, log mode, max-normalised) as melspec() reads them from params."""
+    naf = bool(params.get("naf_mode", False))
+    return naf, (0.06 if naf else 1e-8), (1 if naf else 2), params.get("mel_log", "log"), params.get("spec_norm", "l2") == "max"
+
+
+def melspec_f64(x, params, bank=None, remove_mean=False):
+    """Independent float64 statement of everything melspec() covers (explicit frame gather + numpy rfft): naf_mode
+    (constant padding, power 1, eps 0.06, slaney bank), spec_norm == "max" (inf-norm normalisation, then the window's
+    maximum subtracted), mel_log "log" / "log10" / anything else (no log).  remove_mean: x - x.mean() per window first
+    (musicdata.py:88), as the fused front end does.  Used to size the fp32 error of melspec() and of the HIP kernel.
+    The default mode runs the very operations it always ran, in the same order: every caller's values keep their bits
+    (tests/test_oracle.py)."""
     x = np.asarray(x, dtype=np.float64)
+    naf, eps, power, mel_log, norm_max = _f64_modes(params)
     n_fft, hop = params["stft_n"], params["stft_hop"]
-    x = x / np.maximum(np.linalg.norm(x, axis=-1, keepdims=True), 1e-12)
+    if remove_mean:
+        x = x - x.mean(axis=-1, keepdims=True)
+    if norm_max:
+        x = x / np.maximum(np.abs(x).max(axis=-1, keepdims=True), 1e-12)
+    else:
+        x = x / np.maximum(np.linalg.norm(x, axis=-1, keepdims=True), 1e-12)
     L = x.shape[-1]
     n_frames = 1 + L // hop
     n = np.arange(n_fft)
     win = 0.5 - 0.5 * np.cos(2 * np.pi * n / n_fft)
     idx = np.arange(n_frames)[:, None] * hop - n_fft // 2 + n[None, :]
-    idx = np.where(idx < 0, -idx, idx)
-    idx = np.where(idx > L - 1, 2 * (L - 1) - idx, idx)
-    frames = x[..., idx] * win
-    power = np.abs(np.fft.rfft(frames, axis=-1)) ** 2              # [B, frames, bins]
-    fb = (mel_filterbank(params["sample_rate"], n_fft, params["n_mels"], params["f_min"], params["f_max"], False)
+    if naf:                                                         # pad_mode="constant": zeros outside the window
+        inside = (idx >= 0) & (idx <= L - 1)
+        frames = x[..., np.clip(idx, 0, L - 1)] * inside * win
+    else:
+        idx = np.where(idx < 0, -idx, idx)
+        idx = np.where(idx > L - 1, 2 * (L - 1) - idx, idx)
+        frames = x[..., idx] * win
+    power = np.abs(np.fft.rfft(frames, axis=-1)) ** power          # [B, frames, bins]
+    fb = (mel_filterbank(params["sample_rate"], n_fft, params["n_mels"], params["f_min"], params["f_max"], naf)
           if bank is None else torch.as_tensor(np.asarray(bank, np.float32))).double().numpy()
     mel = np.einsum("...tk,km->...mt", power, fb)
-    return np.log(mel + 1e-8)
+    mel = mel + eps
+    if mel_log == "log":
+        mel = np.log(mel)
+    elif mel_log == "log10":
+        mel = np.log10(mel)
+    if norm_max:
+        mel = mel - mel.max(axis=(-2, -1), keepdims=True)
+    return mel
 
 
-def melspec_f64_torch(x, params, bank=None, device=None):
+def melspec_f64_torch(x, params, bank=None, device=None, remove_mean=False):
     """melspec_f64 with torch float64 ops on `device` (gather, window, torch.fft.rfft, matmul, log) -> torch float64
     tensor [B, n_mels, frames] on that device: the front half of the float64 yardstick when it is evaluated on the GPU
     (oracle/encoder.py: encode(device=...)); tools/embedding_error_budget.py checks it against melspec_f64."""
     x = torch.as_tensor(np.asarray(x, dtype=np.float64), device=device)
+    naf, eps, power, mel_log, norm_max = _f64_modes(params)
     n_fft, hop = params["stft_n"], params["stft_hop"]
-    x = x / torch.clamp(torch.linalg.norm(x, dim=-1, keepdim=True), min=1e-12)
+    if remove_mean:
+        x = x - x.mean(dim=-1, keepdim=True)
+    if norm_max:
+        x = x / torch.clamp(x.abs().amax(dim=-1, keepdim=True), min=1e-12)
+    else:
+        x = x / torch.clamp(torch.linalg.norm(x, dim=-1, keepdim=True), min=1e-12)
     L = x.shape[-1]
     n_frames = 1 + L // hop
     n = torch.arange(n_fft, device=device)
     win = 0.5 - 0.5 * torch.cos(2 * math.pi * n.double() / n_fft)
     idx = torch.arange(n_frames, device=device)[:, None] * hop - n_fft // 2 + n[None, :]
-    idx = torch.where(idx < 0, -idx, idx)
-    idx = torch.where(idx > L - 1, 2 * (L - 1) - idx, idx)
-    frames = x[..., idx] * win
-    power = torch.fft.rfft(frames, dim=-1).abs() ** 2
-    fb = (mel_filterbank(params["sample_rate"], n_fft, params["n_mels"], params["f_min"], params["f_max"], False)
+    if naf:
+        inside = (idx >= 0) & (idx <= L - 1)
+        frames = x[..., torch.clamp(idx, 0, L - 1)] * inside * win
+    else:
+        idx = torch.where(idx < 0, -idx, idx)
+        idx = torch.where(idx > L - 1, 2 * (L - 1) - idx, idx)
+        frames = x[..., idx] * win
+    power = torch.fft.rfft(frames, dim=-1).abs() ** power
+    fb = (mel_filterbank(params["sample_rate"], n_fft, params["n_mels"], params["f_min"], params["f_max"], naf)
           if bank is None else torch.as_tensor(np.asarray(bank, np.float32))).double().to(device)
     mel = torch.matmul(power, fb).transpose(-1, -2)
-    return torch.log(mel + 1e-8)
+    mel = mel + eps
+    if mel_log == "log":
+        mel = torch.log(mel)
+    elif mel_log == "log10":
+        mel = torch.log10(mel)
+    if norm_max:
+        mel = mel - torch.amax(mel, dim=(-2, -1), keepdim=True)
+    return mel

@@ -353,6 +353,13 @@ int pfann_melspec(pfann_ctx *c, const float *segs, int64_t B, int64_t seg_stride
     return launch_melspec(c->mel, segs, B, seg_stride, nullptr, remove_mean, out, (hipStream_t)stream);
 }
 
+int pfann_melspec_plan(pfann_ctx *c, int64_t B, int out[4]) {
+    if (!c->mel_ready) { set_error("pfann_melspec_plan: mel filterbank not set"); return -5; }
+    const MelLaunch ml = plan_melspec(c->mel, B);
+    out[0] = ml.group_out; out[1] = ml.parts; out[2] = (int)ml.lds_bytes; out[3] = ml.radix8;
+    return 0;
+}
+
 static int keep_tap(pfann_ctx *c, int idx, const float *act, int64_t B, hipStream_t s) {
     const SubLayer &L = c->sub[idx];
     const int64_t e = (int64_t)L.co * L.Fo * L.To;

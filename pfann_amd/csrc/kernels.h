@@ -16,6 +16,13 @@ struct MelPlan {
     float *fb_val;        // [nnz]
     int max_nnz_row, fb_nnz;
 };
+// What one melspec_kernel launch of B windows is given: frames per output group (0: whole tile), workgroups per window,
+// dynamic LDS bytes, and whether the 8x8x8 register FFT runs (n_fft == 1024) instead of the radix-2 FFT in LDS.
+struct MelLaunch {
+    int group_out, parts, radix8;
+    size_t lds_bytes;
+};
+MelLaunch plan_melspec(const MelPlan &mp, int64_t B);
 int launch_melspec(const MelPlan &mp, const float *segs, int64_t B, int64_t seg_stride,
                    const int64_t *starts, int remove_mean, float *out, hipStream_t s);
 int launch_resample_to_mono(const int16_t *pcm, int n_ch, const float *K, int old_r, int new_r, int width, const int64_t *plan,

@@ -344,6 +344,34 @@ __global__ __launch_bounds__(256) void melspec_kernel(MelArgs a) {
     }
 }
 
+// The ONLY place a launch variant of melspec_kernel is chosen: pure (no HIP call, no allocation); launch_melspec executes
+// it, pfann_melspec_plan reports it (tests/test_gpu_mel_cases.py asserts the path of every case before it compares).
+MelLaunch plan_melspec(const MelPlan &mp, int64_t B) {
+    MelLaunch ml;
+    const int M = mp.n_fft / 2;
+    const int WSZ = 2 * M > 1152 ? 2 * M : 1152;
+    auto lds_for = [&](int gf) {
+        return sizeof(float) * (size_t)(2 * M + 4 * WSZ + 4 * (M + 4) + mp.n_mels * (gf ? gf + 1 : mp.n_frames + 1) + 8 +
+                                        mp.n_mels + 1 + 2 * (size_t)mp.fb_nnz);
+    };
+    // widest output group (16, 8 or 4 frames = 64 / 32 / 16-byte row pieces) that still leaves three workgroups per CU
+    ml.group_out = 0;
+    if (!mp.spec_norm_max) {
+        for (int gf : {16, 8, 4})
+            if (mp.n_frames % gf == 0 && (ml.group_out == 0 ? (3 * lds_for(gf) <= 160 * 1024 || gf == 4) : false)) ml.group_out = gf;
+    }
+    if (getenv("PFANN_MEL_GROUP")) ml.group_out = atoi(getenv("PFANN_MEL_GROUP"));
+    // small batches (one query = 19 segments): a workgroup per output group instead of per segment, so that the launch
+    // covers more than a handful of CUs; same arithmetic in the same order (every workgroup recomputes the segment statistics)
+    ml.parts = 1;
+    if (ml.group_out && B <= 192 && mp.n_frames % ml.group_out == 0 && (mp.n_frames / ml.group_out) * ml.group_out == mp.n_frames &&
+        ml.group_out % 4 == 0 && mp.n_frames % 4 == 0)
+        ml.parts = mp.n_frames / ml.group_out;
+    ml.lds_bytes = lds_for(ml.group_out);
+    ml.radix8 = mp.n_fft == 1024 ? 1 : 0;
+    return ml;
+}
+
 int launch_melspec(const MelPlan &mp, const float *segs, int64_t B, int64_t seg_stride, const int64_t *starts,
                    int remove_mean, float *out, hipStream_t s) {
     if (B <= 0) return 0;
@@ -355,26 +383,10 @@ int launch_melspec(const MelPlan &mp, const float *segs, int64_t B, int64_t seg_
     a.spec_norm_max = mp.spec_norm_max; a.remove_mean = remove_mean; a.log_eps = mp.log_eps;
     a.window = mp.window; a.twiddle = mp.twiddle;
     a.fb_ptr = mp.fb_ptr; a.fb_idx = mp.fb_idx; a.fb_val = mp.fb_val; a.fb_nnz = mp.fb_nnz;
-    const int M = mp.n_fft / 2;
-    const int WSZ = 2 * M > 1152 ? 2 * M : 1152;
-    auto lds_for = [&](int gf) {
-        return sizeof(float) * (size_t)(2 * M + 4 * WSZ + 4 * (M + 4) + mp.n_mels * (gf ? gf + 1 : mp.n_frames + 1) + 8 +
-                                        mp.n_mels + 1 + 2 * (size_t)mp.fb_nnz);
-    };
-    // widest output group (16, 8 or 4 frames = 64 / 32 / 16-byte row pieces) that still leaves three workgroups per CU
-    a.group_out = 0;
-    if (!mp.spec_norm_max) {
-        for (int gf : {16, 8, 4})
-            if (mp.n_frames % gf == 0 && (a.group_out == 0 ? (3 * lds_for(gf) <= 160 * 1024 || gf == 4) : false)) a.group_out = gf;
-    }
-    if (getenv("PFANN_MEL_GROUP")) a.group_out = atoi(getenv("PFANN_MEL_GROUP"));
-    // small batches (one query = 19 segments): a workgroup per output group instead of per segment, so that the launch
-    // covers more than a handful of CUs; same arithmetic in the same order (every workgroup recomputes the segment statistics)
-    a.parts = 1;
-    if (a.group_out && B <= 192 && mp.n_frames % a.group_out == 0 && (mp.n_frames / a.group_out) * a.group_out == mp.n_frames &&
-        a.group_out % 4 == 0 && mp.n_frames % 4 == 0)
-        a.parts = mp.n_frames / a.group_out;
-    const size_t lds = lds_for(a.group_out);
+    const MelLaunch ml = plan_melspec(mp, B);
+    a.group_out = ml.group_out;
+    a.parts = ml.parts;
+    const size_t lds = ml.lds_bytes;
     if (lds > 160 * 1024) { set_error("melspec: LDS need %zu B > 160 KiB", lds); return -1; }
     if (ensure_dyn_lds((const void *)melspec_kernel, 160 * 1024)) return -1;
     ProfScope ps("melspec", s);

@@ -124,6 +124,16 @@ class Engine:
                                             out.data_ptr(), self._stream()), "pfann_melspec")
         return out.reshape(*lead, self.F, self.T)
 
+    def melspec_plan(self, B):
+        """The launch a melspec call of B windows gets (pfann_melspec_plan; nothing runs) ->
+        {"group_out", "parts", "lds_bytes", "radix8", "in_register"}; in_register (segment statistics from registers
+        instead of from global memory) is the kernel's own rule, seg_len <= 8192."""
+        self._need_front_end("melspec_plan")
+        out = (ctypes.c_int * 4)()
+        _l.check(self.lib.pfann_melspec_plan(self.handle, int(B), out), "pfann_melspec_plan")
+        return {"group_out": out[0], "parts": out[1], "lds_bytes": out[2], "radix8": bool(out[3]),
+                "in_register": self.seg_len <= 8192}
+
     def encode(self, mel, norm=True):
         """FpNetwork.forward: [B, F, T] -> [B, d]."""
         x = self._prep(mel)

@@ -44,6 +44,7 @@ SYMBOLS = {
     "pfann_load_weight": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
     "pfann_weights_missing": (c_int, [c_void_p]),
     "pfann_melspec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "pfann_melspec_plan": (c_int, [c_void_p, c_int64, POINTER(c_int)]),
     "pfann_encode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     "pfann_segment_embed": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
     "pfann_segment_embed_at": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),

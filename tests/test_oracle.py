@@ -346,3 +346,74 @@ def test_canonical_topk_window_matches_brute_force(d, n, k, scale):
     # against the float64 top-k: the same rows up to the window's width
     D64, _ = search.flat_ip_topk(q, x, k)
     assert np.abs(D[:, :kk] - D64[:, :kk]).max() <= 2 * search.canon_window(q, x).max()
+
+
+# ------------------------------------------------------------------ a2: the float64 statement of every mode (tests/mel_cases.py)
+def _melspec_f64_before_generalisation(x, params, bank=None):
+    """oracle.melspec.melspec_f64 as it stood while it stated the default mode only, kept here operation for operation:
+    the generalised function must return the same bits in that mode (every earlier caller's numbers depend on them)."""
+    import torch
+    x = np.asarray(x, dtype=np.float64)
+    n_fft, hop = params["stft_n"], params["stft_hop"]
+    x = x / np.maximum(np.linalg.norm(x, axis=-1, keepdims=True), 1e-12)
+    L = x.shape[-1]
+    n_frames = 1 + L // hop
+    n = np.arange(n_fft)
+    win = 0.5 - 0.5 * np.cos(2 * np.pi * n / n_fft)
+    idx = np.arange(n_frames)[:, None] * hop - n_fft // 2 + n[None, :]
+    idx = np.where(idx < 0, -idx, idx)
+    idx = np.where(idx > L - 1, 2 * (L - 1) - idx, idx)
+    frames = x[..., idx] * win
+    power = np.abs(np.fft.rfft(frames, axis=-1)) ** 2
+    fb = (melspec.mel_filterbank(params["sample_rate"], n_fft, params["n_mels"], params["f_min"], params["f_max"], False)
+          if bank is None else torch.as_tensor(np.asarray(bank, np.float32))).double().numpy()
+    mel = np.einsum("...tk,km->...mt", power, fb)
+    return np.log(mel + 1e-8)
+
+
+@pytest.mark.parametrize("name", ["default_parts", "sr16k", "t24", "fft256"])
+def test_melspec_f64_default_mode_keeps_its_bits(name):
+    import mel_cases as mc
+    p = mc.params_for(name)
+    x, _ = mc.rows(name, min(mc.CASES[name][2]), 0)
+    for bank in (None, mc.bank_for(p)):
+        want = _melspec_f64_before_generalisation(x, p, bank)
+        got = melspec.melspec_f64(x, p, bank)
+        assert got.dtype == want.dtype and np.array_equal(got, want)
+        assert np.array_equal(melspec.melspec_f64_torch(x, p, bank).numpy(),
+                              melspec.melspec_f64_torch(x, p, bank, remove_mean=False).numpy())
+    # remove_mean is x - x.mean() in float64 before the normalisation
+    xd = x[:3].astype(np.float64) + 0.05
+    assert np.array_equal(melspec.melspec_f64(xd, p, remove_mean=True),
+                          melspec.melspec_f64(xd - xd.mean(axis=-1, keepdims=True), p))
+
+
+@pytest.mark.parametrize("name,B,remove_mean", __import__("mel_cases").RUNS)
+def test_melspec_f64_states_every_mode_and_case(name, B, remove_mean):
+    """The float64 statement (gather + numpy rfft) against the fp32 torch.stft statement, two independent writings of the
+    same transform, on every case, signal and mode of the table, under the bars the kernel is held to; the float64 torch
+    form agrees with the numpy one to float64 rounding; the loud-bin mask leaves out at most 0.1 % of a noise window's
+    bins, so that the GPU test cannot hide behind it; the impulse windows' set of live frames is the same in both
+    statements and no value sits within 1e-7 of the 1e-6 threshold that defines it."""
+    import mel_cases as mc
+    p = mc.params_for(name)
+    x, kinds = mc.rows(name, B, remove_mean)
+    ref64, ref32 = mc.references(name, B, remove_mean)
+    assert ref64.shape == ref32.shape == (x.shape[0], p["n_mels"], 1 + x.shape[1] // p["stft_hop"])
+    assert np.isfinite(ref64).all() and np.isfinite(ref32).all()
+    m = mc.compare(ref32, name, B, remove_mean)
+    print(name, B, remove_mean, m)
+    assert m["lin_err"] < 2e-6
+    assert m["log_err_loud"] < 2e-3
+    assert m["noise_loud_share"] >= 0.999
+    t64 = melspec.melspec_f64_torch(x[:4], p, mc.bank_for(p), remove_mean=bool(remove_mean)).numpy()
+    assert np.abs(mc.to_linear(t64, p) - mc.to_linear(ref64[:4], p)).max() < 1e-11 * mc.to_linear(ref64[:4], p).max()
+    imp = np.array([k == "impulse" for k in kinds])
+    if imp.any():
+        a64, a32 = mc.active_frames(ref64[imp], p), mc.active_frames(ref32[imp], p)
+        assert np.array_equal(a64, a32)
+        assert a64.any(axis=1).all() and not a64.all(axis=1).any()           # some frames live, some silent, per impulse
+        d = np.abs(ref64[imp] - (mc.floor_level(ref64[imp], p)[:, None, None] + 1e-6))
+        assert d.min() > 1e-7
+    zero = np.array([k == "zero" for k in kinds])
+    assert not mc.active_frames(ref64[zero], p).any()
