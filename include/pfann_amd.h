@@ -396,6 +396,34 @@ int pfann_match_windows(pfann_db *db, const float *q_dev, const int64_t *labels_
                         int window, int hop, int frame_shift_mul, float score_alpha, int mode,
                         const int64_t *wfirst_dev, pfann_match_result *results_dev, void *stream);
 
+/* Monitor mode, ranked: the n best SONGS of every window, 1 <= n <= 64 (anything else: -1 with a message, nothing is
+ * launched).  Windows, wfirst_dev, short and empty recordings and the whole-database requirement on the handle (a shard:
+ * -1, the same message) are exactly those of pfann_match_windows.  top_dev[wfirst[nR]][n]; n_found_dev[wfirst[nR]] may
+ * be NULL.
+ * The list of window w0 of recording r is FIELD FOR FIELD what pfann_match_topn returns for the query (qstart = rstart[r]
+ * + w0, qlen = window, or the length of a shorter recording) with only_owned = 0: candidates are the alignments that the
+ * window's OWN rows nominate; per song the first candidate in candidate order with the largest score wins (strict >);
+ * songs rank by score descending, ties to the song whose best candidate comes first in candidate order; n_cand of an
+ * entry = the distinct candidates of that song in that window; entries past the candidate songs are {song -1, offset 0,
+ * shift 0, n_cand 0, score -inf}; n_found = the distinct candidate songs of the window, not capped at n.
+ * Entry 0 of every window equals pfann_match_windows' result for the same arguments in song, offset, shift and score,
+ * bit for bit, on whichever path served the call (n_cand differs by definition: here the candidates of that song only).
+ * mode 0, frame_shift_mul 1, score_alpha 0, a chunk that fits (pfann_match_windows' condition) and n <= N_FAST = 64 --
+ * every legal n: ONE kernel (csrc/monitor.hip, profiling tag seq_match_windows_topn), fully asynchronous on `stream`, no
+ * scratch memory.  It forms every (alignment, window) total exactly as pfann_match_windows' kernel does, so the score
+ * bits follow the same summation order and a window's entries are a function of the window's rows and the candidate
+ * alone -- not of hop, the chunking, n, the other windows / recordings of the call or fp32 / fp16 storage; the entries
+ * for n = a are the first a entries for n = b > a.
+ * Everything else (the cases pfann_match_windows lists, PFANN_WINDOWS_GENERAL=1 among them) takes the general path: the
+ * windows are expanded on the device and run through pfann_match_topn in bounded launches, after ONE read-back of
+ * wfirst[nR] that synchronises with `stream`. */
+int pfann_match_windows_topn(pfann_db *db, const float *q_dev, const int64_t *labels_dev, int k,
+                             const int64_t *rstart_dev, const int32_t *rlen_dev, int64_t nR,
+                             int window, int hop, int frame_shift_mul, float score_alpha, int mode,
+                             const int64_t *wfirst_dev, int n,
+                             pfann_match_result *top_dev /* [wfirst[nR]][n] */,
+                             int32_t *n_found_dev /* [wfirst[nR]], may be NULL */, void *stream);
+
 /* Songs whose rows all live in this shard: [*song_lo, *song_hi) (either pointer may be NULL); returns their number. */
 int pfann_db_owned_songs(pfann_db *db, int *song_lo, int *song_hi);
 

@@ -1000,6 +1000,64 @@ int pfann_match_windows(pfann_db *db, const float *q, const int64_t *labels, int
     return 0;
 }
 
+int pfann_match_windows_topn(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart, const int32_t *rlen,
+                             int64_t nR, int window, int hop, int frame_shift_mul, float score_alpha, int mode,
+                             const int64_t *wfirst, int n, pfann_match_result *top, int32_t *n_found, void *stream) {
+    PF_HIP(hipSetDevice(db->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || n > 64) { set_error("match_windows_topn: n=%d outside 1..64", n); return -1; }
+    if (top == nullptr) { set_error("match_windows_topn: top_dev is null"); return -1; }
+    if (db->d % 4 != 0) { set_error("match_windows_topn: d %% 4 != 0 (d=%d)", db->d); return -1; }
+    if (window < 1 || hop < 1 || k < 1 || nR < 0) { set_error("match_windows_topn: window=%d hop=%d k=%d nR=%lld", window, hop, k, (long long)nR); return -1; }
+    if (mode != 0 && mode != 1) { set_error("match_windows_topn: unknown mode %d", mode); return -1; }
+    if (db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
+        db->song_pos_h.empty() || db->song_pos_h.back() != db->n) {
+        set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
+        return -1;
+    }
+    if (nR == 0) return 0;
+    // the routing of pfann_match_windows, so that entry 0 and its answer come from the same summation order
+    const int C = match_windows_chunk(k, window, hop);
+    const char *env = getenv("PFANN_WINDOWS_GENERAL");
+    const bool forced = env != nullptr && env[0] != 0 && !(env[0] == '0' && env[1] == 0);
+    const bool fast = !forced && mode == 0 && frame_shift_mul == 1 && score_alpha == 0.0f && C >= 1 && n <= WIN_TOPN_FAST &&
+                      db->n_songs < (1 << 28) - 1 && db->max_song_rows < (1ll << 28) - 2 * WIN_SMAX;
+    if (fast) {
+        WindowsTopnArgs a;
+        a.db = db->emb; a.dbh = db->emb_h; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+        a.q = q; a.labels = labels; a.k = k; a.rstart = rstart; a.rlen = rlen; a.nR = nR;
+        a.window = window; a.hop = hop; a.C = C; a.wfirst = wfirst; a.results = nullptr;
+        a.n = n; a.top = top; a.n_found = n_found;
+        return launch_match_windows_topn(a, st);
+    }
+    // ---- general path: as pfann_match_windows', through pfann_match_topn (ONE synchronisation: the number of windows)
+    int64_t nW = 0;
+    PF_HIP(hipMemcpyAsync(&nW, wfirst + nR, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PF_HIP(hipStreamSynchronize(st));
+    if (nW <= 0) return 0;
+    const size_t o_ql = (size_t)nW * sizeof(int64_t), need = o_ql + (size_t)nW * sizeof(int32_t);
+    if (db->win_scratch_bytes < need) {              // grow, then free: a failed allocation leaves the handle as it was
+        void *grown = nullptr;
+        PF_HIP(hipMalloc(&grown, need));
+        if (db->win_scratch) (void)hipFree(db->win_scratch);       // (the stream was drained above)
+        db->win_scratch = grown;
+        db->win_scratch_bytes = need;
+    }
+    int64_t *qs = reinterpret_cast<int64_t *>(db->win_scratch);
+    int32_t *ql = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(db->win_scratch) + o_ql);
+    if (launch_expand_windows(rstart, rlen, nR, window, hop, wfirst, nW, qs, ql, st)) return -1;
+    int64_t P = 1;
+    while (P < (int64_t)window * k) P <<= 1;
+    const int64_t step = P > 8192 ? std::max<int64_t>(1, (256ll << 20) / (P * 12)) : 65536;
+    for (int64_t j0 = 0; j0 < nW; j0 += step) {
+        const int64_t m = std::min(step, nW - j0);
+        if (pfann_match_topn(db, q, labels, k, qs + j0, ql + j0, m, window, frame_shift_mul, score_alpha, mode, 0, n, top + j0 * n,
+                             n_found != nullptr ? n_found + j0 : nullptr, stream))
+            return -1;
+    }
+    return 0;
+}
+
 int pfann_song_scores_to_seconds(pfann_db *db, float *song_scores_dev, int64_t n_pairs, int frame_shift_mul, double hop_size,
                                  int native_path, void *stream) {
     PF_HIP(hipSetDevice(db->device));

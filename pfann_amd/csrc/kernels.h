@@ -151,6 +151,12 @@ struct WindowsArgs {
 // window starts one workgroup can take (0: the lists do not fit the LDS, the caller expands the windows instead)
 int match_windows_chunk(int k, int window, int hop);
 int launch_match_windows(const WindowsArgs &a, hipStream_t s);
+// pfann_match_windows_topn, fast path: the n best songs of every window (results unused: top[windows][n], n_found or null)
+static constexpr int WIN_TOPN_FAST = 64;    // longest ranked list the windowed kernel keeps (its per-window lists live in LDS)
+struct WindowsTopnArgs : WindowsArgs {
+    int n; pfann_match_result *top; int *n_found;
+};
+int launch_match_windows_topn(const WindowsTopnArgs &a, hipStream_t s);
 int launch_expand_windows(const int64_t *rstart, const int32_t *rlen, int64_t nR, int window, int hop, const int64_t *wfirst,
                           int64_t nW, int64_t *qstart, int32_t *qlen, hipStream_t s);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is per device

@@ -253,6 +253,282 @@ __global__ __launch_bounds__(WIN_NT) void match_windows_kernel(WindowsArgs a) {
     }
 }
 
+// ---- ranked windows (pfann_match_windows_topn): the n best songs of every window --------------------------------------
+// Keys, sort, run heads, row dots and window totals are those of match_windows_kernel above -- same summation order, so a
+// total has the same bits here and there.  The sorted keys put a song's alignments next to each other, in candidate order,
+// so instead of striding over the alignments the 16 waves take contiguous blocks of them, cut at song boundaries: a wave
+// sees whole songs, and lane i (window i) keeps the song's first maximum and its number of candidates in registers.  When
+// the song ends, every lane that had a candidate packs (total, alignment, count) into one 64-bit word that compares as
+// (total descending, alignment ascending) and pushes it into the window's list of n words in LDS: slot j takes the word
+// with atomicMax and hands the smaller of the two on to slot j + 1.  Every word passes slot 0, which therefore ends with
+// the largest; every other word passes slot 1; and so on: whatever the order in which the waves arrive, the list ends as
+// the n largest words in descending order.  Slot values never decrease and never exceed the slot before, so a word that
+// is not above slot n - 1 can be dropped at once, which is what happens to nearly every song once the lists are warm.
+// LDS: the kernel above's lists without its three per-wave [16][64] arrays, plus [64 slots][64 windows] words = 32 KB
+// and 64 counters: 139.6 KB of the 160 KB of a compute unit; no scratch in HBM.
+static constexpr int WTOP_AL_BITS = 13, WTOP_CNT_BITS = 14;          // alignment < MAXC = 2^13, candidates <= MAXC
+
+__device__ __forceinline__ unsigned ordered_bits(float t) {         // a > b  <=>  ordered_bits(a) > ordered_bits(b)
+    const unsigned u = __float_as_uint(t);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ordered_float(unsigned u) {
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+
+// the row dots of one alignment for the chunk rows [r_lo, r_hi) into the wave's line: match_windows_kernel's, to the bit
+template <bool F16>
+__device__ __forceinline__ void alignment_row_dots(const WindowsArgs &a, const float4 *qb, float *dot, int64_t start, int diag,
+                                                   int r_lo, int r_hi, int a_lo, int a_hi, int nchr, int lane) {
+    for (int tr = r_lo + lane; tr < r_hi; tr += 64)
+        if (tr < a_lo || tr >= a_hi) dot[tr] = 0.f;
+    if (nchr <= 32) {
+        const int half = lane >> 5, hl = lane & 31;
+        for (int t0 = a_lo; t0 < a_hi; t0 += 8) {
+            float s[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int tr = t0 + 2 * u + half;
+                s[u] = 0.f;
+                if (tr < a_hi && hl < nchr) {
+                    const float4 w = qb[(int64_t)tr * nchr + hl];
+                    const int64_t ro = (start + diag + tr) * (int64_t)nchr + hl;
+                    float4 v;
+                    if (F16) {
+                        typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+                        const f16x4 h = reinterpret_cast<const f16x4 *>(a.dbh)[ro];
+                        v = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+                    } else {
+                        v = reinterpret_cast<const float4 *>(a.db)[ro];
+                    }
+                    const float p0 = fmaf(v.x, w.x, 0.f), p1 = fmaf(v.y, w.y, 0.f);
+                    const float p2 = fmaf(v.z, w.z, 0.f), p3 = fmaf(v.w, w.w, 0.f);
+                    s[u] = (p0 + p1) + (p2 + p3);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float v = wave_sum_half(s[u]);
+                const int tr = t0 + 2 * u + half;
+                if (hl == 0 && tr < a_hi) dot[tr] = v;
+            }
+        }
+    } else {
+        for (int tr = a_lo; tr < a_hi; ++tr) {
+            const float4 *wq = qb + (int64_t)tr * nchr;
+            const int64_t ro = (start + diag + tr) * (int64_t)nchr;
+            float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+            for (int ch = lane; ch < nchr; ch += 64) {
+                const float4 w = wq[ch];
+                float4 v;
+                if (F16) {
+                    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+                    const f16x4 h = reinterpret_cast<const f16x4 *>(a.dbh)[ro + ch];
+                    v = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+                } else {
+                    v = reinterpret_cast<const float4 *>(a.db)[ro + ch];
+                }
+                p0 = fmaf(v.x, w.x, p0); p1 = fmaf(v.y, w.y, p1); p2 = fmaf(v.z, w.z, p2); p3 = fmaf(v.w, w.w, p3);
+            }
+            const float v = wave_sum((p0 + p1) + (p2 + p3));
+            if (lane == 0) dot[tr] = v;
+        }
+    }
+}
+
+template <bool F16>
+__global__ __launch_bounds__(WIN_NT) void match_windows_topn_kernel(WindowsTopnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sk[];    // [P] keys, then [P + 1] run heads (ushort)
+    __shared__ long long s_cpos[1024];
+    __shared__ float s_dot[WIN_NT / 64][WIN_SMAX];       // per wave: the row dots of the alignment in hand
+    __shared__ unsigned long long s_top[WIN_TOPN_FAST * 64];     // [slot][window]: the ranked words, 0 = empty
+    __shared__ int s_nf[64];                             // per window: songs with a candidate
+    __shared__ int s_wtot[WIN_NT / 64];
+    constexpr int NWV = WIN_NT / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nchr = a.d >> 2;
+
+    const int64_t nW = a.wfirst[a.nR];
+    const int C = min(a.C, max(4, (int)((nW + 255) / 256)));         // chunks and slots as in match_windows_kernel
+    const int64_t n_slots = nW / C + a.nR;
+    int cshift, n_coarse;
+    load_coarse_song_pos<WIN_NT>(a.song_pos, a.n_songs, s_cpos, tid, cshift, n_coarse);
+    for (int e = tid; e < a.n * 64; e += WIN_NT) s_top[e] = 0;
+    if (tid < 64) s_nf[tid] = 0;
+    // (the first barrier of the first slot orders these stores before any use)
+
+    for (int64_t slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
+        int64_t lo = 0, hi = a.nR;                       // first recording whose slots start after `slot`
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (a.wfirst[mid] / C + mid <= slot) lo = mid + 1; else hi = mid;
+        }
+        const int64_t r = lo - 1;
+        const int L = a.rlen[r];
+        const int64_t nw = min((int64_t)windows_of(L, a.window, a.hop), a.wfirst[r + 1] - a.wfirst[r]);
+        const int64_t c0 = (slot - (a.wfirst[r] / C + r)) * C;       // first window of the chunk
+        if (c0 >= nw) continue;                          // (the whole workgroup: a spare slot)
+        const int nwc = (int)min((int64_t)C, nw - c0);
+        const int wl = min(a.window, L);                 // rows of a window: `window`, or all rows of a shorter recording
+        const int S = (nwc - 1) * a.hop + wl;            // rows the chunk spans (<= WIN_SMAX, S * k <= MAXC: the host's C)
+        const int64_t q0 = a.rstart[r] + c0 * a.hop;
+        const int ntot = S * a.k;
+        int P = 1;
+        while (P < ntot) P <<= 1;
+        unsigned short *heads = reinterpret_cast<unsigned short *>(sk + P);
+
+        // ---- keys (song, diagonal, row)
+        for (int i = tid; i < P; i += WIN_NT) {
+            unsigned long long key = SENT;
+            if (i < ntot) {
+                const int tr = i / a.k;
+                const int64_t lab = a.labels[(q0 + tr) * a.k + (i - tr * a.k)];
+                if (lab >= 0) {
+                    const int song = song_of_label(a.song_pos, a.n_songs, s_cpos, cshift, n_coarse, lab);
+                    const int64_t p = song >= 0 ? lab - a.song_pos[song] : 0;
+                    if (song >= 0 && p < (1ll << WIN_DIAG_BITS) - 2 * WIN_SMAX)
+                        key = ((unsigned long long)song << (WIN_DIAG_BITS + WIN_ROW_BITS)) |
+                              ((unsigned long long)(unsigned)((int)p - tr + WIN_SMAX) << WIN_ROW_BITS) | (unsigned long long)tr;
+                }
+            }
+            sk[i] = key;
+        }
+        __syncthreads();
+        bitonic_sort_keys<WIN_NT>(sk, P, tid);
+
+        // ---- run heads: heads[a] = first key of alignment a, heads[n] = end of the last run
+        const int ept = P >= WIN_NT ? P / WIN_NT : 1;
+        int cnt = 0;
+        unsigned hm = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int i = tid * ept + e;
+            if (e < ept && i < P && (i == 0 || (sk[i] >> WIN_ROW_BITS) != (sk[i - 1] >> WIN_ROW_BITS))) { hm |= 1u << e; ++cnt; }
+        }
+        int incl = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += v;
+        }
+        if (lane == 63) s_wtot[wave] = incl;
+        __syncthreads();
+        int base = 0, total = 0;
+        for (int w = 0; w < NWV; ++w) { const int v = s_wtot[w]; if (w < wave) base += v; total += v; }
+        int pos = base + incl - cnt;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (hm & (1u << e)) heads[pos++] = (unsigned short)(tid * ept + e);
+        if (tid == 0) heads[total] = (unsigned short)P;
+        __syncthreads();
+        const int nalign = total - (sk[P - 1] == SENT ? 1 : 0);
+
+        // ---- the wave's block of alignments [blk0, blk1): from the first song boundary at or after wave * nalign / 16 to
+        // the next wave's (a song that spans several nominal cuts leaves the waves between them an empty block)
+        int blk[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            int b = wave + e >= NWV ? nalign : (wave + e) * nalign / NWV;
+            while (b > 0 && b < nalign) {                // (wave-uniform)
+                const int al = b + lane;
+                const bool edge = al >= nalign || (sk[heads[al]] >> (WIN_DIAG_BITS + WIN_ROW_BITS)) !=
+                                                  (sk[heads[al - 1]] >> (WIN_DIAG_BITS + WIN_ROW_BITS));
+                const unsigned long long m = __ballot(edge);
+                if (m) { b += __ffsll(m) - 1; break; }
+                b += 64;
+            }
+            blk[e] = b;
+        }
+
+        // ---- whole songs: lane i = window i keeps the song's first maximum and its candidates, then ranks the song
+        float best = -INFINITY;
+        int besta = -1, ncand = 0, nsongs = 0, cur = -1;
+        const int ws = lane * a.hop;
+        const bool wlive = lane < nwc;
+        float *dot = s_dot[wave];
+        const float4 *qb = reinterpret_cast<const float4 *>(a.q + q0 * a.d);
+        for (int al = blk[0]; al <= blk[1]; ++al) {
+            int song = -1, h0 = 0, h1 = 0;
+            unsigned long long key0 = 0;
+            if (al < blk[1]) {
+                h0 = heads[al]; h1 = heads[al + 1];
+                key0 = sk[h0];
+                song = (int)(key0 >> (WIN_DIAG_BITS + WIN_ROW_BITS));
+            }
+            if (song != cur) {                           // the song in hand is complete (al == blk1: the block's last one)
+                if (ncand > 0) {
+                    ++nsongs;
+                    if (besta >= 0) {                    // (a song whose totals are all NaN or -inf counts but never ranks)
+                        unsigned long long x = ((unsigned long long)ordered_bits(best) << 32) |
+                                               ((unsigned long long)(MAXC - 1 - besta) << WTOP_CNT_BITS) | (unsigned long long)ncand;
+                        unsigned long long *col = s_top + lane;
+                        if (x > __atomic_load_n(col + (a.n - 1) * 64, __ATOMIC_RELAXED))
+                            for (int j = 0; j < a.n && x != 0; ++j) {
+                                const unsigned long long old = atomicMax(col + j * 64, x);
+                                if (old < x) x = old;
+                            }
+                    }
+                }
+                cur = song; best = -INFINITY; besta = -1; ncand = 0;
+            }
+            if (al == blk[1]) break;
+            const int diag = (int)((key0 >> WIN_ROW_BITS) & ((1ull << WIN_DIAG_BITS) - 1)) - WIN_SMAX;
+            const int tmin = (int)(key0 & (WIN_SMAX - 1)), tmax = (int)(sk[h1 - 1] & (WIN_SMAX - 1));
+            const int i_lo = tmin - wl + 1 <= 0 ? 0 : (tmin - wl + a.hop) / a.hop;
+            const int i_hi = min(nwc - 1, tmax / a.hop);
+            if (i_lo > i_hi) continue;                   // nominated only by rows between two windows (hop > window)
+            const int r_lo = i_lo * a.hop, r_hi = i_hi * a.hop + wl;
+            const int64_t start = a.song_pos[song];
+            const int slen = (int)(a.song_pos[song + 1] - start);
+            const int a_lo = max(r_lo, -diag), a_hi = min(r_hi, slen - diag);
+            alignment_row_dots<F16>(a, qb, dot, start, diag, r_lo, r_hi, a_lo, a_hi, nchr, lane);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the line is written: every lane may read it
+            __builtin_amdgcn_wave_barrier();
+            bool mine = false;
+            for (int e = h0; e < h1; ++e) {
+                const int n = (int)(sk[e] & (WIN_SMAX - 1));
+                mine |= n >= ws && n < ws + wl;
+            }
+            if (wlive && mine) {
+                float tot = 0.f;
+                for (int j = 0; j < wl; ++j) tot += dot[ws + j];
+                ++ncand;
+                if (tot > best) { best = tot; besta = al; }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // all read before the next alignment overwrites
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (nsongs) atomicAdd(&s_nf[lane], nsongs);
+        __syncthreads();
+
+        // ---- the lists leave, and are empty again for the next slot (every thread clears what it read)
+        const int64_t wbase = a.wfirst[r] + c0;
+        for (int e = tid; e < a.n * 64; e += WIN_NT) {
+            const int w = e & 63, j = e >> 6;
+            const unsigned long long x = s_top[e];
+            s_top[e] = 0;
+            if (w >= nwc) continue;
+            pfann_match_result res;
+            if (x != 0) {
+                const unsigned long long key = sk[heads[MAXC - 1 - (int)((x >> WTOP_CNT_BITS) & ((1u << WTOP_AL_BITS) - 1))]];
+                res.song = (int)(key >> (WIN_DIAG_BITS + WIN_ROW_BITS));
+                res.offset = (int)((key >> WIN_ROW_BITS) & ((1ull << WIN_DIAG_BITS) - 1)) - WIN_SMAX + w * a.hop;
+                res.shift = 0;
+                res.n_cand = (int)(x & ((1u << WTOP_CNT_BITS) - 1));
+                res.score = (double)ordered_float((unsigned)(x >> 32)) / (double)wl;
+            } else {
+                res.song = -1; res.offset = 0; res.shift = 0; res.n_cand = 0; res.score = -INFINITY;
+            }
+            a.top[(wbase + w) * a.n + j] = res;
+        }
+        if (tid < 64) {
+            if (tid < nwc && a.n_found != nullptr) a.n_found[wbase + tid] = s_nf[tid];
+            s_nf[tid] = 0;
+        }
+        __syncthreads();                                 // the lists are free for the next slot
+    }
+}
+
 // windows -> (qstart, qlen) of the general path: window g of the call is window g - wfirst[r] of its recording r
 __global__ void expand_windows_kernel(const int64_t *__restrict__ rstart, const int32_t *__restrict__ rlen, int64_t nR, int window,
                                       int hop, const int64_t *__restrict__ wfirst, int64_t nW, int64_t *__restrict__ qstart,
@@ -300,6 +576,25 @@ int launch_match_windows(const WindowsArgs &a, hipStream_t s) {
     ProfScope ps("seq_match_windows", s);
     if (a.db != nullptr) PF_LAUNCH(match_windows_kernel<false>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
     else PF_LAUNCH(match_windows_kernel<true>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
+    PF_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_match_windows_topn(const WindowsTopnArgs &a, hipStream_t s) {
+    if (a.nR <= 0) return 0;
+    if (a.C < 1 || a.C > match_windows_chunk(a.k, a.window, a.hop)) { set_error("match_windows_topn: chunk of %d windows does not fit", a.C); return -1; }
+    if (a.n_songs >= (1 << 28) - 1) { set_error("match_windows_topn: too many songs"); return -1; }
+    if (a.n < 1 || a.n > WIN_TOPN_FAST || a.top == nullptr) { set_error("match_windows_topn: top-N arguments (n=%d)", a.n); return -1; }
+    static_assert(MAXC <= (1 << WTOP_AL_BITS) && MAXC < (1 << WTOP_CNT_BITS), "a ranked word holds an alignment index and a count");
+    const int lds_max = MAXC * 8 + (MAXC + 8) * 2;
+    const void *fn = a.db != nullptr ? (const void *)match_windows_topn_kernel<false> : (const void *)match_windows_topn_kernel<true>;
+    if (ensure_dyn_lds(fn, lds_max)) return -1;
+    int P = 1;
+    while (P < ((a.C - 1) * a.hop + a.window) * a.k) P <<= 1;
+    const size_t lds = (size_t)P * 8 + (size_t)(P + 8) * 2;
+    ProfScope ps("seq_match_windows_topn", s);
+    if (a.db != nullptr) PF_LAUNCH(match_windows_topn_kernel<false>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
+    else PF_LAUNCH(match_windows_topn_kernel<true>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
     PF_HIP(hipGetLastError());
     return 0;
 }

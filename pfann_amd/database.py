@@ -362,6 +362,32 @@ class DeviceIndex:
                                                   wf.data_ptr(), res.data_ptr(), self._stream()), "pfann_match_windows")
         return (self.results_to_host(res) if to_host else res), wfirst
 
+    def match_windows_topn(self, q, labels, rstart, rlen, window, hop, n, fsm=1, alpha=0.0, mode=0, to_host=True):
+        """Ranked answers for every window (pfann_match_windows_topn): recordings and windows as in match_windows.
+        -> ((top [nW, n] of RESULT_DTYPE, n_found int32 [nW]), wfirst): row wfirst[r] + i is, field for field, what
+        `match_topn` returns for window i of recording r, and its entry 0 is match_windows' answer; with to_host=False
+        the two device tensors (uint8 [nW, n, 24], int32 [nW]) that topn_to_host turns into the arrays later."""
+        window, hop, n = int(window), int(hop), int(n)
+        if window < 1 or hop < 1:
+            raise ValueError("match_windows_topn: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
+        if not 1 <= n <= 64:
+            raise _l.PfannError("match_windows_topn: n=%d outside 1..64" % n)
+        q, labels, rs_np, rl_np = self._match_args(q, labels, rstart, rlen)
+        nR = int(rl_np.shape[0])
+        assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
+        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
+        nW = int(wfirst[-1])
+        top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
+        if nW:
+            rs, rl = self._upload_ranges(rs_np, rl_np)
+            wf = _l.upload_async(wfirst, self.device, np.int64)
+            _l.check(self.lib.pfann_match_windows_topn(self.handle, q.data_ptr(), labels.data_ptr(), labels.shape[1], rs.data_ptr(),
+                                                       rl.data_ptr(), nR, window, hop, int(fsm), float(alpha), int(mode),
+                                                       wf.data_ptr(), n, top.data_ptr(), n_found.data_ptr(), self._stream()),
+                     "pfann_match_windows_topn")
+        return ((top, n_found) if not to_host else self.topn_to_host(top, n_found)), wfirst
+
 
 def window_counts(rlen, window, hop):
     """windows per recording (include/pfann_amd.h, pfann_match_windows): starts 0, hop, 2*hop, .. while w0 + window <= L;
@@ -471,6 +497,24 @@ def monitor_rows(res, wfirst, hop, mode, fsm, hop_size):
         rows = np.zeros(b - a, dtype=MONITOR_DTYPE)
         rows["w0"] = np.arange(b - a, dtype=np.int64) * hop
         rows["score"], rows["song"], rows["time_s"] = score[a:b], song[a:b], time_s[a:b]
+        out.append(rows)
+    return out
+
+
+MONITOR_TOPN_DTYPE = np.dtype(MONITOR_DTYPE.descr + [("votes", "<i4")])
+
+
+def monitor_topn_rows(top, wfirst, hop, mode, fsm, hop_size):
+    """ranked windowed results [nW, n] -> per recording a MONITOR_TOPN_DTYPE array [windows, n]: column j is monitor_rows of
+    the rank-j entries (padding entries: -inf, -1, 0 like a window without a candidate), votes = the entry's n_cand"""
+    cols = [monitor_rows(top[:, j], wfirst, hop, mode, fsm, hop_size) for j in range(top.shape[1])]
+    out = []
+    for r, (a, b) in enumerate(zip(wfirst[:-1], wfirst[1:])):
+        rows = np.zeros((b - a, top.shape[1]), dtype=MONITOR_TOPN_DTYPE)
+        for j, col in enumerate(cols):
+            for f in MONITOR_DTYPE.names:
+                rows[f][:, j] = col[r][f]
+        rows["votes"] = top["n_cand"][a:b]
         out.append(rows)
     return out
 
@@ -774,6 +818,35 @@ class Database:
             edge = self._read_back({"res": edge, "ev": p["ev"][-1:]})[0]
             p["edge_rows"] = monitor_rows(edge, efirst, 1, p["mode"], fsm, self.hop_size)
         return out
+
+    def monitor_topn_launch(self, emb, rstart, rlen, window, hop, n, edge_window=0):
+        """monitor_launch with ranked answers (pfann_match_windows_topn): the n best songs of every window, and of every
+        short window of the edge pass, from the same single search."""
+        if self.sharded is not None:
+            raise _l.PfannError("monitor mode is not song-sharded: a recording is matched on one GPU against the whole "
+                                "database (run without PFANN_GPUS / ranks)")
+
+        def match(I, mode):
+            windows = lambda w, h: self.index.match_windows_topn(emb, I, rstart, rlen, w, h, n, self.frame_shift_mul,
+                                                                 self.score_alpha, mode, to_host=False)
+            (top, n_found), wfirst = windows(window, hop)
+            return {"res": top, "n_found": n_found, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None,
+                    "hop": int(hop)}
+        return self._launch(emb, match)
+
+    def monitor_topn_finish(self, p):
+        """Second half: -> (per recording a structured array [windows, n] of (w0, score, song, time_s, votes), best song
+        first, each entry formatted as monitor_finish formats a window's answer -- entry 0 IS that answer --, padding
+        entries (-inf, -1, 0, votes 0); per recording n_found int32 [windows], the window's candidate songs, not capped at n).
+        The ranked short windows of the edge pass are left in p["edge_rows"]."""
+        fsm, wfirst = self.frame_shift_mul, p["wfirst"]
+        out = monitor_topn_rows(self._read_back(p)[0], wfirst, p["hop"], p["mode"], fsm, self.hop_size)
+        n_found = p["n_found"].cpu().numpy()
+        if p.get("fine") is not None:
+            (edge, _), efirst = p["fine"]
+            edge = self._read_back({"res": edge, "ev": p["ev"][-1:]})[0]
+            p["edge_rows"] = monitor_topn_rows(edge, efirst, 1, p["mode"], fsm, self.hop_size)
+        return out, [n_found[a:b] for a, b in zip(wfirst[:-1], wfirst[1:])]
 
     # ---- self-match: the database asked about itself ------------------------------------------------
     def _embeddings_map(self):

@@ -1,5 +1,5 @@
 """Monitor mode: go through long recordings and say what played when.
-    python monitor.py <recording list> <database dir> <result file> [--window N] [--hop N] [--min-score X] [--max-gap N] [--min-windows N] [--edge-window N]
+    python monitor.py <recording list> <database dir> <result file> [--window N] [--hop N] [--min-score X] [--max-gap N] [--min-windows N] [--edge-window N] [--top N]
 
 Every recording is embedded once, all its rows are searched once, and the windowed sequence matcher
 (pfann_match_windows, csrc/monitor.hip) answers every window of `--window` segments, `--hop` segments apart, exactly as
@@ -10,6 +10,13 @@ Outputs: `<result file>`, a TSV with one line per detection
     recording  start_s  end_s  song  song_start_s  mean_score  best_score  n_windows
 (an unreadable recording gives the line "recording<TAB>error"), and `<result-stem>_windows.csv` with one row per window
 (recording, w0, start_s, song, score, time): Database.monitor_finish as it stands.
+
+`--top N` (N > 1) ranks the N best songs of every window (pfann_match_windows_topn) and merges every (song, diagonal) track
+by itself (merge_window_tracks), so that two songs that play at once -- a crossfade, music under a jingle -- both come out,
+as detections that overlap in time.  The detections file then has a ninth column, best_rank (the best rank a member window
+gave the song), and the windows file one row per (window, rank) with two more columns, rank (1-based) and votes (the
+alignments of that song the window nominated); its rank-1 rows are the rows of `--top 1`, which is the default and writes
+both files exactly as described above.
 """
 import argparse
 import csv
@@ -58,6 +65,11 @@ def merge_windows(rows, window, hop, hop_size, min_score=DEFAULT_MIN_SCORE, max_
     refine: a window that only partly overlaps the song scores about that part of the full score (the other rows add ~0),
     so the first / last window of a run place the edges at w0 + window * (1 - s / best) and w0 + window * s / best instead
     of at the windows' own edges; the start is also clipped to where the song begins."""
+    return [det for det, _ in _merge_runs(rows, window, hop, hop_size, min_score, max_gap, refine, min_windows, edge_rows, edge_window)]
+
+
+def _merge_runs(rows, window, hop, hop_size, min_score, max_gap, refine, min_windows, edge_rows, edge_window):
+    """merge_windows' work -> [(detection, (first, last))]: the detection and the rows[] range its run spans"""
     del hop                                              # (the spacing is in the w0 column; kept for the call's symmetry)
     tol = 1e-3 * hop_size
     tab = [(int(w0), float(score), int(song), float(time_s)) for w0, score, song, time_s in rows]
@@ -102,7 +114,81 @@ def merge_windows(rows, window, hop, hop_size, min_score=DEFAULT_MIN_SCORE, max_
                 lo, hi = float(on[0]), float(on[-1] + edge_window)
         start_s, end_s = lo * hop_size, hi * hop_size
         start_s = max(start_s, -run["diag"])             # the song cannot have begun before its first second
-        out.append((start_s, end_s, run["song"], run["diag"] + start_s, float(sc.mean()), best, run["last"] - run["first"] + 1))
+        det = (start_s, end_s, run["song"], run["diag"] + start_s, float(sc.mean()), best, run["last"] - run["first"] + 1)
+        out.append((det, (run["first"], run["last"])))
+    return out
+
+
+def _ranked(rows):
+    """ranked rows in either form -> [[(w0, score, song, time_s), ..] per window]: a [windows, n] structured array
+    (Database.monitor_topn_finish), nested sequences, or one answer per window (Database.monitor_finish: one rank)"""
+    if isinstance(rows, np.ndarray) and rows.dtype.names:
+        flat = rows.ndim == 1
+    else:
+        flat = len(rows) > 0 and np.ndim(rows[0][0]) == 0
+    entry = lambda e: (int(e[0]), float(e[1]), int(e[2]), float(e[3]))
+    return [[entry(row)] if flat else [entry(e) for e in row] for row in rows]
+
+
+def merge_window_tracks(ranked_rows, window, hop, hop_size, min_score=DEFAULT_MIN_SCORE, max_gap=0, refine=True, min_windows=1,
+                        edge_rows=None, edge_window=0):
+    """Ranked per-window answers of ONE recording -> detections that may overlap in time.  Pure host code.
+
+    ranked_rows: per window, in ascending w0, its entries best first, each (w0, score, song, time_s[, votes])
+    (Database.monitor_topn_finish; padding entries have song -1).  The other arguments are merge_windows'; edge_rows are the
+    ranked short windows of the edge pass.
+    A track is a (song, diagonal) pair that some entry of some window names with score >= min_score, diagonals equal to
+    within merge_windows' tolerance.  Every track is merged BY ITSELF: merge_windows runs over the sequence that holds the
+    track's entry where a window has one and (w0, -inf, -1, 0) where it has none, with the edge pass restricted to the
+    track in the same way.  -> the union over the tracks, sorted by (start, song):
+    [(rec_start_s, rec_end_s, song, song_start_s, mean_score, best_score, n_windows, best_rank)], best_rank = the best
+    (smallest, 1-based) rank a member window gave the track.
+    With one rank and max_gap = 0 these are merge_windows' detections exactly (a run is then a maximal stretch of
+    consecutive windows on one track, either way), in (start, song) order.  With max_gap > 0 they can differ: take three
+    windows U T U at max_gap = 1.  merge_windows bridges the middle window -- one detection of U over three windows, and
+    T, swallowed by the bridge, is never reported; here track U still bridges its missing window, and track T, merged by
+    itself, is a detection of its own."""
+    tol = 1e-3 * hop_size
+    tab = _ranked(ranked_rows)
+    edge = _ranked(edge_rows) if edge_rows is not None and edge_window > 0 else None
+    tracks = []                                          # (song, diagonal of the first entry that named it)
+    for row in tab:
+        for w0, score, song, time_s in row:
+            diag = time_s - w0 * hop_size
+            if song >= 0 and score >= min_score and not any(s == song and abs(diag - g) <= tol for s, g in tracks):
+                tracks.append((song, diag))
+
+    def restrict(rows, song, diag):
+        """-> (the track's entry or a blank per window, the 1-based rank it held or 0)"""
+        seq, rank = [], []
+        for row in rows:
+            hit = [j for j, (w0, score, s, time_s) in enumerate(row) if s == song and abs(time_s - w0 * hop_size - diag) <= tol]
+            seq.append(row[hit[0]] if hit else (row[0][0], -np.inf, -1, 0.0))
+            rank.append(hit[0] + 1 if hit else 0)
+        return seq, rank
+
+    out = []
+    for song, diag in tracks:
+        seq, rank = restrict(tab, song, diag)
+        eseq = restrict(edge, song, diag)[0] if edge is not None else None
+        for det, (first, last) in _merge_runs(seq, window, hop, hop_size, min_score, max_gap, refine, min_windows, eseq, edge_window):
+            members = [rank[i] for i in range(first, last + 1) if rank[i] and seq[i][1] >= min_score]
+            out.append(det + (min(members),))
+    return sorted(out, key=lambda det: (det[0], det[2]))
+
+
+WINDOWS_HEADER = ["recording", "w0", "start_s", "song", "score", "time"]
+
+
+def ranked_window_csv(name, ranked_rows, seg_step_s, song_names):
+    """rows of `<stem>_windows.csv` under --top N > 1 for one recording: WINDOWS_HEADER + ["rank", "votes"], one row per
+    (window, rank); rank 1 is always written (it is the --top 1 row), padding entries behind it are not"""
+    out = []
+    for row in ranked_rows:
+        for j, (w0, score, song, time_s, votes) in enumerate(row):
+            if j == 0 or song >= 0:
+                out.append([name, int(w0), int(w0) * seg_step_s, song_names[int(song)] if song >= 0 else "", float(score),
+                            float(time_s), j + 1, int(votes)])
     return out
 
 
@@ -119,6 +205,9 @@ def parse_args(argv):
     ap.add_argument("--edge-window", type=int, default=None,
                     help="short windows (segments, hop 1) that place a detection's edges (default window // 3 + 1; 0: off)")
     ap.add_argument("--max-gap", type=int, default=0, help="disagreeing windows one detection may bridge")
+    ap.add_argument("--top", type=int, default=1,
+                    help="songs ranked per window (1..64, default 1); above 1 detections may overlap in time: every (song, "
+                         "diagonal) is merged by itself, and both files get the extra columns described above")
     return ap.parse_args(argv[1:])
 
 
@@ -131,6 +220,9 @@ def main(argv=None):
         return 2
     if args.hop < 1 or (args.window is not None and args.window < 1):
         print("monitor: --window and --hop are positive numbers of segments", file=sys.stderr)
+        return 2
+    if not 1 <= args.top <= 64:
+        print("monitor: --top ranks 1..64 songs per window", file=sys.stderr)
         return 2
     import torch
     from .builder import embed_file_batches
@@ -159,7 +251,7 @@ def main(argv=None):
     with open(args.result, "w", encoding="utf8", newline="\n") as fout, \
             open(stem + "_windows.csv", "w", encoding="utf8", newline="\n") as fwin:
         wcsv = csv.writer(fwin)
-        wcsv.writerow(["recording", "w0", "start_s", "song", "score", "time"])
+        wcsv.writerow(WINDOWS_HEADER + (["rank", "votes"] if args.top > 1 else []))
 
         def launch(items):
             good = [(i, n, e) for i, n, e in items if n]
@@ -168,13 +260,19 @@ def main(argv=None):
                 emb = torch.cat([e for _, _, e in good])
                 rlen = [n for _, n, _ in good]
                 rstart = np.concatenate([[0], np.cumsum(rlen)[:-1]])
-                p = db.monitor_launch(emb, rstart, rlen, window, args.hop, edge_window=edge_window)
+                if args.top > 1:
+                    p = db.monitor_topn_launch(emb, rstart, rlen, window, args.hop, args.top, edge_window=edge_window)
+                else:
+                    p = db.monitor_launch(emb, rstart, rlen, window, args.hop, edge_window=edge_window)
             return items, good, p
 
         def finish(launched):
             nonlocal n_windows, n_det
             items, good, p = launched
-            per = dict(zip([i for i, _, _ in good], db.monitor_finish(p))) if p is not None else {}
+            if p is not None and args.top > 1:
+                per = dict(zip([i for i, _, _ in good], db.monitor_topn_finish(p)[0]))
+            else:
+                per = dict(zip([i for i, _, _ in good], db.monitor_finish(p))) if p is not None else {}
             edge = dict(zip([i for i, _, _ in good], p.get("edge_rows") or [])) if p is not None else {}
             for i, n, _ in items:                         # list order, error rows in their places
                 name = dataset.files[i]
@@ -183,6 +281,15 @@ def main(argv=None):
                     wcsv.writerow([name, "error", "", "", -1e999, 0])
                     continue
                 rows = per[i]
+                if args.top > 1:
+                    wcsv.writerows(ranked_window_csv(name, rows, seg_step_s, db.songList))
+                    n_windows += len(rows)
+                    for d0, d1, song, s0, mean, best, nw, rank in merge_window_tracks(
+                            rows, min(window, n), args.hop, seg_step_s, args.min_score, args.max_gap, min_windows=args.min_windows,
+                            edge_rows=edge.get(i), edge_window=min(edge_window, n)):
+                        fout.write("%s\t%.3f\t%.3f\t%s\t%.3f\t%.6f\t%.6f\t%d\t%d\n" % (name, d0, d1, db.songList[song], s0, mean, best, nw, rank))
+                        n_det += 1
+                    continue
                 for w0, score, song, time_s in rows:
                     wcsv.writerow([name, int(w0), int(w0) * seg_step_s, db.songList[int(song)] if song >= 0 else "",
                                    float(score), float(time_s)])
