@@ -19,6 +19,7 @@
  *   pfann_db_*              database.py:75-109 Database.__init__ (index + song_pos)
  *   pfann_search_topk       database.py:121  index.search(query, top_k)  (exact flat IP)
  *   pfann_match             database.py:117-166 query_embeddings_base (search + rerank)
+ *   pfann_match_windows_dense  database.py:129-163 with every row's label list = the whole database (no counterpart)
  */
 #ifndef PFANN_AMD_H
 #define PFANN_AMD_H
@@ -423,6 +424,38 @@ int pfann_match_windows_topn(pfann_db *db, const float *q_dev, const int64_t *la
                              const int64_t *wfirst_dev, int n,
                              pfann_match_result *top_dev /* [wfirst[nR]][n] */,
                              int32_t *n_found_dev /* [wfirst[nR]], may be NULL */, void *stream);
+
+/* Dense matcher: EVERY alignment of every window, no top-k nomination (csrc/dense.hip; no reference counterpart: the
+ * reference scores only what its per-row search nominates, database.py:133-140).  Mode 0, frame_shift_mul 1, score_alpha 0.
+ * Recordings, windows, wfirst_dev, short recordings (one window of n = rlen rows) and empty ones follow pfann_match_windows'
+ * rule; n_windows = wfirst[nR], passed by the caller; results_dev[n_windows].
+ * The answer of a window of n rows Q[0..n) is what pfann_match returns for that slice when every row's label list is the
+ * whole database (k = ntotal):
+ *   candidates  every (song s with len_s > 0, offset o) with -(n-1) <= o <= len_s - 1;
+ *   total(s, o) sum over t with 0 <= o + t < len_s of dot(Q[t], db[song_pos[s] + o + t]); rows outside the song add +0;
+ *   score       (double)total / (double)n;
+ *   winner      the largest score, strict >, first wins in (song, offset) ascending order (np.unique order of mode 0);
+ *   n_cand      sum over the songs with rows of (len_s + n - 1); shift 0;
+ *   no candidate (empty database, or everything excluded): song -1, offset 0, shift 0, n_cand 0, score -inf.
+ * excl_song_dev[nR] (or NULL): one song id per recording, -1 for none, whose alignments are no candidates and do not
+ * count in n_cand (self-match).
+ * One MFMA kernel (v_mfma_f32_32x32x2_f32) forms 128 x 128 tiles of row dots in LDS, recording rows x database rows,
+ * neighbouring tiles overlapping by window - 1 rows both ways; every diagonal stretch is cut at the song boundaries into
+ * candidate totals; per (window, tile) one 64-bit atomicMax of (order-preserving bits of the total, 0xFFFFFFFF - id) into
+ * the result slot's score field, id(s, o) = song_pos[s] + s * (n-1) + o + (n-1); a last small kernel decodes the slots in
+ * place.  Fully asynchronous on `stream`: no read-back, no host synchronisation, no allocation.
+ * SUMMATION ORDER: a row dot is the MFMA's fmaf chain from +0 over k ascending; a total adds its row dots in ascending
+ * row order from +0 in fp32; no sliding or prefix sums.
+ * BYTE CONTRACT: a window's 24 result bytes are a function of the window's rows, the database and its recording's excluded
+ * song alone -- not of hop, the other windows or recordings of the call, the tiling or the run.
+ * Returns -1 with a message, and launches nothing, when the handle is a shard (pfann_match_windows' message), the storage
+ * is fp16-only (this form scores fp32 rows), window is outside 1..64, hop < 1, d % 4 != 0, or
+ * ntotal + n_songs * (window - 1) >= 2^32 (the packed id). */
+int pfann_match_windows_dense(pfann_db *db, const float *q_dev,
+                              const int64_t *rstart_dev, const int32_t *rlen_dev, int64_t nR,
+                              int window, int hop, const int64_t *wfirst_dev, int64_t n_windows,
+                              const int32_t *excl_song_dev /* [nR] or NULL */,
+                              pfann_match_result *results_dev, void *stream);
 
 /* Songs whose rows all live in this shard: [*song_lo, *song_hi) (either pointer may be NULL); returns their number. */
 int pfann_db_owned_songs(pfann_db *db, int *song_lo, int *song_hi);

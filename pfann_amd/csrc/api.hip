@@ -586,7 +586,7 @@ void pfann_debug_keep(pfann_ctx *c, int on) { c->keep = on != 0; }
 int pfann_prewarm(int device) {
     if (hipSetDevice(device) != hipSuccess) { set_error("pfann_prewarm: no HIP device %d", device); return -1; }
     int rc = launch_noop_api();
-    rc |= prewarm_mel() | prewarm_encoder() | prewarm_encoder_fused() | prewarm_search() | prewarm_search_f16() | prewarm_rerank() | prewarm_monitor();
+    rc |= prewarm_mel() | prewarm_encoder() | prewarm_encoder_fused() | prewarm_search() | prewarm_search_f16() | prewarm_rerank() | prewarm_monitor() | prewarm_dense();
     if (hipDeviceSynchronize() != hipSuccess) rc = -1;
     return rc ? -1 : 0;
 }
@@ -998,6 +998,39 @@ int pfann_match_windows(pfann_db *db, const float *q, const int64_t *labels, int
             return -1;
     }
     return 0;
+}
+
+int pfann_match_windows_dense(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
+                              int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
+                              pfann_match_result *results, void *stream) {
+    PF_HIP(hipSetDevice(db->device));
+    if (db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
+        db->song_pos_h.empty() || db->song_pos_h.back() != db->n) {
+        set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
+        return -1;
+    }
+    if (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr)) {
+        set_error("match_windows_dense: fp16-only storage (the dense matcher scores fp32 rows)");
+        return -1;
+    }
+    if (db->d % 4 != 0) { set_error("match_windows_dense: d %% 4 != 0 (d=%d)", db->d); return -1; }
+    if (window < 1 || window > 64 || hop < 1 || nR < 0 || n_windows < 0) {
+        set_error("match_windows_dense: window=%d (1..64) hop=%d nR=%lld n_windows=%lld", window, hop, (long long)nR, (long long)n_windows);
+        return -1;
+    }
+    if (db->n + (int64_t)db->n_songs * (window - 1) >= (1ll << 32)) {
+        set_error("match_windows_dense: %lld rows and %d songs at window %d do not fit the 32-bit alignment id", (long long)db->n,
+                  db->n_songs, window);
+        return -1;
+    }
+    if (nR == 0 || n_windows == 0) return 0;
+    int64_t with_rows = 0;
+    for (int s = 0; s < db->n_songs; ++s) with_rows += db->song_pos_h[s + 1] > db->song_pos_h[s];
+    DenseArgs a;
+    a.db = db->emb; a.ntotal = db->n; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+    a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
+    a.nW = n_windows; a.excl = excl_song; a.results = results;
+    return launch_match_windows_dense(a, with_rows, (hipStream_t)stream);
 }
 
 int pfann_match_windows_topn(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart, const int32_t *rlen,

@@ -1,0 +1,294 @@
+// Dense matcher: every alignment of every window, no top-k nomination (pfann_match_windows_dense).
+//
+// The dense answer of a window of n rows Q[0..n) is what pfann_match (mode 0, frame_shift_mul 1, score_alpha 0) returns
+// for that slice when every row's label list is the whole database: candidates = every (song s with rows, offset o) with
+// -(n-1) <= o <= len_s - 1, total(s, o) = sum over t with 0 <= o + t < len_s of dot(Q[t], db[song_pos[s] + o + t]),
+// score = (double)total / (double)n, strict-> first-wins argmax in (song, offset) ascending order.
+//
+// One workgroup owns a TILE of DN_T consecutive rows of one recording x DN_T consecutive database rows:
+//   -> S[i][j] = dot(recording row I0 + i, db row J0 + j) on v_mfma_f32_32x32x2_f32, K ascending; the tile stays in LDS
+//   -> the tile owns the window starts i < DN_T - (window-1) and the alignments whose window row 0 meets db row J0 + j,
+//      j < DN_T - (window-1): neighbouring tiles overlap by window-1 rows in both directions (the halo), so the whole
+//      diagonal stretch S[i + t][j + t], t < n, of every owned (window, alignment) lies inside its tile.  db tiles start
+//      at row -(window-1); rows outside the recording or the database are read as zeros and belong to no song
+//   -> a stretch is cut where the song of db row J0 + j + t changes (song ids of the tile's columns: one lookup per column
+//      in song_pos); every piece is the total of ONE candidate, (that song, o = J0 + j - song_pos[song]), and every
+//      candidate of a window is one piece of exactly one stretch.  Songs shorter than the window put several pieces on
+//      one stretch.  Pieces of the recording's excluded song are dropped here
+//   -> per window start the largest packed word of the tile, then one 64-bit atomicMax into the window's result slot
+//      (its 8-byte score field; the call zeroes it first), and a last small kernel decodes the words in place.
+// Packed word: high half = the order-preserving bits of the fp32 total, low half = 0xFFFFFFFF - id with
+//   id(s, o) = song_pos[s] + s * (n-1) + o + (n-1) = (db row of window row 0) + (s + 1) * (n-1),
+// monotone in (song, offset): equal totals resolve to the first candidate in order, whichever tile arrives first.
+// Comparing totals inside one window is comparing scores (one divisor, monotone), as in the ranked monitor kernel.
+//
+// SUMMATION ORDER.  A row dot is the MFMA's fmaf chain from +0 over k = 0, 1, .., d-1 (the K tile is stored in LDS so that
+// step s of a group of eight reads k = 2 s and k = 2 s + 1); a total is tot = +0; tot += S[i + t][j + t] in ascending t,
+// fp32; no sliding or prefix sums.
+// BYTE CONTRACT.  A window's 24 result bytes are a function of the window's rows, the database and its recording's
+// excluded song alone: not of hop, the other windows or recordings of the call, the tiling or the run.
+#include "kernels.h"
+#include "match_common.h"
+#include <algorithm>
+
+namespace pfann {
+
+static constexpr int DN_T = 128;            // tile edge: recording rows and db rows
+static constexpr int DN_NT = 256;           // 4 waves, 2 x 2, each 64 x 64 of the tile
+static constexpr int DN_BK = 32;            // K per staging step
+static constexpr int DN_LDK = DN_BK + 4;    // staging pitch (dwords): conflict-free b128 reads
+static constexpr int DN_LDS = DN_T + 8;     // pitch of S: the two half waves of an accumulator store hit disjoint banks
+static constexpr int DN_GRID = 2048;
+static constexpr int DN_S_BYTES = DN_T * DN_LDS * 4;
+
+typedef float dn_f32x4 __attribute__((ext_vector_type(4)));
+typedef float dn_f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ unsigned dn_ordered_bits(float t) {      // a > b  <=>  bits(a) > bits(b); never 0 for a number
+    const unsigned u = __float_as_uint(t);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float dn_ordered_float(unsigned u) {
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+__device__ __forceinline__ int dn_windows_of(int L, int window, int hop) {
+    return L <= 0 ? 0 : (L < window ? 1 : (L - window) / hop + 1);
+}
+
+__global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a) {
+    // S[DN_T][DN_LDS]; while the product runs its first bytes are the two K tiles As, Bs [DN_T][DN_LDK]
+    extern __shared__ __attribute__((aligned(16))) float s_S[];          // DN_S_BYTES, dynamic: past the static 64 KB
+    __shared__ long long s_cpos[1024];
+    __shared__ int s_song[DN_T];
+    __shared__ unsigned long long s_best[DN_T];
+    static_assert(2 * DN_T * DN_LDK <= DN_T * DN_LDS, "the K tiles fit under S");
+    float *As = s_S, *Bs = s_S + DN_T * DN_LDK;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lhalf = lane >> 5;
+    const int SI = DN_T - (a.window - 1);                // window starts / alignments a tile owns per edge
+    const int64_t n_slots = a.nW * a.hop / SI + a.nR;    // recording r owns the row-tile slots from wfirst[r] * hop / SI + r
+    const int64_t NJ = (a.ntotal + a.window - 1 + SI - 1) / SI;
+    const int64_t n_items = n_slots * NJ;
+    int cshift, n_coarse;
+    load_coarse_song_pos<DN_NT>(a.song_pos, a.n_songs, s_cpos, tid, cshift, n_coarse);
+
+    for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int64_t jt = item / n_slots, slot = item - jt * n_slots;   // neighbouring workgroups share the db tile
+        int64_t lo = 0, hi = a.nR;                       // first recording whose slots start after `slot`
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (a.wfirst[mid] * a.hop / SI + mid <= slot) lo = mid + 1; else hi = mid;
+        }
+        const int64_t r = lo - 1;
+        const int L = a.rlen[r];
+        const int64_t wf = a.wfirst[r];
+        const int nw = (int)min((int64_t)dn_windows_of(L, a.window, a.hop), a.wfirst[r + 1] - wf);
+        const int64_t I0 = (slot - (wf * a.hop / SI + r)) * SI;          // first recording row of the tile
+        if (nw <= 0 || I0 > (int64_t)(nw - 1) * a.hop) continue;         // (the whole workgroup: a spare slot)
+        const int wl = min(a.window, L);                 // rows of a window: `window`, or all rows of a shorter recording
+        const int64_t J0 = jt * SI - (a.window - 1);     // db row of the tile's column 0 (negative in the first tile)
+        const int excl = a.excl != nullptr ? a.excl[r] : -1;
+        const int i0 = (int)I0;
+
+        if (tid < DN_T) {
+            const int64_t g = J0 + tid;
+            s_song[tid] = g >= 0 && g < a.ntotal ? song_of_label(a.song_pos, a.n_songs, s_cpos, cshift, n_coarse, g) : -1;
+            s_best[tid] = 0;
+        }
+
+        // ---- S = Q tile x db tile^T.  Thread tid stages rows (tid >> 2) and (tid >> 2) + 64 of both operands, eight
+        // consecutive k (two float4) at 8 * (tid & 3) of every K step
+        const int srow = tid >> 2, sk8 = (tid & 3) * 8;
+        const float *qp[2], *dp[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int row = srow + 64 * u;
+            qp[u] = i0 + row < L ? a.q + (a.rstart[r] + i0 + row) * (int64_t)a.d : nullptr;
+            const int64_t g = J0 + row;
+            dp[u] = g >= 0 && g < a.ntotal ? a.db + g * (int64_t)a.d : nullptr;
+        }
+        dn_f32x4 ra[2][2], rb[2][2];
+        auto load_tile = [&](int k0) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int k = k0 + sk8 + 4 * h;
+                    const dn_f32x4 z = {0.f, 0.f, 0.f, 0.f};
+                    ra[u][h] = qp[u] != nullptr && k < a.d ? *reinterpret_cast<const dn_f32x4 *>(qp[u] + k) : z;
+                    rb[u][h] = dp[u] != nullptr && k < a.d ? *reinterpret_cast<const dn_f32x4 *>(dp[u] + k) : z;
+                }
+        };
+        // position 4 * half + s of a group of eight holds k = 2 * s + half: the half wave that supplies the MFMA's k = half
+        // reads one b128 and steps s = 0..3 walk k in ascending order
+        auto store_tile = [&]() {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int o = (srow + 64 * u) * DN_LDK + sk8;
+                const dn_f32x4 ae = {ra[u][0][0], ra[u][0][2], ra[u][1][0], ra[u][1][2]};
+                const dn_f32x4 ao = {ra[u][0][1], ra[u][0][3], ra[u][1][1], ra[u][1][3]};
+                const dn_f32x4 be = {rb[u][0][0], rb[u][0][2], rb[u][1][0], rb[u][1][2]};
+                const dn_f32x4 bo = {rb[u][0][1], rb[u][0][3], rb[u][1][1], rb[u][1][3]};
+                *reinterpret_cast<dn_f32x4 *>(&As[o]) = ae;
+                *reinterpret_cast<dn_f32x4 *>(&As[o + 4]) = ao;
+                *reinterpret_cast<dn_f32x4 *>(&Bs[o]) = be;
+                *reinterpret_cast<dn_f32x4 *>(&Bs[o + 4]) = bo;
+            }
+        };
+        dn_f32x16 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        const int nk = (a.d + DN_BK - 1) / DN_BK;
+        load_tile(0);
+#pragma unroll 1
+        for (int kt = 0; kt < nk; ++kt) {
+            store_tile();
+            __syncthreads();
+            if (kt + 1 < nk) load_tile((kt + 1) * DN_BK);
+#pragma unroll
+            for (int kk = 0; kk < DN_BK / 8; ++kk) {
+                dn_f32x4 a4[2], b4[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                    a4[i] = *reinterpret_cast<const dn_f32x4 *>(&As[(wm * 64 + i * 32 + l31) * DN_LDK + kk * 8 + lhalf * 4]);
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    b4[j] = *reinterpret_cast<const dn_f32x4 *>(&Bs[(wn * 64 + j * 32 + l31) * DN_LDK + kk * 8 + lhalf * 4]);
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[i][s], b4[j][s], acc[i][j], 0, 0, 0);
+            }
+            __syncthreads();                             // the K tiles are read: the next step, or S, may overwrite them
+        }
+        // acc[i][j][e]: recording row (e & 3) + 8 * (e >> 2) + 4 * lhalf, db row l31 of the 32 x 32 block
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    s_S[(wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lhalf) * DN_LDS + wn * 64 + j * 32 + l31] = acc[i][j][e];
+        __syncthreads();
+
+        // ---- diagonals: thread = column j, the two halves of the workgroup take the window starts in turn (wave-uniform i)
+        {
+            const int j = tid & (DN_T - 1);
+            const int64_t g = J0 + j;
+            for (int i = tid >> 7; i < SI; i += DN_NT / DN_T) {
+                const int w0 = i0 + i;
+                if (w0 % a.hop != 0 || w0 / a.hop >= nw) continue;       // not a window start of this recording
+                unsigned long long best = 0;
+                if (j < SI) {
+                    int cur = s_song[j];
+                    float tot = 0.f;
+                    for (int t = 0; t < wl; ++t) {
+                        const int sg = s_song[j + t];
+                        if (sg != cur) {
+                            if (cur >= 0 && cur != excl) {
+                                const unsigned id = (unsigned)(g + (int64_t)(cur + 1) * (wl - 1));
+                                const unsigned long long x = ((unsigned long long)dn_ordered_bits(tot) << 32) | (0xFFFFFFFFu - id);
+                                best = x > best ? x : best;
+                            }
+                            cur = sg;
+                            tot = 0.f;
+                        }
+                        tot += s_S[(i + t) * DN_LDS + j + t];
+                    }
+                    if (cur >= 0 && cur != excl) {
+                        const unsigned id = (unsigned)(g + (int64_t)(cur + 1) * (wl - 1));
+                        const unsigned long long x = ((unsigned long long)dn_ordered_bits(tot) << 32) | (0xFFFFFFFFu - id);
+                        best = x > best ? x : best;
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const unsigned long long v = __shfl_xor(best, o, 64);
+                    best = v > best ? v : best;
+                }
+                if (lane == 0 && best != 0) atomicMax(&s_best[i], best);
+            }
+        }
+        __syncthreads();
+        if (tid < SI) {
+            const unsigned long long x = s_best[tid];
+            if (x != 0) {                                // (only window starts of the recording ever get a word)
+                const int64_t w = wf + (i0 + tid) / a.hop;
+                atomicMax(reinterpret_cast<unsigned long long *>(&a.results[w].score), x);
+            }
+        }
+        __syncthreads();                                 // S, the songs and the maxima are free for the next tile
+    }
+}
+
+// packed words -> results, in place.  n_cand = sum over songs with rows (without the excluded one) of len_s + n - 1
+__global__ void dense_decode_kernel(DenseArgs a, int64_t songs_with_rows) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= a.nW) return;
+    int64_t lo = 0, hi = a.nR - 1;                       // first recording whose windows end after w
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.wfirst[mid + 1] <= w) lo = mid + 1; else hi = mid;
+    }
+    const int n = min(a.window, a.rlen[lo]);
+    const int excl = a.excl != nullptr ? a.excl[lo] : -1;
+    int64_t ncand = a.ntotal + songs_with_rows * (n - 1);
+    if (excl >= 0 && excl < a.n_songs) {
+        const int64_t len = a.song_pos[excl + 1] - a.song_pos[excl];
+        if (len > 0) ncand -= len + n - 1;
+    }
+    const unsigned long long x = *reinterpret_cast<const unsigned long long *>(&a.results[w].score);
+    pfann_match_result res;
+    if (x != 0) {
+        const int64_t id = (int64_t)(0xFFFFFFFFu - (unsigned)x);
+        int sl = 0, sh = a.n_songs;                      // largest s with song_pos[s] + s * (n-1) <= id
+        while (sl < sh) {
+            const int mid = (sl + sh) >> 1;
+            if (a.song_pos[mid] + (int64_t)mid * (n - 1) <= id) sl = mid + 1; else sh = mid;
+        }
+        const int s = sl - 1;
+        res.song = s;
+        res.offset = (int)(id - a.song_pos[s] - (int64_t)(s + 1) * (n - 1));
+        res.shift = 0;
+        res.n_cand = (int)ncand;
+        res.score = (double)dn_ordered_float((unsigned)(x >> 32)) / (double)n;
+    } else {
+        res.song = -1; res.offset = 0; res.shift = 0; res.n_cand = 0; res.score = -INFINITY;
+    }
+    a.results[w] = res;
+}
+
+int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipStream_t s) {
+    if (a.nR <= 0 || a.nW <= 0) return 0;
+    // every slot's running best starts empty (word 0: no number has the ordered bits 0)
+    PF_HIP(hipMemsetAsync(a.results, 0, (size_t)a.nW * sizeof(pfann_match_result), s));
+    if (a.ntotal > 0) {
+        const int SI = DN_T - (a.window - 1);
+        const int64_t n_slots = a.nW * a.hop / SI + a.nR;
+        const int64_t NJ = (a.ntotal + a.window - 1 + SI - 1) / SI;
+        const int64_t n_items = n_slots * NJ;
+        const double rows = (double)a.nW * a.hop + (double)a.nR * a.window;
+        if (ensure_dyn_lds((const void *)match_windows_dense_kernel, DN_S_BYTES)) return -1;
+        ProfScope ps("seq_match_windows_dense", s, 2.0 * rows * (double)a.ntotal * a.d);
+        PF_LAUNCH(match_windows_dense_kernel, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
+        PF_HIP(hipGetLastError());
+    }
+    PF_LAUNCH(dense_decode_kernel, dim3((unsigned)cdiv(a.nW, 256)), dim3(256), 0, s, a, songs_with_rows);
+    PF_HIP(hipGetLastError());
+    return 0;
+}
+
+__global__ void noop_dense_kernel() {}
+int prewarm_dense() {
+    hipLaunchKernelGGL(noop_dense_kernel, dim3(1), dim3(1), 0, 0);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace pfann

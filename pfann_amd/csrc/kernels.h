@@ -159,6 +159,21 @@ struct WindowsTopnArgs : WindowsArgs {
 int launch_match_windows_topn(const WindowsTopnArgs &a, hipStream_t s);
 int launch_expand_windows(const int64_t *rstart, const int32_t *rlen, int64_t nR, int window, int hop, const int64_t *wfirst,
                           int64_t nW, int64_t *qstart, int32_t *qlen, hipStream_t s);
+
+// ---- dense.hip: every alignment of every window, no nomination (pfann_match_windows_dense) ----------------
+struct DenseArgs {
+    const float *db; int64_t ntotal; int d;     // fp32 rows of the WHOLE database
+    const int64_t *song_pos; int n_songs;
+    const float *q;
+    const int64_t *rstart; const int32_t *rlen; int64_t nR;
+    int window, hop;        // window 1..64
+    const int64_t *wfirst;  // [nR + 1]
+    int64_t nW;             // wfirst[nR], from the caller
+    const int32_t *excl;    // [nR] song whose alignments are no candidates (-1: none), or null
+    pfann_match_result *results;
+};
+// songs_with_rows: songs of the database with len > 0 (n_cand)
+int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipStream_t s);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is per device
 int ensure_dyn_lds(const void *func, int bytes);
 
@@ -170,5 +185,6 @@ int prewarm_search();
 int prewarm_search_f16();
 int prewarm_rerank();
 int prewarm_monitor();
+int prewarm_dense();
 
 }  // namespace pfann

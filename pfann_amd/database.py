@@ -388,6 +388,35 @@ class DeviceIndex:
                      "pfann_match_windows_topn")
         return ((top, n_found) if not to_host else self.topn_to_host(top, n_found)), wfirst
 
+    def match_windows_dense(self, q, rstart, rlen, window, hop, exclude_song=None, to_host=True):
+        """Dense matcher over every window of nR recordings (pfann_match_windows_dense): no labels -- every alignment of
+        every song is a candidate of every window, so the answer is what `match` gives for the slice when each row's label
+        list is the whole database.  Recordings, windows and the return value (results, wfirst) are match_windows'.
+        exclude_song: one song id per recording (-1: none) whose alignments are no candidates.  window <= 64, fp32 rows."""
+        window, hop = int(window), int(hop)
+        if window < 1 or hop < 1:
+            raise ValueError("match_windows_dense: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
+        q = q.to(self.device, torch.float32).contiguous()
+        rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
+        nR = int(rl_np.shape[0])
+        assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
+        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
+        nW = int(wfirst[-1])
+        res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        ex = None
+        if exclude_song is not None:
+            ex_np = np.ascontiguousarray(exclude_song, dtype=np.int32)
+            if ex_np.shape != (nR,):
+                raise ValueError("match_windows_dense: exclude_song wants one song id per recording (%d), got %r" % (nR, ex_np.shape))
+            ex = _l.upload_async(ex_np, self.device, np.int32)
+        if nW:
+            rs, rl = self._upload_ranges(rs_np, rl_np)
+            wf = _l.upload_async(wfirst, self.device, np.int64)
+            _l.check(self.lib.pfann_match_windows_dense(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
+                                                        wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
+                                                        res.data_ptr(), self._stream()), "pfann_match_windows_dense")
+        return (self.results_to_host(res) if to_host else res), wfirst
+
 
 def window_counts(rlen, window, hop):
     """windows per recording (include/pfann_amd.h, pfann_match_windows): starts 0, hop, 2*hop, .. while w0 + window <= L;
@@ -806,6 +835,38 @@ class Database:
             return {"res": res, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None, "hop": int(hop)}
         return self._launch(emb, match)
 
+    def _dense_check(self, what):
+        """the dense matcher is defined for the default family only: whole database, mode 0, frame_shift_mul 1, score_alpha 0"""
+        if self.sharded is not None:
+            raise _l.PfannError("%s: the dense matcher is not song-sharded: the whole database sits on one handle (run without "
+                                "PFANN_GPUS / ranks)" % what)
+        if self.frame_shift_mul != 1:
+            raise _l.PfannError("%s: the dense matcher needs frame_shift_mul 1 (the database has %r)" % (what, self.frame_shift_mul))
+        if self.score_alpha != 0:
+            raise _l.PfannError("%s: the dense matcher needs score_alpha 0 (the database has %r)" % (what, self.score_alpha))
+        if default_mode() != 0:
+            raise _l.PfannError("%s: the dense matcher is the python path's form; the native mode (cpp_accelerate) is in effect" % what)
+
+    def _launch_dense(self, emb, match):
+        """_launch without a search: the three timed events with an empty search stage, mode 0"""
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        ev[1].record()
+        out = match()
+        ev[2].record()
+        return dict(out, ev=ev, keep=(emb, None), mode=0)
+
+    def monitor_dense_launch(self, emb, rstart, rlen, window, hop, edge_window=0):
+        """monitor_launch on the dense matcher (pfann_match_windows_dense): no search, every alignment of every song is a
+        candidate of every window (and of every short window of the edge pass).  -> what monitor_finish reads."""
+        self._dense_check("monitor_dense_launch")
+
+        def match():
+            windows = lambda w, h: self.index.match_windows_dense(emb, rstart, rlen, w, h, to_host=False)
+            res, wfirst = windows(window, hop)
+            return {"res": res, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None, "hop": int(hop)}
+        return self._launch_dense(emb, match)
+
     def monitor_finish(self, p):
         """Second half: -> per recording a structured array (w0, score, song, time_s), one entry per window: its first
         row, and score / song / time exactly as query_finish reports them for that slice (no candidate: -inf, -1, 0)."""
@@ -859,12 +920,16 @@ class Database:
             self._emb_map = np.memmap(path, dtype=np.float32, mode="r", shape=(n_rows, self.d)) if n_rows else np.zeros((0, self.d), np.float32)
         return self._emb_map
 
-    def self_match_launch(self, song_lo, song_hi, window, hop, k=None, emb=None):
+    def self_match_launch(self, song_lo, song_hi, window, hop, k=None, emb=None, dense=False):
         """One launch group of self-match, asynchronous like monitor_launch: the rows of the songs [song_lo, song_hi) are the
         recordings (song s: rows [song_pos[s], song_pos[s + 1]) of `emb`, by default the memory-mapped `embeddings` file),
         every row is searched with its own song's rows left out (pfann_search_topk_excl: exact, the own rows are never
         nominated), and the windowed matcher answers every window of `window` rows, `hop` apart.  The rows are database
-        rows, one per hop_size, so the matcher runs with frame_shift_mul 1.  Songs without rows give no windows."""
+        rows, one per hop_size, so the matcher runs with frame_shift_mul 1.  Songs without rows give no windows.
+        dense=True: no search; the dense matcher (pfann_match_windows_dense) scores every alignment of every OTHER song --
+        the song's own id is its recording's excluded song -- so the recall does not depend on k."""
+        if dense:
+            self._dense_check("self_match")
         if self.sharded is not None:
             raise _l.PfannError("self-match is not song-sharded: the whole database sits on one handle (run without "
                                 "PFANN_GPUS / ranks)")
@@ -875,6 +940,12 @@ class Database:
         rstart, rlen, lo, hi = self_match_ranges(self.song_pos, song_lo, song_hi)
         r0, r1 = int(self.song_pos[song_lo]), int(self.song_pos[song_hi])
         q = _l.upload_async(np.array(emb[r0:r1], dtype=np.float32).reshape(-1, self.d), self.index.device, np.float32)
+        if dense:
+            def match_dense():
+                res, wfirst = self.index.match_windows_dense(q, rstart, rlen, window, hop,
+                                                             exclude_song=np.arange(song_lo, song_hi, dtype=np.int32), to_host=False)
+                return {"res": res, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
+            return self._launch_dense(q, match_dense)
 
         def match(I, mode):
             res, wfirst = self.index.match_windows(q, I, rstart, rlen, window, hop, 1, self.score_alpha, mode, to_host=False)
@@ -885,13 +956,14 @@ class Database:
         """-> per song of the group a structured array (w0, score, song, time_s), one entry per window, as monitor_finish"""
         return self._windows_finish(p, 1)
 
-    def self_match(self, song_lo, song_hi, window, hop, k=None, emb=None, max_rows=None):
+    def self_match(self, song_lo, song_hi, window, hop, k=None, emb=None, max_rows=None, dense=False):
         """Self-match of the songs [song_lo, song_hi): yields (song, rows) in song order, rows as monitor_finish gives them.
         The songs are cut into launch groups of at most max_rows rows (default PFANN_MAX_BATCH, 9728; a longer song is a
-        group of its own) and group g + 1 is launched before group g is read back, as the monitor does."""
+        group of its own) and group g + 1 is launched before group g is read back, as the monitor does.  dense: see
+        self_match_launch."""
         max_rows = int(os.environ.get("PFANN_MAX_BATCH", "9728")) if max_rows is None else int(max_rows)
         groups = self_match_groups(self.song_pos, int(song_lo), int(song_hi), max_rows)
-        for p in launch_ahead(groups, lambda g: self.self_match_launch(g[0], g[1], window, hop, k, emb)):
+        for p in launch_ahead(groups, lambda g: self.self_match_launch(g[0], g[1], window, hop, k, emb, dense)):
             yield from zip(range(*p["songs"]), self.self_match_finish(p))
 
     # ---- the reference's per-query contract ---------------------------------------------

@@ -1,5 +1,5 @@
 """Monitor mode: go through long recordings and say what played when.
-    python monitor.py <recording list> <database dir> <result file> [--window N] [--hop N] [--min-score X] [--max-gap N] [--min-windows N] [--edge-window N] [--top N]
+    python monitor.py <recording list> <database dir> <result file> [--window N] [--hop N] [--min-score X] [--max-gap N] [--min-windows N] [--edge-window N] [--top N] [--dense]
 
 Every recording is embedded once, all its rows are searched once, and the windowed sequence matcher
 (pfann_match_windows, csrc/monitor.hip) answers every window of `--window` segments, `--hop` segments apart, exactly as
@@ -17,6 +17,10 @@ as detections that overlap in time.  The detections file then has a ninth column
 gave the song), and the windows file one row per (window, rank) with two more columns, rank (1-based) and votes (the
 alignments of that song the window nominated); its rank-1 rows are the rows of `--top 1`, which is the default and writes
 both files exactly as described above.
+
+`--dense` answers every window with the dense matcher (pfann_match_windows_dense, csrc/dense.hip): no search, EVERY alignment
+of every song is a candidate of every window, so the answers do not depend on the indexer's top_k.  Same files, same
+columns; windows of at most 64 segments; not together with `--top N` > 1.
 """
 import argparse
 import csv
@@ -33,6 +37,7 @@ DEFAULT_MIN_SCORE = 0.2
 # a detection needs this many agreeing windows when its recording has that many: a window that half overlaps a song can
 # name a chance alignment at a song-like score, but chance does not repeat on one diagonal
 DEFAULT_MIN_WINDOWS = 2
+DENSE_MAX_WINDOW = 64                                    # pfann_match_windows_dense
 
 
 def default_window(params):
@@ -208,6 +213,9 @@ def parse_args(argv):
     ap.add_argument("--top", type=int, default=1,
                     help="songs ranked per window (1..64, default 1); above 1 detections may overlap in time: every (song, "
                          "diagonal) is merged by itself, and both files get the extra columns described above")
+    ap.add_argument("--dense", action="store_true",
+                    help="score every alignment of every song in every window instead of the ones a top-k search nominates "
+                         "(window <= 64, --top 1)")
     return ap.parse_args(argv[1:])
 
 
@@ -223,6 +231,12 @@ def main(argv=None):
         return 2
     if not 1 <= args.top <= 64:
         print("monitor: --top ranks 1..64 songs per window", file=sys.stderr)
+        return 2
+    if args.dense and args.top > 1:
+        print("monitor: --dense gives one answer per window; it cannot be combined with --top %d" % args.top, file=sys.stderr)
+        return 2
+    if args.dense and args.window is not None and args.window > DENSE_MAX_WINDOW:
+        print("monitor: --dense takes windows of at most %d segments" % DENSE_MAX_WINDOW, file=sys.stderr)
         return 2
     import torch
     from .builder import embed_file_batches
@@ -260,7 +274,9 @@ def main(argv=None):
                 emb = torch.cat([e for _, _, e in good])
                 rlen = [n for _, n, _ in good]
                 rstart = np.concatenate([[0], np.cumsum(rlen)[:-1]])
-                if args.top > 1:
+                if args.dense:
+                    p = db.monitor_dense_launch(emb, rstart, rlen, window, args.hop, edge_window=edge_window)
+                elif args.top > 1:
                     p = db.monitor_topn_launch(emb, rstart, rlen, window, args.hop, args.top, edge_window=edge_window)
                 else:
                     p = db.monitor_launch(emb, rstart, rlen, window, args.hop, edge_window=edge_window)

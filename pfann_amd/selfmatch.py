@@ -1,6 +1,6 @@
 """Self-match: ask a database about itself -- which entries are the same recording under two names, which song contains a
 stretch of another.
-    python selfmatch.py <db dir> <result.tsv> [--window N] [--hop N] [--min-score X] [--min-windows N] [--max-gap N] [--songs A:B] [--topk K]
+    python selfmatch.py <db dir> <result.tsv> [--window N] [--hop N] [--min-score X] [--min-windows N] [--max-gap N] [--songs A:B] [--topk K] [--dense]
 
 Needs no model and no audio: it reads configs.json, songList.txt, landmarkKey and embeddings of a directory written by
 builder.py.  Every song's own fingerprints are the recording: each row is searched with its own song's rows left out
@@ -13,7 +13,9 @@ Outputs: `<result.tsv>`, one line per detection
 ("seconds start_s .. end_s of A are B from offset_in_B_s on"), and `<stem>_windows.csv` with one row per window as the
 monitor writes it (song A in the recording column).  A duplicate pair appears twice, as A in B and as B in A: that is
 intended -- nothing is de-duplicated.  A partial containment appears from the contained side and, where the windows fit
-into the shared stretch, from the container's side.  --songs A:B limits the songs QUERIED, not the songs searched."""
+into the shared stretch, from the container's side.  --songs A:B limits the songs QUERIED, not the songs searched.
+--dense: no search; the dense matcher (pfann_match_windows_dense) scores every alignment of every other song in every window
+(the song's own alignments are excluded), so nothing depends on --topk.  Same files, same columns; windows of at most 64 rows."""
 import argparse
 import csv
 import os
@@ -48,6 +50,8 @@ def parse_args(argv):
     ap.add_argument("--max-gap", type=int, default=0, help="disagreeing windows one detection may bridge")
     ap.add_argument("--songs", default=None, help="A:B: query only the songs A..B-1 of the list (all are searched)")
     ap.add_argument("--topk", type=int, default=None, help="neighbours per row (default: the indexer's top_k)")
+    ap.add_argument("--dense", action="store_true",
+                    help="score every alignment of every other song in every window instead of the nominated ones (window <= 64)")
     return ap.parse_args(argv[1:])
 
 
@@ -74,6 +78,9 @@ def main(argv=None):
     if args.hop < 1 or (args.window is not None and args.window < 1) or (args.topk is not None and not 1 <= args.topk <= 1024):
         print("selfmatch: --window and --hop are positive numbers of rows, --topk is 1..1024", file=sys.stderr)
         return 2
+    if args.dense and args.window is not None and args.window > 64:
+        print("selfmatch: --dense takes windows of at most 64 rows", file=sys.stderr)
+        return 2
     from . import lib as _l
     from .utils import read_config
     params = read_config(os.path.join(args.db, "configs.json"))
@@ -93,7 +100,7 @@ def main(argv=None):
             open(stem + "_windows.csv", "w", encoding="utf8", newline="\n") as fwin:
         wcsv = csv.writer(fwin)
         wcsv.writerow(["recording", "w0", "start_s", "song", "score", "time"])
-        for s, rows in db.self_match(song_lo, song_hi, window, args.hop, args.topk):
+        for s, rows in db.self_match(song_lo, song_hi, window, args.hop, args.topk, dense=args.dense):
             n_song = int(db.song_pos[s + 1] - db.song_pos[s])
             nw, nd = write_song(fout, wcsv, db.songList[s], rows, db.songList, min(window, n_song) if n_song else window, args.hop,
                                 seg_step_s, args.min_score, args.max_gap, args.min_windows)
