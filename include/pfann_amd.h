@@ -213,6 +213,43 @@ int64_t pfann_db_ntotal(pfann_db *db);
 int pfann_db_load(pfann_db *db, const float *emb, int emb_is_device, int64_t n,
                   const int64_t *song_pos_host, int n_songs, int64_t label_base);
 
+/* ---- Database updates: songs are added to and taken out of a loaded handle without a reload.
+ *
+ * State contract.  After a successful pfann_db_append or pfann_db_remove_songs the handle answers EVERY later call --
+ * search, masked search, both sharded halves, pfann_match*, the windowed, ranked and dense matchers, seq_score, the
+ * pfann_search_plan text, pfann_db_ntotal / _bytes / _owned_songs / _row_norm_max -- exactly, bit for bit, as a fresh
+ * handle of the same storage mode and pre-filter setting that was pfann_db_load-ed with the resulting rows and song_pos.
+ * After a failed call (< 0) the handle is unchanged: arguments are validated before anything is touched, and what has to
+ * grow is allocated first and the old buffer freed only on success.  (A device error in the middle of a removal's move is
+ * the one exception: the rows are moved in place.)
+ *
+ * Both are BLOCKING MAINTENANCE calls: they synchronise the device on entry and are complete on return.  They must not
+ * overlap queries on the same handle (no query in flight on any stream, none issued from another thread meanwhile).
+ * Both refuse a shard of a song-sharded database (label_base != 0 or not all songs owned) with -1; nothing is changed.
+ *
+ * pfann_db_reserve: capacity of at least `rows` rows and `songs` songs, never shrinks, contents unchanged.  On a handle
+ *   without rows the request is noted and honoured by the first append (an empty handle holds no matrix, like a fresh one).
+ * pfann_db_capacity: rows the matrices can hold without reallocation.
+ * pfann_db_row_norm_max: the largest row norm the search uses for its fp16 error margin (0 when no fp16 rows were asked for).
+ * pfann_db_append: n_new_songs songs with song_rows_host[i] >= 0 rows each (sum == n_rows, else -1) get the ids n_songs,
+ *   n_songs + 1, ...; their rows emb[n_rows][d] (host or device pointer) go behind the last row.  Within the capacity the
+ *   cost is proportional to the NEW rows: old rows are neither copied nor converted again, the fp16 copy is extended by
+ *   converting the tail.  Beyond it the matrices grow geometrically (at least 1.5x), one device-to-device copy each.
+ *   fp16-only storage: the fp32 rows pass through the bounded staging buffer of pfann_db_load; rows whose norm does not fit
+ *   (>= 6e4) refuse the call with -3.  fp32 storage: a norm >= 1e4 drops the fp16 copy as a fresh load would.
+ * pfann_db_remove_songs: the listed songs (any order, duplicates allowed; an id outside 0..n_songs-1 refuses the call) lose
+ *   their rows, later rows move down in order, every song keeps its id: a removed song becomes a song without rows.  Rows
+ *   before the first removed song are not touched.  The move walks the matrix in ascending chunks -- per chunk one gather
+ *   launch into a bounded staging buffer and one copy down (csrc/dbstore.hip) -- whatever the number of songs; chunk size:
+ *   the 64 MB of the load's staging, or PFANN_DB_MOVE_ROWS=<rows> (read at every call).  fp16 rows are moved, never
+ *   converted again.  The norm maximum is taken again from per-song maxima kept since the load / append. */
+int pfann_db_reserve(pfann_db *db, int64_t rows, int songs);
+int64_t pfann_db_capacity(pfann_db *db);
+float pfann_db_row_norm_max(pfann_db *db);
+int pfann_db_append(pfann_db *db, const float *emb, int emb_is_device, int64_t n_rows,
+                    const int32_t *song_rows_host, int n_new_songs);
+int pfann_db_remove_songs(pfann_db *db, const int32_t *songs_host, int n);
+
 /* Storage precision of the shard's rows; call BEFORE pfann_db_load.  Returns the mode in effect, <0 on error.
  *   PFANN_DB_F32 (default): fp32 rows (+ an fp16 copy for the pre-filter below); every result is exact fp32.
  *   PFANN_DB_F16: ONLY fp16 rows are kept (n*d*2 bytes, half the HBM footprint and half the bytes per scan

@@ -586,7 +586,7 @@ void pfann_debug_keep(pfann_ctx *c, int on) { c->keep = on != 0; }
 int pfann_prewarm(int device) {
     if (hipSetDevice(device) != hipSuccess) { set_error("pfann_prewarm: no HIP device %d", device); return -1; }
     int rc = launch_noop_api();
-    rc |= prewarm_mel() | prewarm_encoder() | prewarm_encoder_fused() | prewarm_search() | prewarm_search_f16() | prewarm_rerank() | prewarm_monitor() | prewarm_dense();
+    rc |= prewarm_mel() | prewarm_encoder() | prewarm_encoder_fused() | prewarm_search() | prewarm_search_f16() | prewarm_rerank() | prewarm_monitor() | prewarm_dense() | prewarm_dbstore();
     if (hipDeviceSynchronize() != hipSuccess) rc = -1;
     return rc ? -1 : 0;
 }
@@ -652,6 +652,14 @@ struct pfann_db {
     void *win_scratch = nullptr;        // pfann_match_windows, general path: (qstart, qlen) of the expanded windows
     size_t win_scratch_bytes = 0;
     int64_t max_song_rows = 0;          // longest song (pfann_db_load)
+    // updates (pfann_db_reserve / _append / _remove_songs).  Invariant: n == 0 <=> emb == emb_h == nullptr and cap == 0 (what
+    // a fresh load of no rows leaves), so a reservation on an empty handle is only noted and honoured by the first append
+    int64_t cap = 0;                    // rows emb / emb_h can hold
+    int song_cap = 0;                   // songs the device song_pos can hold (song_cap + 1 entries)
+    int64_t want_rows = 0;
+    int want_songs = 0;
+    bool norms = false;                 // xnorm_max is kept (fp16 storage, or fp32 storage with the fp16 copy asked for at load)
+    std::vector<float> song_norm;       // [n_songs] largest row norm of every song (0: no rows, or norms not kept)
     // the seq_score seam (the reference's ctypes call, database.py:178-189): device slab, PINNED host image and a
     // private stream, kept between calls; seq_mu serialises concurrent callers on one handle (the reference's seam is
     // re-entrant: cpp/seqscore.cpp keeps no state)
@@ -717,9 +725,23 @@ int pfann_db_load(pfann_db *db, const float *emb, int emb_is_device, int64_t n, 
     if (db->song_pos) { (void)hipFree(db->song_pos); db->song_pos = nullptr; }
     if (db->emb_h) { (void)hipFree(db->emb_h); db->emb_h = nullptr; }
     db->n = 0;
+    db->cap = 0;
     db->label_base = label_base;
     db->n_songs = n_songs;
     db->xnorm_max = 0.f;
+    db->norms = false;
+    db->song_norm.assign((size_t)std::max(n_songs, 0), 0.f);
+    PF_HIP(hipMalloc(&db->song_pos, (size_t)(n_songs + 1) * sizeof(int64_t)));
+    PF_HIP(hipMemcpy(db->song_pos, song_pos, (size_t)(n_songs + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    db->song_cap = n_songs;
+    // per-song maxima of the row norms, for the updates: beside the conversion below, which they do not change
+    float *song_max = nullptr;
+    const bool keep_norms = n > 0 && n_songs > 0 &&
+                            (db->storage == PFANN_DB_F16 || (db->d % 8 == 0 && getenv("PFANN_NO_F16_PREFILTER") == nullptr));
+    if (keep_norms) {
+        PF_HIP(hipMalloc(&song_max, (size_t)n_songs * sizeof(float)));
+        PF_HIP(hipMemset(song_max, 0, (size_t)n_songs * sizeof(float)));
+    }
     if (n > 0 && db->storage == PFANN_DB_F16) {
         // fp16-only storage: the fp32 rows pass through a bounded staging buffer and are never kept
         float *nm = nullptr, *stage = nullptr;
@@ -736,6 +758,7 @@ int pfann_db_load(pfann_db *db, const float *emb, int emb_is_device, int64_t n, 
                 src = stage;
             }
             if (launch_rows_to_half(src, nr, db->d, reinterpret_cast<char *>(db->emb_h) + (size_t)r0 * db->d * 2, nm, 0)) return -1;
+            if (song_max && launch_song_norm_max(src, nr, db->d, label_base + r0, db->song_pos, n_songs, 0, song_max, 0)) return -1;
             PF_HIP(hipDeviceSynchronize());
         }
         PF_HIP(hipMemcpy(&db->xnorm_max, nm, sizeof(float), hipMemcpyDeviceToHost));
@@ -744,6 +767,7 @@ int pfann_db_load(pfann_db *db, const float *emb, int emb_is_device, int64_t n, 
         if (!(db->xnorm_max < 6.0e4f)) {
             (void)hipFree(db->emb_h);
             db->emb_h = nullptr;
+            if (song_max) (void)hipFree(song_max);
             set_error("db_load: rows with norm %g do not fit fp16 storage", (double)db->xnorm_max);
             return -3;
         }
@@ -758,6 +782,7 @@ int pfann_db_load(pfann_db *db, const float *emb, int emb_is_device, int64_t n, 
             PF_HIP(hipMalloc(&nm, sizeof(float)));
             PF_HIP(hipMemset(nm, 0, sizeof(float)));
             if (launch_rows_to_half(db->emb, n, db->d, db->emb_h, nm, 0)) return -1;
+            if (song_max && launch_song_norm_max(db->emb, n, db->d, label_base, db->song_pos, n_songs, 0, song_max, 0)) return -1;
             PF_HIP(hipMemcpy(&db->xnorm_max, nm, sizeof(float), hipMemcpyDeviceToHost));
             (void)hipFree(nm);
             if (!(db->xnorm_max < 1.0e4f)) {       // fp16 range / NaN guard: keep the exact-fp32 scan only
@@ -766,12 +791,16 @@ int pfann_db_load(pfann_db *db, const float *emb, int emb_is_device, int64_t n, 
             }
         }
     }
+    if (song_max) {
+        PF_HIP(hipMemcpy(db->song_norm.data(), song_max, (size_t)n_songs * sizeof(float), hipMemcpyDeviceToHost));
+        (void)hipFree(song_max);
+        db->norms = true;
+    }
     db->n = n;
+    db->cap = n;
     db->song_pos_h.assign(song_pos, song_pos + n_songs + 1);
     db->max_song_rows = 0;
     for (int i = 0; i < n_songs; ++i) db->max_song_rows = std::max(db->max_song_rows, song_pos[i + 1] - song_pos[i]);
-    PF_HIP(hipMalloc(&db->song_pos, (size_t)(n_songs + 1) * sizeof(int64_t)));
-    PF_HIP(hipMemcpy(db->song_pos, song_pos, (size_t)(n_songs + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     // songs whose rows all live in [label_base, label_base + n)
     int lo = 0;
     while (lo < n_songs && song_pos[lo] < label_base) ++lo;
@@ -784,6 +813,270 @@ int pfann_db_load(pfann_db *db, const float *emb, int emb_is_device, int64_t n, 
                   (long long)(label_base + n));
         return -3;
     }
+    return 0;
+}
+
+// ---- updates of a loaded handle (include/pfann_amd.h: "Database updates"; kernels in dbstore.hip) -----------------------
+}  // extern "C"
+
+// maximum of two non-negative floats by bit pattern, as the kernels' atomicMax takes it (a NaN wins)
+static float norm_max2(float a, float b) {
+    unsigned ua, ub;
+    memcpy(&ua, &a, 4);
+    memcpy(&ub, &b, 4);
+    return ua >= ub ? a : b;
+}
+
+static bool db_is_shard(const pfann_db *db) {
+    return db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
+           (!db->song_pos_h.empty() && db->song_pos_h.back() != db->n) || (db->song_pos_h.empty() && db->n != 0);
+}
+
+// device allocations of one update call: whatever was not handed over to the handle is freed when the call returns
+struct DbTemps {
+    std::vector<void *> p;
+    ~DbTemps() { for (void *q : p) if (q) (void)hipFree(q); }
+    template <typename T> hipError_t get(T **out, size_t bytes) {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess) p.push_back(q);
+        *out = reinterpret_cast<T *>(q);
+        return e;
+    }
+    void keep(void *q) { for (void *&x : p) if (x == q) x = nullptr; }
+};
+
+extern "C" {
+
+int64_t pfann_db_capacity(pfann_db *db) { return db->cap; }
+float pfann_db_row_norm_max(pfann_db *db) { return db->xnorm_max; }
+
+int pfann_db_reserve(pfann_db *db, int64_t rows, int songs) {
+    PF_HIP(hipSetDevice(db->device));
+    PF_HIP(hipDeviceSynchronize());
+    if (rows < 0 || songs < 0) { set_error("db_reserve: rows=%lld songs=%d", (long long)rows, songs); return -1; }
+    DbTemps tmp;
+    float *emb = nullptr;
+    char *emb_h = nullptr;
+    int64_t *sp = nullptr;
+    const bool grow_rows = db->n > 0 && rows > db->cap, grow_songs = db->song_pos != nullptr && songs > db->song_cap;
+    // everything new first: a failed allocation leaves the handle as it was
+    if (grow_rows && db->emb) PF_HIP(tmp.get(&emb, (size_t)rows * db->d * sizeof(float)));
+    if (grow_rows && db->emb_h) PF_HIP(tmp.get(&emb_h, (size_t)rows * db->d * 2));
+    if (grow_songs) PF_HIP(tmp.get(&sp, (size_t)(songs + 1) * sizeof(int64_t)));
+    if (emb) PF_HIP(hipMemcpy(emb, db->emb, (size_t)db->n * db->d * sizeof(float), hipMemcpyDeviceToDevice));
+    if (emb_h) PF_HIP(hipMemcpy(emb_h, db->emb_h, (size_t)db->n * db->d * 2, hipMemcpyDeviceToDevice));
+    if (sp) PF_HIP(hipMemcpy(sp, db->song_pos_h.data(), db->song_pos_h.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    PF_HIP(hipDeviceSynchronize());
+    if (emb) { (void)hipFree(db->emb); db->emb = emb; tmp.keep(emb); }
+    if (emb_h) { (void)hipFree(db->emb_h); db->emb_h = emb_h; tmp.keep(emb_h); }
+    if (grow_rows) db->cap = rows;
+    if (sp) { (void)hipFree(db->song_pos); db->song_pos = sp; db->song_cap = songs; tmp.keep(sp); }
+    db->want_rows = std::max(db->want_rows, rows);
+    db->want_songs = std::max(db->want_songs, songs);
+    return 0;
+}
+
+int pfann_db_append(pfann_db *db, const float *emb, int emb_is_device, int64_t n_rows, const int32_t *song_rows_host,
+                    int n_new_songs) {
+    PF_HIP(hipSetDevice(db->device));
+    PF_HIP(hipDeviceSynchronize());
+    // ---- validate before touching anything
+    if (n_rows < 0 || n_new_songs < 0 || (n_rows > 0 && emb == nullptr) || (n_new_songs > 0 && song_rows_host == nullptr)) {
+        set_error("db_append: n_rows=%lld n_new_songs=%d", (long long)n_rows, n_new_songs);
+        return -1;
+    }
+    if (db_is_shard(db)) {
+        set_error("db_append: the handle holds a shard of the database (monitor mode is not song-sharded)");
+        return -1;
+    }
+    int64_t sum = 0;
+    for (int i = 0; i < n_new_songs; ++i) {
+        if (song_rows_host[i] < 0) { set_error("db_append: song %d has %d rows", i, song_rows_host[i]); return -1; }
+        sum += song_rows_host[i];
+    }
+    if (sum != n_rows) { set_error("db_append: the songs have %lld rows, the call brings %lld", (long long)sum, (long long)n_rows); return -1; }
+    if ((int64_t)db->n_songs + n_new_songs > 0x7fffffff - 1) { set_error("db_append: too many songs"); return -1; }
+    if (n_new_songs == 0) return 0;
+    const int d = db->d;
+    const int64_t n0 = db->n, n1 = n0 + n_rows;
+    const int s0 = db->n_songs, s1 = s0 + n_new_songs;
+    const bool f16 = db->storage == PFANN_DB_F16;
+    // the first rows of a handle decide about the fp16 copy and the norms as pfann_db_load would
+    const bool norms = n0 == 0 ? (f16 || (d % 8 == 0 && getenv("PFANN_NO_F16_PREFILTER") == nullptr)) : db->norms;
+    const bool with_h = f16 || (n0 == 0 ? norms : db->emb_h != nullptr);
+    std::vector<int64_t> sp1(db->song_pos_h.empty() ? std::vector<int64_t>(1, 0) : db->song_pos_h);
+    sp1.reserve((size_t)s1 + 1);
+    for (int i = 0; i < n_new_songs; ++i) sp1.push_back(sp1.back() + song_rows_host[i]);
+
+    // ---- everything new is allocated first; the handle's own buffers are written only behind row n, where no query looks
+    DbTemps tmp;
+    float *new_emb = nullptr, *song_max = nullptr, *nm = nullptr, *stage = nullptr;
+    char *new_h = nullptr;
+    int64_t *new_sp = nullptr;
+    int64_t new_cap = db->cap;
+    int new_song_cap = db->song_cap;
+    if (n1 > db->cap) {       // geometric growth: one device-to-device copy per matrix
+        new_cap = std::max(std::max(n1, db->cap + db->cap / 2), db->want_rows);
+        if (!f16) PF_HIP(tmp.get(&new_emb, (size_t)new_cap * d * sizeof(float)));
+        if (with_h) PF_HIP(tmp.get(&new_h, (size_t)new_cap * d * 2));
+    }
+    if (db->song_pos == nullptr || s1 > db->song_cap) {
+        new_song_cap = std::max(std::max(s1, db->song_cap + db->song_cap / 2), db->want_songs);
+        PF_HIP(tmp.get(&new_sp, (size_t)(new_song_cap + 1) * sizeof(int64_t)));
+    }
+    if (norms) {
+        PF_HIP(tmp.get(&song_max, (size_t)n_new_songs * sizeof(float)));
+        PF_HIP(hipMemset(song_max, 0, (size_t)n_new_songs * sizeof(float)));
+    }
+    PF_HIP(tmp.get(&nm, sizeof(float)));
+    PF_HIP(hipMemset(nm, 0, sizeof(float)));
+    const int64_t chunk = std::max<int64_t>(1, (64ll << 20) / ((int64_t)d * 4));
+    if (f16 && !emb_is_device && n_rows > 0) PF_HIP(tmp.get(&stage, (size_t)std::min(chunk, n_rows) * d * sizeof(float)));
+    if (new_emb && n0 > 0) PF_HIP(hipMemcpy(new_emb, db->emb, (size_t)n0 * d * sizeof(float), hipMemcpyDeviceToDevice));
+    if (new_h && n0 > 0 && db->emb_h) PF_HIP(hipMemcpy(new_h, db->emb_h, (size_t)n0 * d * 2, hipMemcpyDeviceToDevice));
+    if (new_sp) PF_HIP(hipMemcpy(new_sp, sp1.data(), sp1.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    else PF_HIP(hipMemcpy(db->song_pos + s0 + 1, sp1.data() + s0 + 1, (size_t)n_new_songs * sizeof(int64_t), hipMemcpyHostToDevice));
+    const int64_t *sp_dev = new_sp ? new_sp : db->song_pos;
+    float *E = new_emb ? new_emb : db->emb;
+    char *H = with_h ? (new_h ? new_h : reinterpret_cast<char *>(db->emb_h)) : nullptr;
+
+    // ---- the new rows: copied (fp32 storage) or passed through the staging buffer (fp16 storage), the tail of the fp16
+    // copy converted, the new songs' norm maxima taken; the old rows are not read
+    if (n_rows > 0 && !f16) {
+        float *tail = E + (size_t)n0 * d;
+        PF_HIP(hipMemcpy(tail, emb, (size_t)n_rows * d * sizeof(float), emb_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        if (H && launch_rows_to_half(tail, n_rows, d, H + (size_t)n0 * d * 2, nm, 0)) return -1;
+        if (norms && launch_song_norm_max(tail, n_rows, d, n0, sp_dev, s1, s0, song_max, 0)) return -1;
+    } else if (n_rows > 0) {
+        for (int64_t r0 = 0; r0 < n_rows; r0 += chunk) {
+            const int64_t nr = std::min(chunk, n_rows - r0);
+            const float *src = emb + r0 * d;
+            if (!emb_is_device) {
+                PF_HIP(hipMemcpy(stage, src, (size_t)nr * d * sizeof(float), hipMemcpyHostToDevice));
+                src = stage;
+            }
+            if (launch_rows_to_half(src, nr, d, H + (size_t)(n0 + r0) * d * 2, nm, 0)) return -1;
+            if (launch_song_norm_max(src, nr, d, n0 + r0, sp_dev, s1, s0, song_max, 0)) return -1;
+            PF_HIP(hipDeviceSynchronize());
+        }
+    }
+    std::vector<float> new_norm((size_t)n_new_songs, 0.f);
+    if (norms) PF_HIP(hipMemcpy(new_norm.data(), song_max, (size_t)n_new_songs * sizeof(float), hipMemcpyDeviceToHost));
+    PF_HIP(hipDeviceSynchronize());
+    float xmax = norms ? db->xnorm_max : 0.f, tail_max = 0.f;
+    for (float v : new_norm) tail_max = norm_max2(tail_max, v);
+    xmax = norm_max2(xmax, tail_max);
+    if (f16 && !(tail_max < 6.0e4f)) {        // pfann_db_load's rule; the handle is as it was
+        set_error("db_append: rows with norm %g do not fit fp16 storage", (double)tail_max);
+        return -3;
+    }
+    const bool drop_h = !f16 && H != nullptr && !(xmax < 1.0e4f);      // fp16 range / NaN guard of pfann_db_load
+
+    // ---- commit: nothing below can fail
+    if (new_emb) { if (db->emb) (void)hipFree(db->emb); db->emb = new_emb; tmp.keep(new_emb); }
+    if (new_h) { if (db->emb_h) (void)hipFree(db->emb_h); db->emb_h = new_h; tmp.keep(new_h); }
+    if (drop_h) { (void)hipFree(db->emb_h); db->emb_h = nullptr; }
+    if (new_sp) { if (db->song_pos) (void)hipFree(db->song_pos); db->song_pos = new_sp; tmp.keep(new_sp); }
+    db->cap = new_cap;
+    db->song_cap = new_song_cap;
+    db->n = n1;
+    db->n_songs = s1;
+    db->song_lo = 0;
+    db->song_hi = s1;
+    db->song_pos_h.swap(sp1);
+    db->song_norm.resize((size_t)s0, 0.f);
+    db->song_norm.insert(db->song_norm.end(), new_norm.begin(), new_norm.end());
+    for (int i = 0; i < n_new_songs; ++i) db->max_song_rows = std::max<int64_t>(db->max_song_rows, song_rows_host[i]);
+    if (n1 > 0) { db->norms = norms; db->xnorm_max = xmax; }
+    db->ws.bound_valid = false;
+    return 0;
+}
+
+int pfann_db_remove_songs(pfann_db *db, const int32_t *songs_host, int n) {
+    PF_HIP(hipSetDevice(db->device));
+    PF_HIP(hipDeviceSynchronize());
+    if (n < 0 || (n > 0 && songs_host == nullptr)) { set_error("db_remove_songs: n=%d", n); return -1; }
+    if (db_is_shard(db)) {
+        set_error("db_remove_songs: the handle holds a shard of the database (monitor mode is not song-sharded)");
+        return -1;
+    }
+    std::vector<char> gone((size_t)db->n_songs, 0);
+    for (int i = 0; i < n; ++i) {
+        if (songs_host[i] < 0 || songs_host[i] >= db->n_songs) {
+            set_error("db_remove_songs: song %d outside 0..%d", songs_host[i], db->n_songs - 1);
+            return -1;
+        }
+        gone[songs_host[i]] = 1;
+    }
+    if (n == 0 || db->n == 0) return 0;
+    const int d = db->d;
+    std::vector<DbRun> runs;
+    int64_t first = 0;
+    const int64_t n1 = db_kept_runs(db->song_pos_h, gone, runs, &first);
+    if (n1 == db->n) return 0;                // only songs without rows
+    std::vector<int64_t> sp1(db->song_pos_h.size(), 0);
+    float xmax = 0.f;
+    int64_t longest = 0;
+    for (int s = 0; s < db->n_songs; ++s) {
+        const int64_t len = gone[s] ? 0 : db->song_pos_h[s + 1] - db->song_pos_h[s];
+        sp1[s + 1] = sp1[s] + len;
+        longest = std::max(longest, len);
+        if (!gone[s] && len > 0) xmax = norm_max2(xmax, db->song_norm[s]);
+    }
+    if (!db->norms) xmax = 0.f;
+    // a fresh load of the rows left keeps an fp16 copy when their norms allow it: the song that stood in its way may be gone
+    const bool rebuild_h = db->storage == PFANN_DB_F32 && db->norms && db->emb_h == nullptr && n1 > 0 && xmax < 1.0e4f;
+    DbTemps tmp;
+    char *stage = nullptr, *new_h = nullptr;
+    DbRun *runs_dev = nullptr;
+    float *nm = nullptr;
+    // rows per chunk of the move: the 64 MB staging of the fp16 load, or PFANN_DB_MOVE_ROWS (read at every call)
+    int64_t chunk = std::max<int64_t>(1, (64ll << 20) / ((int64_t)d * 4));
+    if (const char *env = getenv("PFANN_DB_MOVE_ROWS")) {
+        if (atoll(env) > 0) chunk = atoll(env);
+    }
+    chunk = std::min<int64_t>(chunk, (1ll << 30) / d);        // (the gather kernel indexes a chunk's vectors with 31 bits)
+    const int64_t row_bytes = db->emb ? (int64_t)d * 4 : (int64_t)d * 2;
+    if (n1 > first) {
+        PF_HIP(tmp.get(&stage, (size_t)(std::min(chunk, n1 - first) * row_bytes)));
+        PF_HIP(tmp.get(&runs_dev, runs.size() * sizeof(DbRun)));
+    }
+    if (rebuild_h) {
+        PF_HIP(tmp.get(&new_h, (size_t)db->cap * d * 2));
+        PF_HIP(tmp.get(&nm, sizeof(float)));
+        PF_HIP(hipMemset(nm, 0, sizeof(float)));
+    }
+    // ---- the move, every matrix alike: ascending chunks of destination rows, gather -> staging -> down, in stream order
+    if (n1 > first) {
+        PF_HIP(hipMemcpy(runs_dev, runs.data(), runs.size() * sizeof(DbRun), hipMemcpyHostToDevice));
+        struct { char *base; int64_t rb; } mats[2] = {{reinterpret_cast<char *>(db->emb), (int64_t)d * 4},
+                                                     {reinterpret_cast<char *>(db->emb_h), (int64_t)d * 2}};
+        for (auto &m : mats) {
+            if (m.base == nullptr) continue;
+            for (int64_t r0 = first; r0 < n1; r0 += chunk) {
+                const int64_t nr = std::min(chunk, n1 - r0);
+                if (launch_gather_rows(m.base, stage, runs_dev, (int)runs.size(), r0, nr, m.rb, 0)) return -1;
+                PF_HIP(hipMemcpyAsync(m.base + (size_t)r0 * m.rb, stage, (size_t)nr * m.rb, hipMemcpyDeviceToDevice, 0));
+            }
+        }
+    }
+    if (rebuild_h && launch_rows_to_half(db->emb, n1, d, new_h, nm, 0)) return -1;
+    PF_HIP(hipDeviceSynchronize());
+    PF_HIP(hipMemcpy(db->song_pos, sp1.data(), sp1.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (new_h) { db->emb_h = new_h; tmp.keep(new_h); }
+    if (n1 == 0) {                            // what a fresh load of no rows leaves
+        if (db->emb) { (void)hipFree(db->emb); db->emb = nullptr; }
+        if (db->emb_h) { (void)hipFree(db->emb_h); db->emb_h = nullptr; }
+        db->cap = 0;
+        db->norms = false;
+    }
+    db->n = n1;
+    db->song_pos_h.swap(sp1);
+    db->max_song_rows = longest;
+    db->xnorm_max = xmax;
+    for (int s = 0; s < db->n_songs; ++s) if (gone[s]) db->song_norm[s] = 0.f;
+    db->ws.bound_valid = false;
     return 0;
 }
 

@@ -177,6 +177,17 @@ int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipS
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is per device
 int ensure_dyn_lds(const void *func, int bytes);
 
+// ---- dbstore.hip: what an update of a loaded handle needs (pfann_db_append / pfann_db_remove_songs) ----------------
+struct DbRun { int64_t src, dst, len; };    // kept rows [src, src + len) go to [dst, dst + len), dst <= src
+// atomic maximum of the row norms (the per-row arithmetic of rows_to_half_kernel) into song_max[song - song_base]; row r of x
+// is global row row0_global + r; song_max holds non-negative floats (zeroed by the caller)
+int launch_song_norm_max(const float *x, int64_t n, int d, int64_t row0_global, const int64_t *song_pos, int n_songs,
+                         int song_base, float *song_max, hipStream_t s);
+// destination rows [dst0, dst0 + n_rows) of the move, gathered into stage; runs_dev[0].dst <= dst0, ascending
+int launch_gather_rows(const void *src, void *stage, const DbRun *runs_dev, int n_runs, int64_t dst0, int64_t n_rows,
+                       int64_t row_bytes, hipStream_t s);
+int64_t db_kept_runs(const std::vector<int64_t> &song_pos, const std::vector<char> &gone, std::vector<DbRun> &runs, int64_t *first);
+
 // one per translation unit with device code (pfann_prewarm)
 int prewarm_mel();
 int prewarm_encoder();
@@ -186,5 +197,6 @@ int prewarm_search_f16();
 int prewarm_rerank();
 int prewarm_monitor();
 int prewarm_dense();
+int prewarm_dbstore();
 
 }  // namespace pfann

@@ -100,6 +100,47 @@ class DeviceIndex:
             _l.check(self.lib.pfann_db_set_owned_songs(self.handle, int(song_range[0]), int(song_range[1])),
                      "pfann_db_set_owned_songs")
 
+    # ---- updates (include/pfann_amd.h: "Database updates"): blocking maintenance calls, never beside a query on this index
+    def reserve(self, rows, songs=0):
+        """room for `rows` rows and `songs` songs without reallocation (never shrinks) -> capacity in rows"""
+        _l.check(self.lib.pfann_db_reserve(self.handle, int(rows), int(songs)), "pfann_db_reserve")
+        return self.capacity()
+
+    def capacity(self):
+        return int(self.lib.pfann_db_capacity(self.handle))
+
+    def row_norm_max(self):
+        return float(self.lib.pfann_db_row_norm_max(self.handle))
+
+    def append(self, emb, rows_per_song):
+        """New songs behind the last one: emb float32 [sum(rows_per_song), d] (numpy, or a torch cuda tensor), one entry of
+        rows_per_song per song (0 allowed) -> the id of the first new song.  A refused call leaves the index as it was."""
+        rps = np.ascontiguousarray(rows_per_song, dtype=np.int32).reshape(-1)
+        if isinstance(emb, torch.Tensor) and emb.is_cuda:
+            e = emb.to(torch.float32).contiguous().reshape(-1, self.d)
+            ptr, is_dev, n = e.data_ptr(), 1, e.shape[0]
+        else:
+            e = np.ascontiguousarray(emb.cpu().numpy() if isinstance(emb, torch.Tensor) else emb, np.float32).reshape(-1, self.d)
+            ptr, is_dev, n = e.ctypes.data, 0, e.shape[0]
+        _l.check(self.lib.pfann_db_append(self.handle, ptr, is_dev, n, rps.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                          rps.shape[0]), "pfann_db_append")
+        first = self.n_songs
+        base = getattr(self, "song_pos", np.zeros(1, np.int64))
+        self.song_pos = np.concatenate([base, base[-1] + np.cumsum(rps, dtype=np.int64)])
+        self.n_songs += rps.shape[0]
+        self.ntotal += n
+        return first
+
+    def remove_songs(self, songs):
+        """The songs (ids, any order) lose their rows and keep their ids; later rows move down."""
+        ids = np.ascontiguousarray(songs, dtype=np.int32).reshape(-1)
+        _l.check(self.lib.pfann_db_remove_songs(self.handle, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ids.shape[0]),
+                 "pfann_db_remove_songs")
+        lens = np.diff(self.song_pos)
+        lens[ids] = 0
+        self.song_pos = np.pad(np.cumsum(lens, dtype=np.int64), (1, 0))
+        self.ntotal = int(self.song_pos[-1])
+
     def set_prefilter(self, on=True):
         """fp16 pre-filter of the batched scan (exact result either way) -> True if in use."""
         self._prefilter = bool(on)
@@ -598,6 +639,9 @@ class Database:
         self._copy_stream = None   # the side stream results are read back on (_read_back makes it at the first read)
         self._pin = {}             # pinned landing buffers of _pinned, by dtype
 
+        if os.path.exists(os.path.join(dir_for_db, "dbupdate.journal")):
+            raise _l.PfannError("%s holds the journal of an interrupted update: run `python dbupdate.py check %s --repair` "
+                                "first (pfann_amd/dbfiles.py)" % (dir_for_db, dir_for_db))
         self.songList = read_file_list(os.path.join(dir_for_db, "songList.txt"))
         key = np.fromfile(os.path.join(dir_for_db, "landmarkKey"), dtype=np.int32)
         assert len(self.songList) == key.shape[0]
@@ -908,6 +952,62 @@ class Database:
             edge = self._read_back({"res": edge, "ev": p["ev"][-1:]})[0]
             p["edge_rows"] = monitor_topn_rows(edge, efirst, 1, p["mode"], fsm, self.hop_size)
         return out, [n_found[a:b] for a, b in zip(wfirst[:-1], wfirst[1:])]
+
+    # ---- updates: songs added and removed without a rebuild (include/pfann_amd.h: "Database updates") ---------------
+    def _update_check(self, what):
+        if self.sharded is not None or self.ranks is not None:
+            raise _l.PfannError("%s: the handle holds a shard of the database (monitor mode is not song-sharded)" % what)
+
+    def _updated(self):
+        self.song_pos = np.array(self.index.song_pos, dtype=np.int64)
+        self.song_range = (0, len(self.songList))
+        self._emb_map = None                         # (self-match reads it: the file behind it has other rows now)
+
+    def add_songs(self, names, emb, rows_per_song, persist=True):
+        """New songs behind the last one -> the id of the first.  names: their songList.txt lines; emb float32
+        [sum(rows_per_song), d] (numpy or torch); rows_per_song may hold zeros (the builder's unreadable file).  The handle is
+        updated first -- it is the one that can refuse the rows -- then, with persist, the files through dbfiles.add_songs.
+        A blocking maintenance call: no query of this Database may be in flight."""
+        self._update_check("add_songs")
+        names = list(names)
+        rps = np.ascontiguousarray(rows_per_song, dtype=np.int32).reshape(-1)
+        if len(names) != rps.shape[0]:
+            raise ValueError("add_songs: %d names for %d songs" % (len(names), rps.shape[0]))
+        first = self.index.append(emb, rps)
+        self.songList = list(self.songList) + names
+        self._updated()
+        if persist:
+            from . import dbfiles
+            host = emb.detach().cpu().numpy() if isinstance(emb, torch.Tensor) else emb
+            dbfiles.add_songs(self.dir_for_db, names, host, rps)
+        return first
+
+    def song_ids(self, ids_or_names):
+        """ids (int) and songList.txt lines (str; every song of that name) -> sorted ids; unknown ones raise ValueError"""
+        out = set()
+        for x in ids_or_names:
+            if isinstance(x, str):
+                hit = [i for i, n in enumerate(self.songList) if n == x]
+                if not hit:
+                    raise ValueError("no song %r in the database" % x)
+                out.update(hit)
+            elif 0 <= int(x) < len(self.songList):
+                out.add(int(x))
+            else:
+                raise ValueError("no song #%d in the database (0..%d)" % (int(x), len(self.songList) - 1))
+        return sorted(out)
+
+    def remove_songs(self, ids_or_names, persist=True):
+        """The songs lose their rows and keep their ids (0-row songs, as landmarkKey spells them) -> the ids.  Handle
+        first, then with persist the files through dbfiles.remove_songs.  A blocking maintenance call."""
+        self._update_check("remove_songs")
+        ids = self.song_ids(ids_or_names)
+        self.index.remove_songs(ids)
+        self._updated()
+        if persist:
+            from . import dbfiles
+            dbfiles.remove_songs(self.dir_for_db, ids)
+        return ids
 
     # ---- self-match: the database asked about itself ------------------------------------------------
     def _embeddings_map(self):

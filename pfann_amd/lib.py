@@ -70,6 +70,11 @@ SYMBOLS = {
     "pfann_db_ntotal": (c_int64, [c_void_p]),
     "pfann_db_bytes": (c_int64, [c_void_p]),
     "pfann_db_load": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_int, c_int64]),
+    "pfann_db_reserve": (c_int, [c_void_p, c_int64, c_int]),
+    "pfann_db_capacity": (c_int64, [c_void_p]),
+    "pfann_db_row_norm_max": (c_float, [c_void_p]),
+    "pfann_db_append": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int32), c_int]),
+    "pfann_db_remove_songs": (c_int, [c_void_p, POINTER(c_int32), c_int]),
     "pfann_search_topk": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "pfann_search_topk_excl": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pfann_search_bound": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
