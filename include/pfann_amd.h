@@ -20,6 +20,7 @@
  *   pfann_search_topk       database.py:121  index.search(query, top_k)  (exact flat IP)
  *   pfann_match             database.py:117-166 query_embeddings_base (search + rerank)
  *   pfann_match_windows_dense  database.py:129-163 with every row's label list = the whole database (no counterpart)
+ *   pfann_match_windows_dense_topn  the same candidates, the n best songs per window and the per-song block (no counterpart)
  */
 #ifndef PFANN_AMD_H
 #define PFANN_AMD_H
@@ -493,6 +494,53 @@ int pfann_match_windows_dense(pfann_db *db, const float *q_dev,
                               int window, int hop, const int64_t *wfirst_dev, int64_t n_windows,
                               const int32_t *excl_song_dev /* [nR] or NULL */,
                               pfann_match_result *results_dev, void *stream);
+
+/* Dense matcher, ranked: the n best SONGS of every window over every alignment, 1 <= n <= 64 (csrc/dense.hip).  Recordings,
+ * windows, wfirst_dev, n_windows, short and empty recordings and excl_song_dev follow pfann_match_windows_dense.
+ * top_dev[n_windows][n]; n_found_dev[n_windows] and song_scores_dev[n_windows][n_songs][2] may be NULL.
+ *   candidates, totals   exactly those of pfann_match_windows_dense: every (song s with rows, offset o) with
+ *                 -(n_rows-1) <= o <= len_s - 1; total(s, o) adds the row dots in ascending row order from +0 in fp32, a row
+ *                 dot is the MFMA's fmaf chain over ascending k; score = (double)total / (double)n_rows;
+ *   per-song best  among a song's candidates the largest total, strict >, first wins in offset order: ties to the smaller offset;
+ *   ranking       songs by score descending, ties to the lower song id.  Entry i = the i-th song: song, offset and score of
+ *                 its best candidate, shift 0, n_cand = the distinct candidates of THAT song, len_s + n_rows - 1: field for
+ *                 field what pfann_match_topn returns for the slice (mode 0, frame_shift_mul 1, score_alpha 0) when every
+ *                 row's label list is the whole database;
+ *   entry 0       equals pfann_match_windows_dense's result for the same arguments in song, offset, shift and score, bit for
+ *                 bit (n_cand differs by definition);
+ *   prefix        the entries for n = a are the first a entries for n = b > a;
+ *   padding       entries past the songs are {song -1, offset 0, shift 0, n_cand 0, score -inf}; n_found = the songs with rows,
+ *                 not counting the excluded song, not capped at n; a window without a candidate: all padding, n_found 0;
+ *   song_scores   when given, EVERY slot of every window is written: ((float)score, (float)offset) of the song's best
+ *                 candidate by the rule above where that score, rounded to float32, is > 0, and (0, 0) everywhere else
+ *                 (songs without rows, the excluded song, scores <= 0: the reference's zero-initialised block records only
+ *                 scores above it, database.py:125,158).  Offsets are frames; pfann_song_scores_to_seconds converts them.
+ *                 ONE DELIBERATE DIFFERENCE from pfann_match's block: that block compares a song's candidates after rounding
+ *                 the score to float32, this one compares totals; the two differ only where two different totals of one song
+ *                 round to the same float32 score (then the offsets may differ, the scores do not).
+ * BYTE CONTRACT: a window's n * 24 result bytes, its n_found and its row of the block are a function of the window's rows,
+ * the database, its recording's excluded song and n (through the prefix rule only) -- not of hop, the other windows or
+ * recordings of the call, the tiling, how the call was chunked, or the run.
+ * The tile kernel of pfann_match_windows_dense reduces the candidate totals of every (window, tile) per SONG in LDS and
+ * leaves each song's best packed word with one 64-bit atomicMax in a workspace [windows of a chunk][n_songs] that the
+ * handle owns (8 bytes per pair, zeroed per chunk, at most 256 MB unless one row-tile slot of windows needs more); a select
+ * kernel, one workgroup per window, lists the n largest words -- word order is the ranking -- and fills n_found and the
+ * block.  Longer calls walk chunks of whole row-tile slots; PFANN_DENSE_TOPN_WINDOWS=<windows> in the environment (read at
+ * every call) lowers the windows per chunk, rounded up to whole slots.
+ * Fully asynchronous on `stream`, with ONE exception: a call that has to grow the workspace waits for `stream` first (the rule
+ * of pfann_search_topk_excl's range buffers).  The workspace is sized from the handle's n_songs at every call, so after
+ * pfann_db_append / pfann_db_remove_songs the call answers as a fresh handle would ("Database updates").
+ * Returns -1 with a message, launches nothing and writes nothing, when n is outside 1..64, the handle is a shard
+ * (pfann_match_windows' message), the storage is fp16-only, window is outside 1..64, hop < 1, d % 4 != 0, or
+ * ntotal + n_songs * (window - 1) >= 2^32 (the packed id). */
+int pfann_match_windows_dense_topn(pfann_db *db, const float *q_dev,
+                                   const int64_t *rstart_dev, const int32_t *rlen_dev, int64_t nR,
+                                   int window, int hop, const int64_t *wfirst_dev, int64_t n_windows,
+                                   const int32_t *excl_song_dev /* [nR] or NULL */, int n,
+                                   pfann_match_result *top_dev /* [n_windows][n] */,
+                                   int32_t *n_found_dev /* [n_windows] or NULL */,
+                                   float *song_scores_dev /* [n_windows][n_songs][2] or NULL */,
+                                   void *stream);
 
 /* Songs whose rows all live in this shard: [*song_lo, *song_hi) (either pointer may be NULL); returns their number. */
 int pfann_db_owned_songs(pfann_db *db, int *song_lo, int *song_hi);

@@ -651,6 +651,8 @@ struct pfann_db {
     size_t match_scratch_bytes = 0;
     void *win_scratch = nullptr;        // pfann_match_windows, general path: (qstart, qlen) of the expanded windows
     size_t win_scratch_bytes = 0;
+    void *dense_ws = nullptr;           // pfann_match_windows_dense_topn: per-song words of one chunk of windows, grown on demand
+    size_t dense_ws_bytes = 0;
     int64_t max_song_rows = 0;          // longest song (pfann_db_load)
     // updates (pfann_db_reserve / _append / _remove_songs).  Invariant: n == 0 <=> emb == emb_h == nullptr and cap == 0 (what
     // a fresh load of no rows leaves), so a reservation on an empty handle is only noted and honoured by the first append
@@ -696,6 +698,7 @@ void pfann_db_destroy(pfann_db *db) {
     if (db->ws.excl) (void)hipFree(db->ws.excl);        // (excl_tile lies in the same allocation)
     if (db->match_scratch) (void)hipFree(db->match_scratch);
     if (db->win_scratch) (void)hipFree(db->win_scratch);
+    if (db->dense_ws) (void)hipFree(db->dense_ws);
     if (db->seq_scratch) (void)hipFree(db->seq_scratch);
     if (db->seq_host) (void)hipHostFree(db->seq_host);
     if (db->seq_stream) (void)hipStreamDestroy(db->seq_stream);
@@ -1324,6 +1327,65 @@ int pfann_match_windows_dense(pfann_db *db, const float *q, const int64_t *rstar
     a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
     a.nW = n_windows; a.excl = excl_song; a.results = results;
     return launch_match_windows_dense(a, with_rows, (hipStream_t)stream);
+}
+
+int pfann_match_windows_dense_topn(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
+                                   int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, int n,
+                                   pfann_match_result *top, int32_t *n_found, float *song_scores, void *stream) {
+    PF_HIP(hipSetDevice(db->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || n > 64) { set_error("match_windows_dense_topn: n=%d outside 1..64", n); return -1; }
+    if (top == nullptr) { set_error("match_windows_dense_topn: top_dev is null"); return -1; }
+    if (db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
+        db->song_pos_h.empty() || db->song_pos_h.back() != db->n) {
+        set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
+        return -1;
+    }
+    if (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr)) {
+        set_error("match_windows_dense_topn: fp16-only storage (the dense matcher scores fp32 rows)");
+        return -1;
+    }
+    if (db->d % 4 != 0) { set_error("match_windows_dense_topn: d %% 4 != 0 (d=%d)", db->d); return -1; }
+    if (window < 1 || window > 64 || hop < 1 || nR < 0 || n_windows < 0) {
+        set_error("match_windows_dense_topn: window=%d (1..64) hop=%d nR=%lld n_windows=%lld", window, hop, (long long)nR,
+                  (long long)n_windows);
+        return -1;
+    }
+    if (db->n + (int64_t)db->n_songs * (window - 1) >= (1ll << 32)) {
+        set_error("match_windows_dense_topn: %lld rows and %d songs at window %d do not fit the 32-bit alignment id", (long long)db->n,
+                  db->n_songs, window);
+        return -1;
+    }
+    if (nR == 0 || n_windows == 0) return 0;
+    // chunks of whole row-tile slots: the workspace holds 8 bytes per (window the chunk's slots can hold, song), at most 256 MB
+    // unless one slot alone needs more; PFANN_DENSE_TOPN_WINDOWS (read per call) lowers the windows per chunk
+    const int wps = dense_topn_wps(window, hop);
+    const int64_t n_slots = dense_topn_slots(n_windows, nR, window, hop);
+    const int64_t songs = std::max(db->n_songs, 1);
+    int64_t cap = (256ll << 20) / (8 * songs);
+    const char *env = getenv("PFANN_DENSE_TOPN_WINDOWS");
+    if (env != nullptr && env[0] != 0 && atoll(env) > 0) cap = std::min<int64_t>(cap, atoll(env));
+    const int64_t step = std::min(n_slots, std::max<int64_t>(1, cap / wps));
+    const size_t need = (size_t)step * wps * songs * 8;
+    if (db->dense_ws_bytes < need) {                 // grow, then free: a failed allocation leaves the handle as it was
+        PF_HIP(hipStreamSynchronize(st));            // (the one exception to the asynchrony: earlier calls may still read it)
+        void *grown = nullptr;
+        PF_HIP(hipMalloc(&grown, need));
+        if (db->dense_ws) (void)hipFree(db->dense_ws);
+        db->dense_ws = grown;
+        db->dense_ws_bytes = need;
+    }
+    DenseTopnArgs a;
+    a.db = db->emb; a.ntotal = db->n; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+    a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
+    a.nW = n_windows; a.excl = excl_song; a.results = nullptr;
+    a.ws = reinterpret_cast<unsigned long long *>(db->dense_ws); a.wps = wps;
+    a.n = n; a.top = top; a.n_found = n_found; a.song_scores = song_scores;
+    for (int64_t s0 = 0; s0 < n_slots; s0 += step) {
+        a.slot_lo = s0; a.slot_n = std::min(step, n_slots - s0);
+        if (launch_match_windows_dense_topn(a, st)) return -1;
+    }
+    return 0;
 }
 
 int pfann_match_windows_topn(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart, const int32_t *rlen,

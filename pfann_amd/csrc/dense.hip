@@ -30,6 +30,7 @@
 #include "kernels.h"
 #include "match_common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace pfann {
 
@@ -55,12 +56,17 @@ __device__ __forceinline__ int dn_windows_of(int L, int window, int hop) {
     return L <= 0 ? 0 : (L < window ? 1 : (L - window) / hop + 1);
 }
 
-__global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a) {
+// RANKED (pfann_match_windows_dense_topn): the same tiles over the row-tile slots of one chunk; the pieces of a window start
+// are reduced per SONG inside the tile -- s_best is then one table per half of the workgroup, indexed by the song's first
+// column in the tile (s_head) -- and every non-empty entry goes out with one atomicMax into ws[window of the chunk][song].
+template <bool RANKED>
+__global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(typename std::conditional<RANKED, DenseTopnArgs, DenseArgs>::type a) {
     // S[DN_T][DN_LDS]; while the product runs its first bytes are the two K tiles As, Bs [DN_T][DN_LDK]
     extern __shared__ __attribute__((aligned(16))) float s_S[];          // DN_S_BYTES, dynamic: past the static 64 KB
     __shared__ long long s_cpos[1024];
     __shared__ int s_song[DN_T];
-    __shared__ unsigned long long s_best[DN_T];
+    __shared__ int s_head[RANKED ? DN_T : 1];
+    __shared__ unsigned long long s_best[RANKED ? 2 * DN_T : DN_T];
     static_assert(2 * DN_T * DN_LDK <= DN_T * DN_LDS, "the K tiles fit under S");
     float *As = s_S, *Bs = s_S + DN_T * DN_LDK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -68,12 +74,14 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a)
     const int SI = DN_T - (a.window - 1);                // window starts / alignments a tile owns per edge
     const int64_t n_slots = a.nW * a.hop / SI + a.nR;    // recording r owns the row-tile slots from wfirst[r] * hop / SI + r
     const int64_t NJ = (a.ntotal + a.window - 1 + SI - 1) / SI;
-    const int64_t n_items = n_slots * NJ;
+    int64_t slot_lo = 0, slot_n = n_slots;
+    if constexpr (RANKED) { slot_lo = a.slot_lo; slot_n = a.slot_n; }
+    const int64_t n_items = slot_n * NJ;
     int cshift, n_coarse;
     load_coarse_song_pos<DN_NT>(a.song_pos, a.n_songs, s_cpos, tid, cshift, n_coarse);
 
     for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
-        const int64_t jt = item / n_slots, slot = item - jt * n_slots;   // neighbouring workgroups share the db tile
+        const int64_t jt = item / slot_n, slot = slot_lo + (item - jt * slot_n);   // neighbouring workgroups share the db tile
         int64_t lo = 0, hi = a.nR;                       // first recording whose slots start after `slot`
         while (lo < hi) {
             const int64_t mid = (lo + hi) >> 1;
@@ -94,6 +102,11 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a)
             const int64_t g = J0 + tid;
             s_song[tid] = g >= 0 && g < a.ntotal ? song_of_label(a.song_pos, a.n_songs, s_cpos, cshift, n_coarse, g) : -1;
             s_best[tid] = 0;
+            if constexpr (RANKED) {                      // the song's first column in the tile (a column without a song: itself)
+                const int sg = s_song[tid];
+                s_head[tid] = sg >= 0 ? (int)max((int64_t)0, a.song_pos[sg] - J0) : tid;
+                s_best[DN_T + tid] = 0;
+            }
         }
 
         // ---- S = Q tile x db tile^T.  Thread tid stages rows (tid >> 2) and (tid >> 2) + 64 of both operands, eight
@@ -178,50 +191,113 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a)
                     s_S[(wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lhalf) * DN_LDS + wn * 64 + j * 32 + l31] = acc[i][j][e];
         __syncthreads();
 
-        // ---- diagonals: thread = column j, the two halves of the workgroup take the window starts in turn (wave-uniform i)
-        {
-            const int j = tid & (DN_T - 1);
+        if constexpr (RANKED) {
+            // ---- diagonals, per song: thread = column j, half h of the workgroup takes window start ib + h.  A thread's FIRST
+            // piece (the song of column j) is reduced over the lanes of the same song by a segmented shuffle maximum -- songs
+            // are contiguous in column order --, and the first lane of every run updates the half's table; later pieces
+            // (the stretch crossed a song boundary) update it directly.  Then one global atomicMax per non-empty entry.
+            const int j = tid & (DN_T - 1), half = tid >> 7;
             const int64_t g = J0 + j;
-            for (int i = tid >> 7; i < SI; i += DN_NT / DN_T) {
-                const int w0 = i0 + i;
-                if (w0 % a.hop != 0 || w0 / a.hop >= nw) continue;       // not a window start of this recording
-                unsigned long long best = 0;
-                if (j < SI) {
-                    int cur = s_song[j];
-                    float tot = 0.f;
-                    for (int t = 0; t < wl; ++t) {
-                        const int sg = s_song[j + t];
-                        if (sg != cur) {
-                            if (cur >= 0 && cur != excl) {
-                                const unsigned id = (unsigned)(g + (int64_t)(cur + 1) * (wl - 1));
-                                const unsigned long long x = ((unsigned long long)dn_ordered_bits(tot) << 32) | (0xFFFFFFFFu - id);
-                                best = x > best ? x : best;
+            unsigned long long *tab = s_best + half * DN_T;
+            const int head0 = s_head[j];
+            const int first_w = (i0 + a.hop - 1) / a.hop;            // the tile's first window start, in windows
+            const int64_t ws_row0 = (slot - slot_lo) * a.wps - first_w;
+            auto starts = [&](int i) { const int w0 = i0 + i; return i < SI && w0 % a.hop == 0 && w0 / a.hop < nw; };
+            auto packed = [&](int cur, float tot) -> unsigned long long {
+                if (cur < 0 || cur == excl) return 0;
+                const unsigned id = (unsigned)(g + (int64_t)(cur + 1) * (wl - 1));
+                return ((unsigned long long)dn_ordered_bits(tot) << 32) | (0xFFFFFFFFu - id);
+            };
+            for (int ib = 0; ib < SI; ib += DN_NT / DN_T) {
+                const bool act0 = starts(ib), act1 = starts(ib + 1);
+                if (!act0 && !act1) continue;                        // (the whole workgroup)
+                const int i = ib + half;
+                if (half ? act1 : act0) {                            // (whole waves)
+                    unsigned long long x0 = 0;
+                    if (j < SI) {
+                        int cur = s_song[j], head = head0;
+                        bool first = true;
+                        float tot = 0.f;
+                        for (int t = 0; t < wl; ++t) {
+                            const int sg = s_song[j + t];
+                            if (sg != cur) {
+                                const unsigned long long x = packed(cur, tot);
+                                if (first) x0 = x; else if (x != 0) atomicMax(&tab[head], x);
+                                first = false;
+                                cur = sg;
+                                head = s_head[j + t];
+                                tot = 0.f;
                             }
-                            cur = sg;
-                            tot = 0.f;
+                            tot += s_S[(i + t) * DN_LDS + j + t];
                         }
-                        tot += s_S[(i + t) * DN_LDS + j + t];
+                        const unsigned long long x = packed(cur, tot);
+                        if (first) x0 = x; else if (x != 0) atomicMax(&tab[head], x);
                     }
-                    if (cur >= 0 && cur != excl) {
-                        const unsigned id = (unsigned)(g + (int64_t)(cur + 1) * (wl - 1));
-                        const unsigned long long x = ((unsigned long long)dn_ordered_bits(tot) << 32) | (0xFFFFFFFFu - id);
-                        best = x > best ? x : best;
-                    }
-                }
 #pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const unsigned long long v = __shfl_xor(best, o, 64);
-                    best = v > best ? v : best;
+                    for (int o = 1; o < 64; o <<= 1) {               // lane l: the maximum of lanes l .. l + 2 o - 1 of its run
+                        const unsigned long long v = __shfl_down(x0, o, 64);
+                        const int hv = __shfl_down(head0, o, 64);
+                        if (lane + o < 64 && hv == head0 && v > x0) x0 = v;
+                    }
+                    const int hp = __shfl_up(head0, 1, 64);
+                    if ((lane == 0 || hp != head0) && x0 != 0) atomicMax(&tab[head0], x0);
                 }
-                if (lane == 0 && best != 0) atomicMax(&s_best[i], best);
+                __syncthreads();
+                {
+                    const unsigned long long x = tab[j];             // entry j: the song whose first column is j
+                    if (x != 0) {                                    // (only a half with a window start has any)
+                        tab[j] = 0;
+                        atomicMax(&a.ws[(ws_row0 + (i0 + i) / a.hop) * a.n_songs + s_song[j]], x);
+                    }
+                }
+                __syncthreads();                                     // the tables are empty again
             }
-        }
-        __syncthreads();
-        if (tid < SI) {
-            const unsigned long long x = s_best[tid];
-            if (x != 0) {                                // (only window starts of the recording ever get a word)
-                const int64_t w = wf + (i0 + tid) / a.hop;
-                atomicMax(reinterpret_cast<unsigned long long *>(&a.results[w].score), x);
+        } else {
+            // ---- diagonals: thread = column j, the two halves of the workgroup take the window starts in turn (wave-uniform i)
+            {
+                const int j = tid & (DN_T - 1);
+                const int64_t g = J0 + j;
+                for (int i = tid >> 7; i < SI; i += DN_NT / DN_T) {
+                    const int w0 = i0 + i;
+                    if (w0 % a.hop != 0 || w0 / a.hop >= nw) continue;       // not a window start of this recording
+                    unsigned long long best = 0;
+                    if (j < SI) {
+                        int cur = s_song[j];
+                        float tot = 0.f;
+                        for (int t = 0; t < wl; ++t) {
+                            const int sg = s_song[j + t];
+                            if (sg != cur) {
+                                if (cur >= 0 && cur != excl) {
+                                    const unsigned id = (unsigned)(g + (int64_t)(cur + 1) * (wl - 1));
+                                    const unsigned long long x = ((unsigned long long)dn_ordered_bits(tot) << 32) | (0xFFFFFFFFu - id);
+                                    best = x > best ? x : best;
+                                }
+                                cur = sg;
+                                tot = 0.f;
+                            }
+                            tot += s_S[(i + t) * DN_LDS + j + t];
+                        }
+                        if (cur >= 0 && cur != excl) {
+                            const unsigned id = (unsigned)(g + (int64_t)(cur + 1) * (wl - 1));
+                            const unsigned long long x = ((unsigned long long)dn_ordered_bits(tot) << 32) | (0xFFFFFFFFu - id);
+                            best = x > best ? x : best;
+                        }
+                    }
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) {
+                        const unsigned long long v = __shfl_xor(best, o, 64);
+                        best = v > best ? v : best;
+                    }
+                    if (lane == 0 && best != 0) atomicMax(&s_best[i], best);
+                }
+            }
+            __syncthreads();
+            if (tid < SI) {
+                const unsigned long long x = s_best[tid];
+                if (x != 0) {                                // (only window starts of the recording ever get a word)
+                    const int64_t w = wf + (i0 + tid) / a.hop;
+                    atomicMax(reinterpret_cast<unsigned long long *>(&a.results[w].score), x);
+                }
             }
         }
         __syncthreads();                                 // S, the songs and the maxima are free for the next tile
@@ -275,12 +351,132 @@ int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipS
         const int64_t NJ = (a.ntotal + a.window - 1 + SI - 1) / SI;
         const int64_t n_items = n_slots * NJ;
         const double rows = (double)a.nW * a.hop + (double)a.nR * a.window;
-        if (ensure_dyn_lds((const void *)match_windows_dense_kernel, DN_S_BYTES)) return -1;
+        if (ensure_dyn_lds((const void *)match_windows_dense_kernel<false>, DN_S_BYTES)) return -1;
         ProfScope ps("seq_match_windows_dense", s, 2.0 * rows * (double)a.ntotal * a.d);
-        PF_LAUNCH(match_windows_dense_kernel, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
+        PF_LAUNCH(match_windows_dense_kernel<false>, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
         PF_HIP(hipGetLastError());
     }
     PF_LAUNCH(dense_decode_kernel, dim3((unsigned)cdiv(a.nW, 256)), dim3(256), 0, s, a, songs_with_rows);
+    PF_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- ranked: ws -> the n best songs of every window of the chunk (pfann_match_windows_dense_topn) --------------------------
+// One workgroup per (slot of the chunk, window start of the slot); a pair that is no window of the call ends at once.  A
+// song's word holds its best candidate; word order IS the ranking (higher total first, equal totals to the smaller id: the
+// lower song), and words are distinct, so the lists are selected by comparing words, never by arrival: every thread keeps
+// the largest word of its strided share of the songs, the workgroup's maximum is the next entry, and the thread that held
+// it looks for its next largest word below it.
+static constexpr int DN_SEL_NT = 256;
+
+__global__ __launch_bounds__(DN_SEL_NT) void dense_select_kernel(DenseTopnArgs a) {
+    __shared__ unsigned long long s_max[2][DN_SEL_NT / 64];
+    __shared__ int s_cnt[DN_SEL_NT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int SI = DN_T - (a.window - 1);
+    const int64_t slot = a.slot_lo + blockIdx.x / a.wps;
+    const int kw = blockIdx.x % a.wps;
+    int64_t lo = 0, hi = a.nR;                           // the recording of the slot, as in the tile kernel
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.wfirst[mid] * a.hop / SI + mid <= slot) lo = mid + 1; else hi = mid;
+    }
+    const int64_t r = lo - 1;
+    const int L = a.rlen[r];
+    const int64_t wf = a.wfirst[r];
+    const int nw = (int)min((int64_t)dn_windows_of(L, a.window, a.hop), a.wfirst[r + 1] - wf);
+    const int64_t I0 = (slot - (wf * a.hop / SI + r)) * SI;
+    if (nw <= 0 || I0 > (int64_t)(nw - 1) * a.hop) return;
+    const int64_t wi = (I0 + a.hop - 1) / a.hop + kw;    // window of the recording
+    if (wi * a.hop >= I0 + SI || wi >= nw) return;
+    const int64_t w = wf + wi;
+    const int n = min(a.window, L);
+    const unsigned long long *row = a.ws + (int64_t)blockIdx.x * a.n_songs;
+    pfann_match_result *top = a.top + w * a.n;
+    auto offset_of = [&](unsigned long long x, int s) {
+        return (int)((int64_t)(0xFFFFFFFFu - (unsigned)x) - a.song_pos[s] - (int64_t)(s + 1) * (n - 1));
+    };
+    auto score_of = [&](unsigned long long x) { return (double)dn_ordered_float((unsigned)(x >> 32)) / (double)n; };
+
+    unsigned long long mine = 0;                         // the largest word of this thread's songs not yet listed
+    int mine_s = -1, cnt = 0;
+    for (int s = tid; s < a.n_songs; s += DN_SEL_NT) {
+        const unsigned long long x = row[s];
+        cnt += x != 0;
+        if (x > mine) { mine = x; mine_s = s; }
+        if (a.song_scores != nullptr) {                  // the reference's block records only scores above its zeros
+            const float f = x != 0 ? (float)score_of(x) : 0.f;
+            float2 v = {0.f, 0.f};
+            if (f > 0.f) { v.x = f; v.y = (float)offset_of(x, s); }
+            reinterpret_cast<float2 *>(a.song_scores)[w * a.n_songs + s] = v;
+        }
+    }
+    if (a.n_found != nullptr) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+        if (lane == 0) s_cnt[wave] = cnt;
+        __syncthreads();
+        if (tid == 0) {
+            int c = 0;
+            for (int i = 0; i < DN_SEL_NT / 64; ++i) c += s_cnt[i];
+            a.n_found[w] = c;
+        }
+    }
+    for (int e = 0; e < a.n; ++e) {
+        unsigned long long best = mine;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long v = __shfl_xor(best, o, 64);
+            best = v > best ? v : best;
+        }
+        if (lane == 0) s_max[e & 1][wave] = best;
+        __syncthreads();                                 // (one per entry: the next entry writes the other row)
+#pragma unroll
+        for (int i = 0; i < DN_SEL_NT / 64; ++i) best = s_max[e & 1][i] > best ? s_max[e & 1][i] : best;
+        if (best == 0) {                                 // no song left: padding
+            for (int i = e + tid; i < a.n; i += DN_SEL_NT) {
+                pfann_match_result res;
+                res.song = -1; res.offset = 0; res.shift = 0; res.n_cand = 0; res.score = -INFINITY;
+                top[i] = res;
+            }
+            return;
+        }
+        if (mine == best) {                              // words are distinct: exactly one thread
+            pfann_match_result res;
+            res.song = mine_s;
+            res.offset = offset_of(best, mine_s);
+            res.shift = 0;
+            res.n_cand = (int)(a.song_pos[mine_s + 1] - a.song_pos[mine_s]) + n - 1;
+            res.score = score_of(best);
+            top[e] = res;
+            mine = 0; mine_s = -1;
+            if (e + 1 < a.n)
+                for (int s = tid; s < a.n_songs; s += DN_SEL_NT) {
+                    const unsigned long long x = row[s];
+                    if (x < best && x > mine) { mine = x; mine_s = s; }
+                }
+        }
+    }
+}
+
+int dense_topn_wps(int window, int hop) { return (DN_T - (window - 1) + hop - 1) / hop; }
+int64_t dense_topn_slots(int64_t nW, int64_t nR, int window, int hop) { return nW * hop / (DN_T - (window - 1)) + nR; }
+
+int launch_match_windows_dense_topn(const DenseTopnArgs &a, hipStream_t s) {
+    if (a.nR <= 0 || a.nW <= 0 || a.slot_n <= 0) return 0;
+    const int SI = DN_T - (a.window - 1);
+    const int64_t rows = a.slot_n * a.wps;               // windows the chunk's slots can hold
+    if (a.n_songs > 0) PF_HIP(hipMemsetAsync(a.ws, 0, (size_t)rows * a.n_songs * sizeof(unsigned long long), s));
+    if (a.ntotal > 0) {
+        const int64_t NJ = (a.ntotal + a.window - 1 + SI - 1) / SI;
+        const int64_t n_items = a.slot_n * NJ;
+        if (ensure_dyn_lds((const void *)match_windows_dense_kernel<true>, DN_S_BYTES)) return -1;
+        ProfScope ps("seq_match_windows_dense_topn", s, 2.0 * (double)a.slot_n * DN_T * (double)a.ntotal * a.d);
+        PF_LAUNCH(match_windows_dense_kernel<true>, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
+        PF_HIP(hipGetLastError());
+    }
+    ProfScope ps("seq_dense_select", s, (double)rows * a.n_songs * 8.0);
+    PF_LAUNCH(dense_select_kernel, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);
     PF_HIP(hipGetLastError());
     return 0;
 }

@@ -174,6 +174,18 @@ struct DenseArgs {
 };
 // songs_with_rows: songs of the database with len > 0 (n_cand)
 int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipStream_t s);
+// pfann_match_windows_dense_topn: one chunk of row-tile slots [slot_lo, slot_lo + slot_n) of the call (results unused).  The
+// tile kernel leaves every song's best packed word of every window of the chunk in ws, the select kernel ranks them.
+struct DenseTopnArgs : DenseArgs {
+    unsigned long long *ws; // [slot_n][wps][n_songs] packed words, zeroed by the launcher
+    int64_t slot_lo, slot_n;
+    int wps;                // window starts one slot can hold: ceil((128 - (window-1)) / hop)
+    int n; pfann_match_result *top; int32_t *n_found;   // top[nW][n]; n_found[nW] or null
+    float *song_scores;     // [nW][n_songs][2] or null
+};
+int dense_topn_wps(int window, int hop);
+int64_t dense_topn_slots(int64_t nW, int64_t nR, int window, int hop);
+int launch_match_windows_dense_topn(const DenseTopnArgs &a, hipStream_t s);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is per device
 int ensure_dyn_lds(const void *func, int bytes);
 

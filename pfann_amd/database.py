@@ -458,6 +458,44 @@ class DeviceIndex:
                                                         res.data_ptr(), self._stream()), "pfann_match_windows_dense")
         return (self.results_to_host(res) if to_host else res), wfirst
 
+    def match_windows_dense_topn(self, q, rstart, rlen, window, hop, n, exclude_song=None, want_song_scores=False, to_host=True):
+        """Ranked dense answers (pfann_match_windows_dense_topn): the n best songs of every window over EVERY alignment, and
+        with want_song_scores the per-song block [nW, n_songs, 2] of (float32 score, best offset in frames; zeros where the
+        score is not > 0).  Recordings, windows and exclude_song as in match_windows_dense.
+        -> ((top [nW, n] of RESULT_DTYPE, n_found int32 [nW], block or None), wfirst): entry 0 of a window is
+        match_windows_dense's answer; with to_host=False the device tensors (uint8 [nW, n, 24], int32 [nW], float32 block)."""
+        window, hop, n = int(window), int(hop), int(n)
+        if window < 1 or hop < 1:
+            raise ValueError("match_windows_dense_topn: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
+        if not 1 <= n <= 64:
+            raise _l.PfannError("match_windows_dense_topn: n=%d outside 1..64" % n)
+        q = q.to(self.device, torch.float32).contiguous()
+        rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
+        nR = int(rl_np.shape[0])
+        assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
+        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
+        nW = int(wfirst[-1])
+        top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
+        ss = torch.empty((nW, self.n_songs, 2), device=self.device, dtype=torch.float32) if want_song_scores else None
+        ex = None
+        if exclude_song is not None:
+            ex_np = np.ascontiguousarray(exclude_song, dtype=np.int32)
+            if ex_np.shape != (nR,):
+                raise ValueError("match_windows_dense_topn: exclude_song wants one song id per recording (%d), got %r" % (nR, ex_np.shape))
+            ex = _l.upload_async(ex_np, self.device, np.int32)
+        if nW:
+            rs, rl = self._upload_ranges(rs_np, rl_np)
+            wf = _l.upload_async(wfirst, self.device, np.int64)
+            _l.check(self.lib.pfann_match_windows_dense_topn(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
+                                                             wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None, n,
+                                                             top.data_ptr(), n_found.data_ptr(),
+                                                             ss.data_ptr() if ss is not None else None, self._stream()),
+                     "pfann_match_windows_dense_topn")
+        if not to_host:
+            return (top, n_found, ss), wfirst
+        return self.topn_to_host(top, n_found) + (ss.cpu().numpy() if ss is not None else None,), wfirst
+
 
 def window_counts(rlen, window, hop):
     """windows per recording (include/pfann_amd.h, pfann_match_windows): starts 0, hop, 2*hop, .. while w0 + window <= L;
@@ -911,6 +949,74 @@ class Database:
             return {"res": res, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None, "hop": int(hop)}
         return self._launch_dense(emb, match)
 
+    def monitor_dense_topn_launch(self, emb, rstart, rlen, window, hop, n, edge_window=0):
+        """monitor_topn_launch on the ranked dense matcher (pfann_match_windows_dense_topn): no search, the n best songs of every
+        window -- and of every short window of the edge pass -- over every alignment.  -> what monitor_dense_topn_finish reads."""
+        self._dense_check("monitor_dense_topn_launch")
+
+        def match():
+            def windows(w, h):
+                (top, n_found, _), wfirst = self.index.match_windows_dense_topn(emb, rstart, rlen, w, h, n, to_host=False)
+                return (top, n_found), wfirst
+            (top, n_found), wfirst = windows(window, hop)
+            return {"res": top, "n_found": n_found, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None,
+                    "hop": int(hop)}
+        return self._launch_dense(emb, match)
+
+    def monitor_dense_topn_finish(self, p):
+        """Second half of monitor_dense_topn_launch: what monitor_topn_finish returns, votes = len_s + window rows - 1 (every
+        alignment of the song is a candidate)."""
+        return self._windows_topn_finish(p, self.frame_shift_mul)
+
+    # ---- plain queries through the dense form: every query is one recording and one window ----------------------------
+    def query_dense_launch(self, emb, qstart, qlen, n=1, want_song_scores=False):
+        """First half of query_dense_batch: the ranked dense matcher (pfann_match_windows_dense_topn) with window = the longest
+        query of the call (at most 64 segments; every query has at least one), so that by the short-recording rule every query is
+        exactly one window over all its rows, and by the byte contract its answer does not depend on what it was batched with.
+        No search.  The per-song block is converted to seconds where it lives, as query_launch does."""
+        self._dense_check("query_dense_launch")
+        ql = np.ascontiguousarray(qlen, dtype=np.int32)
+        if ql.shape[0] and (int(ql.min()) < 1 or int(ql.max()) > 64):
+            raise _l.PfannError("query_dense_launch: a query has 1..64 segments (got %d..%d)" % (int(ql.min()), int(ql.max())))
+        window = int(ql.max()) if ql.shape[0] else 1
+
+        def match():
+            (top, n_found, ss), wfirst = self.index.match_windows_dense_topn(emb, qstart, ql, window, 1, n,
+                                                                             want_song_scores=want_song_scores, to_host=False)
+            assert int(wfirst[-1]) == ql.shape[0]
+            self.index.song_scores_to_seconds(ss, 1, self.hop_size)
+            return {"res": top, "n_found": n_found, "ss": ss}
+        return self._launch_dense(emb, match)
+
+    def query_dense_launch_chunks(self, emb, qstart, qlen, n=1, want_song_scores=False):
+        """query_dense_launch cut by the score-block budget, lazily, exactly as query_launch_chunks cuts query_launch"""
+        nq = len(qlen)
+        step = max(1, nq) if not want_song_scores else max(1, min(nq, self.max_score_pairs // max(len(self.songList), 1)))
+        qstart = np.asarray(qstart, dtype=np.int64)
+
+        def launch(j0, j1):
+            r0 = int(qstart[j0])
+            r1 = int(qstart[j1 - 1]) + int(qlen[j1 - 1])
+            sub = emb if (j0 == 0 and j1 == nq) else emb[r0:r1]
+            return self.query_dense_launch(sub, qstart[j0:j1] - r0, qlen[j0:j1], n, want_song_scores)
+        return LazyLaunches([(j0, min(j0 + step, nq)) for j0 in range(0, nq, step)], launch)
+
+    def query_dense_finish(self, p, reuse_buffers=False):
+        """Second half: -> (answers, ranked): answers as query_finish gives them, [(score, (song, time_s), song_score|None)]
+        from entry 0, and ranked as query_topn_finish gives them, per query up to n (score, (song, time_s)) best first; both
+        through the one read-back and the one formatter.  reuse_buffers: as in query_finish."""
+        res, land = self._read_back(p)
+        if land is None:
+            blocks = [None] * len(res)
+        else:
+            blocks = land.numpy() if reuse_buffers else land.numpy().copy()
+        answers = [r + (b,) for r, b in zip(self._answers(res[:, 0], 0), blocks)]
+        return answers, self._answers(res, 0, topn_tuples)
+
+    def query_dense_batch(self, emb, qstart, qlen, n=1, want_song_scores=False):
+        """emb: torch cuda [sum(qlen), d] unit-norm rows, queries of 1..64 segments -> (answers, ranked), see query_dense_finish"""
+        return self.query_dense_finish(self.query_dense_launch(emb, qstart, qlen, n, want_song_scores))
+
     def monitor_finish(self, p):
         """Second half: -> per recording a structured array (w0, score, song, time_s), one entry per window: its first
         row, and score / song / time exactly as query_finish reports them for that slice (no candidate: -inf, -1, 0)."""
@@ -944,7 +1050,10 @@ class Database:
         first, each entry formatted as monitor_finish formats a window's answer -- entry 0 IS that answer --, padding
         entries (-inf, -1, 0, votes 0); per recording n_found int32 [windows], the window's candidate songs, not capped at n).
         The ranked short windows of the edge pass are left in p["edge_rows"]."""
-        fsm, wfirst = self.frame_shift_mul, p["wfirst"]
+        return self._windows_topn_finish(p, self.frame_shift_mul)
+
+    def _windows_topn_finish(self, p, fsm):
+        wfirst = p["wfirst"]
         out = monitor_topn_rows(self._read_back(p)[0], wfirst, p["hop"], p["mode"], fsm, self.hop_size)
         n_found = p["n_found"].cpu().numpy()
         if p.get("fine") is not None:
@@ -1020,14 +1129,19 @@ class Database:
             self._emb_map = np.memmap(path, dtype=np.float32, mode="r", shape=(n_rows, self.d)) if n_rows else np.zeros((0, self.d), np.float32)
         return self._emb_map
 
-    def self_match_launch(self, song_lo, song_hi, window, hop, k=None, emb=None, dense=False):
+    def self_match_launch(self, song_lo, song_hi, window, hop, k=None, emb=None, dense=False, top=1):
         """One launch group of self-match, asynchronous like monitor_launch: the rows of the songs [song_lo, song_hi) are the
         recordings (song s: rows [song_pos[s], song_pos[s + 1]) of `emb`, by default the memory-mapped `embeddings` file),
         every row is searched with its own song's rows left out (pfann_search_topk_excl: exact, the own rows are never
         nominated), and the windowed matcher answers every window of `window` rows, `hop` apart.  The rows are database
         rows, one per hop_size, so the matcher runs with frame_shift_mul 1.  Songs without rows give no windows.
         dense=True: no search; the dense matcher (pfann_match_windows_dense) scores every alignment of every OTHER song --
-        the song's own id is its recording's excluded song -- so the recall does not depend on k."""
+        the song's own id is its recording's excluded song -- so the recall does not depend on k.
+        top=N > 1: the N best OTHER songs of every window, by pfann_match_windows_dense_topn (dense) or pfann_match_windows_topn
+        on the masked search's labels; self_match_finish then answers as monitor_topn_finish does."""
+        top = int(top)
+        if not 1 <= top <= 64:
+            raise _l.PfannError("self_match: top=%d outside 1..64" % top)
         if dense:
             self._dense_check("self_match")
         if self.sharded is not None:
@@ -1042,28 +1156,40 @@ class Database:
         q = _l.upload_async(np.array(emb[r0:r1], dtype=np.float32).reshape(-1, self.d), self.index.device, np.float32)
         if dense:
             def match_dense():
-                res, wfirst = self.index.match_windows_dense(q, rstart, rlen, window, hop,
-                                                             exclude_song=np.arange(song_lo, song_hi, dtype=np.int32), to_host=False)
+                own = np.arange(song_lo, song_hi, dtype=np.int32)
+                if top > 1:
+                    (res, n_found, _), wfirst = self.index.match_windows_dense_topn(q, rstart, rlen, window, hop, top,
+                                                                                    exclude_song=own, to_host=False)
+                    return {"res": res, "n_found": n_found, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
+                res, wfirst = self.index.match_windows_dense(q, rstart, rlen, window, hop, exclude_song=own, to_host=False)
                 return {"res": res, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
             return self._launch_dense(q, match_dense)
 
         def match(I, mode):
+            if top > 1:
+                (res, n_found), wfirst = self.index.match_windows_topn(q, I, rstart, rlen, window, hop, top, 1, self.score_alpha,
+                                                                       mode, to_host=False)
+                return {"res": res, "n_found": n_found, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
             res, wfirst = self.index.match_windows(q, I, rstart, rlen, window, hop, 1, self.score_alpha, mode, to_host=False)
             return {"res": res, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
         return self._launch(q, match, k=k, exclude=(lo, hi))
 
     def self_match_finish(self, p):
-        """-> per song of the group a structured array (w0, score, song, time_s), one entry per window, as monitor_finish"""
+        """-> per song of the group a structured array (w0, score, song, time_s), one entry per window, as monitor_finish; a
+        launch with top > 1: per song the [windows, top] array of monitor_topn_finish (its n_found is left in p["n_found_rows"])"""
+        if "n_found" in p:
+            out, p["n_found_rows"] = self._windows_topn_finish(p, 1)
+            return out
         return self._windows_finish(p, 1)
 
-    def self_match(self, song_lo, song_hi, window, hop, k=None, emb=None, max_rows=None, dense=False):
+    def self_match(self, song_lo, song_hi, window, hop, k=None, emb=None, max_rows=None, dense=False, top=1):
         """Self-match of the songs [song_lo, song_hi): yields (song, rows) in song order, rows as monitor_finish gives them.
         The songs are cut into launch groups of at most max_rows rows (default PFANN_MAX_BATCH, 9728; a longer song is a
-        group of its own) and group g + 1 is launched before group g is read back, as the monitor does.  dense: see
-        self_match_launch."""
+        group of its own) and group g + 1 is launched before group g is read back, as the monitor does.  dense, top: see
+        self_match_launch (top > 1: rows is the ranked [windows, top] array of monitor_topn_finish)."""
         max_rows = int(os.environ.get("PFANN_MAX_BATCH", "9728")) if max_rows is None else int(max_rows)
         groups = self_match_groups(self.song_pos, int(song_lo), int(song_hi), max_rows)
-        for p in launch_ahead(groups, lambda g: self.self_match_launch(g[0], g[1], window, hop, k, emb, dense)):
+        for p in launch_ahead(groups, lambda g: self.self_match_launch(g[0], g[1], window, hop, k, emb, dense, top)):
             yield from zip(range(*p["songs"]), self.self_match_finish(p))
 
     # ---- the reference's per-query contract ---------------------------------------------

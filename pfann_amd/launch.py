@@ -113,3 +113,16 @@ def matcher_flags(args):
     if (top or no_bin) and (int(os.environ.get("PFANN_GPUS", "1") or 1) > 1 or int(os.environ.get("WORLD_SIZE", "1") or 1) > 1):
         return top, no_bin, "matcher: --top and --no-bin are not supported by a song-sharded multi-GPU run (unset PFANN_GPUS)"
     return top, no_bin, None
+
+
+DENSE_MAX_SEGMENTS = 64                                  # pfann_match_windows_dense_topn: rows of a window
+
+
+def matcher_dense_flag(args):
+    """matcher.py's --dense among its optional arguments -> (dense, error message or None).  Beside matcher_flags (whose
+    signature stays) for the same reason: a song-sharded multi-GPU run (PFANN_GPUS / WORLD_SIZE > 1) ends with status 2
+    before anything heavy is imported."""
+    dense = "--dense" in args
+    if dense and (int(os.environ.get("PFANN_GPUS", "1") or 1) > 1 or int(os.environ.get("WORLD_SIZE", "1") or 1) > 1):
+        return dense, "matcher: --dense is not supported by a song-sharded multi-GPU run: the dense matcher holds the whole database on one GPU (unset PFANN_GPUS)"
+    return dense, None

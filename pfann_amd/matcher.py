@@ -1,5 +1,5 @@
 """Matcher CLI, drop-in for the reference's matcher.py:
-    python matcher.py <query list> <database dir> <result file> [--top N] [--no-bin]
+    python matcher.py <query list> <database dir> <result file> [--top N] [--no-bin] [--dense]
 
 Same argv and outputs (matcher.py:34-42,84,158-163): `<result>` TSV "query\\tanswer",
 `<result-stem>_detail.csv` with header query,answer,score,time,part_scores, and
@@ -12,7 +12,12 @@ Two optional flags after the three positional arguments (without them every outp
              query, rank from 1, selected on the GPU (pfann_match_topn); an unreadable query gets one row name,1,error,-inf,0
   --no-bin   do not write `<result>.bin` and do not compute the per-song block; with --top no n_queries x n_songs array
              exists anywhere
-Neither is supported by a song-sharded multi-GPU run (PFANN_GPUS / WORLD_SIZE > 1): exit status 2.
+  --dense    answer every query with the dense matcher (pfann_match_windows_dense_topn, csrc/dense.hip): no search, EVERY
+             alignment of every song is a candidate, so the answer does not depend on the indexer's top_k.  Same files, same
+             columns: the TSV and _detail.csv from the best song, `.bin` from the per-song block, _top.csv from the ranked
+             list.  Defined for frame_shift_mul 1, score_alpha 0 and the python path (anything else: exit status 2); a query
+             of more than 64 segments gets the error row and one line on stderr.
+None of them is supported by a song-sharded multi-GPU run (PFANN_GPUS / WORLD_SIZE > 1): exit status 2.
 """
 import csv
 import ctypes
@@ -28,7 +33,7 @@ import torch
 from .builder import embed_file_batches, gather_round
 from .database import Database
 from .dist import finish_ranks, init_ranks, self_launch_if_asked
-from .launch import matcher_flags
+from .launch import DENSE_MAX_SEGMENTS, matcher_dense_flag, matcher_flags
 from .engine import Engine
 from .musicdata import MusicDataset
 from .utils import StageTimer, StartupClock, get_logger, init_logger, read_config
@@ -145,8 +150,9 @@ def main(argv=None):
         print("Usage: python %s <query list> <database dir> <result file>" % argv[0])
         return 1
     top_n, no_bin, err = matcher_flags(argv[4:])
-    if err:
-        print(err, file=sys.stderr)
+    dense, dense_err = matcher_dense_flag(argv[4:])
+    if err or dense_err:
+        print(err or dense_err, file=sys.stderr)
         return 2
     rc = self_launch_if_asked(argv)         # PFANN_GPUS=N: N ranks of this command, one per GPU
     if rc is not None:
@@ -200,7 +206,17 @@ def main(argv=None):
     db = db_box[0]
     db.attach_engine(engine)
     clock.lap("database (rest of its load after the engine was ready)")
-    if top_n or no_bin:
+    if dense:
+        try:
+            db._dense_check("matcher --dense")
+        except Exception as x:                      # (PfannError: a config the dense form does not define)
+            print(str(x), file=sys.stderr)
+            return 2
+        if int(db.song_pos[-1]):
+            wq = torch.zeros((19, db.d), device=db.index.device)
+            wq[:, 0] = 1.0
+            db.query_dense_batch(wq, [0], [19], max(top_n, 1), want_song_scores=not no_bin)
+    elif top_n or no_bin:
         db.warmup(rows=warm, want_song_scores=not no_bin, topn=top_n)
     else:
         db.warmup(rows=warm * (ranks.world if multi else 1))
@@ -212,15 +228,23 @@ def main(argv=None):
     out = ResultWriter(result_file, len(db.songList), ranks=ranks, n_queries=len(dataset), song_range=db.song_range,
                        top=top_n > 0, no_bin=no_bin)
 
+    too_long = lambda n: dense and n > DENSE_MAX_SEGMENTS
+
     def launch(items):
         """items: one launch group of (index, n_seg, emb) in list order -> search + match in flight."""
-        good = [(i, n, e) for i, n, e in items if n]
+        good = [(i, n, e) for i, n, e in items if n and not too_long(n)]
+        for i, n, _ in items:
+            if too_long(n):
+                print("matcher: %s has %d segments; --dense answers queries of at most %d: error row" % (dataset.files[i], n, DENSE_MAX_SEGMENTS),
+                      file=sys.stderr)
         ps = []
         if good:
             emb = torch.cat([e for _, _, e in good])
             qlen = [n for _, n, _ in good]
             qstart = np.concatenate([[0], np.cumsum(qlen)[:-1]])
-            if top_n and no_bin:                 # search + top-N match: no per-song block, so nothing to cut into chunks
+            if dense:
+                ps = db.query_dense_launch_chunks(emb, qstart, qlen, max(top_n, 1), want_song_scores=not no_bin)
+            elif top_n and no_bin:                 # search + top-N match: no per-song block, so nothing to cut into chunks
                 ps = [(0, len(good), db.query_topn_launch(emb, qstart, qlen, top_n))]
             else:
                 ps = db.query_launch_chunks(emb, qstart, qlen, want_song_scores=not no_bin)
@@ -231,7 +255,11 @@ def main(argv=None):
         it = iter(items)
         for j0, j1, p in ps:
             results = {}
-            if top_n and no_bin:
+            if dense:
+                answers, ranked = db.query_dense_finish(p, reuse_buffers=True)
+                for (i, _, _), r, rows in zip(good[j0:j1], answers, ranked):
+                    results[i] = r + (rows if top_n else None,)
+            elif top_n and no_bin:
                 for (i, _, _), rows in zip(good[j0:j1], db.query_topn_finish(p)):
                     results[i] = rows[0] + (None, rows)
             else:
@@ -256,7 +284,7 @@ def main(argv=None):
 
     def write_one(i, n, results):
         name = dataset.files[i]
-        if n == 0:                                                        # matcher.py:94-107
+        if n == 0 or too_long(n):                                         # matcher.py:94-107
             out.write_error(name, qi=i)
         else:
             sco, (sid, tim), song_score, rows = results[i]

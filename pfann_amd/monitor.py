@@ -20,7 +20,9 @@ both files exactly as described above.
 
 `--dense` answers every window with the dense matcher (pfann_match_windows_dense, csrc/dense.hip): no search, EVERY alignment
 of every song is a candidate of every window, so the answers do not depend on the indexer's top_k.  Same files, same
-columns; windows of at most 64 segments; not together with `--top N` > 1.
+columns; windows of at most 64 segments; not together with `--top N` > 1 here: ranked dense answers exist
+(pfann_match_windows_dense_topn, Database.monitor_dense_topn_launch / monitor_dense_topn_finish), this tool does not route
+`--dense --top N` to them yet.
 """
 import argparse
 import csv

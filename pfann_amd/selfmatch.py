@@ -1,6 +1,6 @@
 """Self-match: ask a database about itself -- which entries are the same recording under two names, which song contains a
 stretch of another.
-    python selfmatch.py <db dir> <result.tsv> [--window N] [--hop N] [--min-score X] [--min-windows N] [--max-gap N] [--songs A:B] [--topk K] [--dense]
+    python selfmatch.py <db dir> <result.tsv> [--window N] [--hop N] [--min-score X] [--min-windows N] [--max-gap N] [--songs A:B] [--topk K] [--dense] [--top N]
 
 Needs no model and no audio: it reads configs.json, songList.txt, landmarkKey and embeddings of a directory written by
 builder.py.  Every song's own fingerprints are the recording: each row is searched with its own song's rows left out
@@ -15,13 +15,19 @@ monitor writes it (song A in the recording column).  A duplicate pair appears tw
 intended -- nothing is de-duplicated.  A partial containment appears from the contained side and, where the windows fit
 into the shared stretch, from the container's side.  --songs A:B limits the songs QUERIED, not the songs searched.
 --dense: no search; the dense matcher (pfann_match_windows_dense) scores every alignment of every other song in every window
-(the song's own alignments are excluded), so nothing depends on --topk.  Same files, same columns; windows of at most 64 rows."""
+(the song's own alignments are excluded), so nothing depends on --topk.  Same files, same columns; windows of at most 64 rows.
+--top N (1..64; 1 is the default and writes both files exactly as described above): the N best OTHER songs of every window
+(pfann_match_windows_dense_topn with --dense, pfann_match_windows_topn on the masked search's labels without), every (song,
+diagonal) track merged by itself with monitor.merge_window_tracks, as monitor.py --top does -- a stretch stored three times
+is then reported against BOTH other copies.  The detections file gets the ninth column best_rank, the windows file one row
+per (window, rank) with the columns rank and votes."""
 import argparse
 import csv
 import os
 import sys
 
-from .monitor import DEFAULT_HOP, DEFAULT_MIN_SCORE, DEFAULT_MIN_WINDOWS, default_window, merge_windows
+from .monitor import (DEFAULT_HOP, DEFAULT_MIN_SCORE, DEFAULT_MIN_WINDOWS, WINDOWS_HEADER, default_window, merge_window_tracks,
+                      merge_windows, ranked_window_csv)
 
 
 def parse_songs(text, n_songs):
@@ -52,6 +58,9 @@ def parse_args(argv):
     ap.add_argument("--topk", type=int, default=None, help="neighbours per row (default: the indexer's top_k)")
     ap.add_argument("--dense", action="store_true",
                     help="score every alignment of every other song in every window instead of the nominated ones (window <= 64)")
+    ap.add_argument("--top", type=int, default=1,
+                    help="other songs ranked per window (1..64, default 1); above 1 every (song, diagonal) is merged by itself "
+                         "and both files get the extra columns of monitor.py --top")
     return ap.parse_args(argv[1:])
 
 
@@ -72,11 +81,24 @@ def write_song(fout, wcsv, name_a, rows, song_list, window, hop, seg_step_s, min
     return len(rows), len(dets)
 
 
+def write_song_ranked(fout, wcsv, name_a, rows, song_list, window, hop, seg_step_s, min_score, max_gap, min_windows):
+    """write_song for the ranked [windows, n] rows of --top N > 1: one CSV row per (window, rank), every (song, diagonal)
+    track merged by itself, detection lines with the ninth column best_rank"""
+    wcsv.writerows(ranked_window_csv(name_a, rows, seg_step_s, song_list))
+    dets = merge_window_tracks(rows, window, hop, seg_step_s, min_score, max_gap, min_windows=min_windows)
+    for det in dets:
+        fout.write(detection_line(name_a, det[:7], song_list) + "\t%d\n" % det[7])
+    return len(rows), len(dets)
+
+
 def main(argv=None):
     argv = sys.argv if argv is None else argv
     args = parse_args(argv)
     if args.hop < 1 or (args.window is not None and args.window < 1) or (args.topk is not None and not 1 <= args.topk <= 1024):
         print("selfmatch: --window and --hop are positive numbers of rows, --topk is 1..1024", file=sys.stderr)
+        return 2
+    if not 1 <= args.top <= 64:
+        print("selfmatch: --top ranks 1..64 songs per window", file=sys.stderr)
         return 2
     if args.dense and args.window is not None and args.window > 64:
         print("selfmatch: --dense takes windows of at most 64 rows", file=sys.stderr)
@@ -99,10 +121,11 @@ def main(argv=None):
     with open(args.result, "w", encoding="utf8", newline="\n") as fout, \
             open(stem + "_windows.csv", "w", encoding="utf8", newline="\n") as fwin:
         wcsv = csv.writer(fwin)
-        wcsv.writerow(["recording", "w0", "start_s", "song", "score", "time"])
-        for s, rows in db.self_match(song_lo, song_hi, window, args.hop, args.topk, dense=args.dense):
+        wcsv.writerow(WINDOWS_HEADER + (["rank", "votes"] if args.top > 1 else []))
+        write = write_song_ranked if args.top > 1 else write_song
+        for s, rows in db.self_match(song_lo, song_hi, window, args.hop, args.topk, dense=args.dense, top=args.top):
             n_song = int(db.song_pos[s + 1] - db.song_pos[s])
-            nw, nd = write_song(fout, wcsv, db.songList[s], rows, db.songList, min(window, n_song) if n_song else window, args.hop,
+            nw, nd = write(fout, wcsv, db.songList[s], rows, db.songList, min(window, n_song) if n_song else window, args.hop,
                                 seg_step_s, args.min_score, args.max_gap, args.min_windows)
             n_windows += nw
             n_det += nd
