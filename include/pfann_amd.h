@@ -20,6 +20,7 @@
  *   pfann_search_topk       database.py:121  index.search(query, top_k)  (exact flat IP)
  *   pfann_match             database.py:117-166 query_embeddings_base (search + rerank)
  *   pfann_match_windows_dense  database.py:129-163 with every row's label list = the whole database (no counterpart)
+ *   pfann_match_windows_dense_stats  the same answer, and the moments of every window's full candidates (no counterpart)
  *   pfann_match_windows_dense_topn  the same candidates, the n best songs per window and the per-song block (no counterpart)
  */
 #ifndef PFANN_AMD_H
@@ -217,7 +218,8 @@ int pfann_db_load(pfann_db *db, const float *emb, int emb_is_device, int64_t n,
 /* ---- Database updates: songs are added to and taken out of a loaded handle without a reload.
  *
  * State contract.  After a successful pfann_db_append or pfann_db_remove_songs the handle answers EVERY later call --
- * search, masked search, both sharded halves, pfann_match*, the windowed, ranked and dense matchers, seq_score, the
+ * search, masked search, both sharded halves, pfann_match*, the windowed, ranked and dense matchers (the dense statistics of
+ * pfann_match_windows_dense_stats among them), seq_score, the
  * pfann_search_plan text, pfann_db_ntotal / _bytes / _owned_songs / _row_norm_max -- exactly, bit for bit, as a fresh
  * handle of the same storage mode and pre-filter setting that was pfann_db_load-ed with the resulting rows and song_pos.
  * After a failed call (< 0) the handle is unchanged: arguments are validated before anything is touched, and what has to
@@ -494,6 +496,37 @@ int pfann_match_windows_dense(pfann_db *db, const float *q_dev,
                               int window, int hop, const int64_t *wfirst_dev, int64_t n_windows,
                               const int32_t *excl_song_dev /* [nR] or NULL */,
                               pfann_match_result *results_dev, void *stream);
+
+/* Dense matcher with background statistics: pfann_match_windows_dense's answer, and per window the first two moments of the
+ * totals of its FULL candidates, from the same pass over the database (csrc/dense.hip).  Arguments, the window rule, short and
+ * empty recordings, excl_song_dev and the asynchrony follow pfann_match_windows_dense; results_dev[n_windows] gets, byte for
+ * byte, what that call writes for the same arguments; stats_dev[n_windows] gets, for a window of n rows,
+ *   n_full    the candidates whose n rows all lie inside their song, 0 <= o <= len_s - n: the sum over the songs s other than
+ *             the recording's excluded song with len_s >= n of (len_s - n + 1).  Candidates that hang over a song's edge, and
+ *             every candidate of a song shorter than n, have fewer rows in their total and enter no sum (their numbers per
+ *             overlap length follow from the song lengths alone: pfann_amd/significance.py);
+ *   sum_q     the sum over those candidates of rint((double)total * 2^PFANN_DENSE_STATS_SUM_SHIFT);
+ *   sumsq_q   the sum over those candidates of rint((double)total * (double)total * 2^PFANN_DENSE_STATS_SQ_SHIFT);
+ * total = the fp32 total of pfann_match_windows_dense (SUMMATION ORDER there); both products are exact in double, so rint is
+ * the only rounding, and the sums are 64-bit integer additions (wave shuffles, LDS, one 64-bit atomicAdd per non-zero entry
+ * of a (window, tile)).  mean = sum_q / 2^24 / n_full, mean square = sumsq_q / 2^18 / n_full.
+ * BYTE CONTRACT: integer addition is associative, so a window's 24 stats bytes, like its 24 result bytes, are a function of the
+ * window's rows, the database and its recording's excluded song alone -- not of hop, the other windows or recordings of the
+ * call, the tiling or the run.
+ * RANGE: with unit-norm rows |total| <= 64, so a candidate adds at most 2^30 to either sum in magnitude, and with fewer than
+ * 2^32 candidates neither sum can wrap.  Outside that range the sums wrap in two's complement, deterministically.
+ * The call zeroes stats_dev with hipMemsetAsync on `stream`; no read-back, no host synchronisation, no allocation.
+ * Returns -1 with a message, launches nothing and writes nothing, when stats_dev is NULL and in every case in which
+ * pfann_match_windows_dense does.  After pfann_db_append / pfann_db_remove_songs the call answers as a fresh handle would. */
+#define PFANN_DENSE_STATS_SUM_SHIFT 24
+#define PFANN_DENSE_STATS_SQ_SHIFT  18
+typedef struct { int64_t n_full, sum_q, sumsq_q; } pfann_dense_stats;
+int pfann_match_windows_dense_stats(pfann_db *db, const float *q_dev,
+                                    const int64_t *rstart_dev, const int32_t *rlen_dev, int64_t nR,
+                                    int window, int hop, const int64_t *wfirst_dev, int64_t n_windows,
+                                    const int32_t *excl_song_dev /* [nR] or NULL */,
+                                    pfann_match_result *results_dev,
+                                    pfann_dense_stats *stats_dev /* [n_windows] */, void *stream);
 
 /* Dense matcher, ranked: the n best SONGS of every window over every alignment, 1 <= n <= 64 (csrc/dense.hip).  Recordings,
  * windows, wfirst_dev, n_windows, short and empty recordings and excl_song_dev follow pfann_match_windows_dense.

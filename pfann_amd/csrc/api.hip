@@ -1296,9 +1296,10 @@ int pfann_match_windows(pfann_db *db, const float *q, const int64_t *labels, int
     return 0;
 }
 
-int pfann_match_windows_dense(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
-                              int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
-                              pfann_match_result *results, void *stream) {
+// pfann_match_windows_dense (stats == nullptr) and pfann_match_windows_dense_stats: one set of refusals, `what` names the call
+static int match_windows_dense_impl(const char *what, pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen,
+                                    int64_t nR, int window, int hop, const int64_t *wfirst, int64_t n_windows,
+                                    const int32_t *excl_song, pfann_match_result *results, pfann_dense_stats *stats, void *stream) {
     PF_HIP(hipSetDevice(db->device));
     if (db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
         db->song_pos_h.empty() || db->song_pos_h.back() != db->n) {
@@ -1306,27 +1307,43 @@ int pfann_match_windows_dense(pfann_db *db, const float *q, const int64_t *rstar
         return -1;
     }
     if (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr)) {
-        set_error("match_windows_dense: fp16-only storage (the dense matcher scores fp32 rows)");
+        set_error("%s: fp16-only storage (the dense matcher scores fp32 rows)", what);
         return -1;
     }
-    if (db->d % 4 != 0) { set_error("match_windows_dense: d %% 4 != 0 (d=%d)", db->d); return -1; }
+    if (db->d % 4 != 0) { set_error("%s: d %% 4 != 0 (d=%d)", what, db->d); return -1; }
     if (window < 1 || window > 64 || hop < 1 || nR < 0 || n_windows < 0) {
-        set_error("match_windows_dense: window=%d (1..64) hop=%d nR=%lld n_windows=%lld", window, hop, (long long)nR, (long long)n_windows);
+        set_error("%s: window=%d (1..64) hop=%d nR=%lld n_windows=%lld", what, window, hop, (long long)nR, (long long)n_windows);
         return -1;
     }
     if (db->n + (int64_t)db->n_songs * (window - 1) >= (1ll << 32)) {
-        set_error("match_windows_dense: %lld rows and %d songs at window %d do not fit the 32-bit alignment id", (long long)db->n,
+        set_error("%s: %lld rows and %d songs at window %d do not fit the 32-bit alignment id", what, (long long)db->n,
                   db->n_songs, window);
         return -1;
     }
     if (nR == 0 || n_windows == 0) return 0;
     int64_t with_rows = 0;
     for (int s = 0; s < db->n_songs; ++s) with_rows += db->song_pos_h[s + 1] > db->song_pos_h[s];
-    DenseArgs a;
+    DenseStatsArgs a;
     a.db = db->emb; a.ntotal = db->n; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
     a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
-    a.nW = n_windows; a.excl = excl_song; a.results = results;
+    a.nW = n_windows; a.excl = excl_song; a.results = results; a.stats = stats;
+    if (stats != nullptr) return launch_match_windows_dense_stats(a, with_rows, (hipStream_t)stream);
     return launch_match_windows_dense(a, with_rows, (hipStream_t)stream);
+}
+
+int pfann_match_windows_dense(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
+                              int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
+                              pfann_match_result *results, void *stream) {
+    return match_windows_dense_impl("match_windows_dense", db, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song, results,
+                                    nullptr, stream);
+}
+
+int pfann_match_windows_dense_stats(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
+                                    int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
+                                    pfann_match_result *results, pfann_dense_stats *stats, void *stream) {
+    if (stats == nullptr) { set_error("match_windows_dense_stats: stats_dev is null"); return -1; }
+    return match_windows_dense_impl("match_windows_dense_stats", db, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song,
+                                    results, stats, stream);
 }
 
 int pfann_match_windows_dense_topn(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,

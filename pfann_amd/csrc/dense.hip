@@ -59,14 +59,26 @@ __device__ __forceinline__ int dn_windows_of(int L, int window, int hop) {
 // RANKED (pfann_match_windows_dense_topn): the same tiles over the row-tile slots of one chunk; the pieces of a window start
 // are reduced per SONG inside the tile -- s_best is then one table per half of the workgroup, indexed by the song's first
 // column in the tile (s_head) -- and every non-empty entry goes out with one atomicMax into ws[window of the chunk][song].
-template <bool RANKED>
-__global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(typename std::conditional<RANKED, DenseTopnArgs, DenseArgs>::type a) {
+//
+// STATS (pfann_match_windows_dense_stats, unranked only): beside the maximum, the first two moments of the window's FULL pieces --
+// stretches that no song boundary cuts, of a song that is not the excluded one: the candidates 0 <= o <= len_s - n.  A piece
+// with fp32 total tot adds the integers 1, rint((double)tot * 2^24) and rint((double)tot * (double)tot * 2^18); both products
+// are exact in double, so the rounding is the only rounding, and everything after it -- wave shuffles, one LDS entry per
+// window start, one global 64-bit atomicAdd per non-zero entry -- is integer addition: the three sums of a window are, like
+// its result bytes, a function of its rows, the database and the excluded song alone.
+template <bool RANKED, bool STATS = false>
+__global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(
+        typename std::conditional<RANKED, DenseTopnArgs, typename std::conditional<STATS, DenseStatsArgs, DenseArgs>::type>::type a) {
+    static_assert(!(RANKED && STATS), "the moments are kept by the unranked form");
     // S[DN_T][DN_LDS]; while the product runs its first bytes are the two K tiles As, Bs [DN_T][DN_LDK]
     extern __shared__ __attribute__((aligned(16))) float s_S[];          // DN_S_BYTES, dynamic: past the static 64 KB
     __shared__ long long s_cpos[1024];
     __shared__ int s_song[DN_T];
     __shared__ int s_head[RANKED ? DN_T : 1];
     __shared__ unsigned long long s_best[RANKED ? 2 * DN_T : DN_T];
+    // per window start of the tile: sum_q, sumsq_q and the number of full pieces (at most DN_T: 20 bytes per start)
+    __shared__ unsigned long long s_sum[STATS ? 2 * DN_T : 1];
+    __shared__ int s_full[STATS ? DN_T : 1];
     static_assert(2 * DN_T * DN_LDK <= DN_T * DN_LDS, "the K tiles fit under S");
     float *As = s_S, *Bs = s_S + DN_T * DN_LDK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -107,6 +119,7 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(typename std
                 s_head[tid] = sg >= 0 ? (int)max((int64_t)0, a.song_pos[sg] - J0) : tid;
                 s_best[DN_T + tid] = 0;
             }
+            if constexpr (STATS) { s_sum[2 * tid] = 0; s_sum[2 * tid + 1] = 0; s_full[tid] = 0; }
         }
 
         // ---- S = Q tile x db tile^T.  Thread tid stages rows (tid >> 2) and (tid >> 2) + 64 of both operands, eight
@@ -261,8 +274,11 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(typename std
                     const int w0 = i0 + i;
                     if (w0 % a.hop != 0 || w0 / a.hop >= nw) continue;       // not a window start of this recording
                     unsigned long long best = 0;
+                    [[maybe_unused]] int full = 0;                           // STATS: this thread's stretch is a full piece
+                    [[maybe_unused]] long long sum = 0, sumsq = 0;
                     if (j < SI) {
                         int cur = s_song[j];
+                        [[maybe_unused]] bool cut = false;
                         float tot = 0.f;
                         for (int t = 0; t < wl; ++t) {
                             const int sg = s_song[j + t];
@@ -274,6 +290,7 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(typename std
                                 }
                                 cur = sg;
                                 tot = 0.f;
+                                if constexpr (STATS) cut = true;
                             }
                             tot += s_S[(i + t) * DN_LDS + j + t];
                         }
@@ -281,14 +298,34 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(typename std
                             const unsigned id = (unsigned)(g + (int64_t)(cur + 1) * (wl - 1));
                             const unsigned long long x = ((unsigned long long)dn_ordered_bits(tot) << 32) | (0xFFFFFFFFu - id);
                             best = x > best ? x : best;
+                            if constexpr (STATS) {
+                                if (!cut) {
+                                    const double td = (double)tot;
+                                    full = 1;
+                                    sum = __double2ll_rn(td * 16777216.0);           // 2^PFANN_DENSE_STATS_SUM_SHIFT
+                                    sumsq = __double2ll_rn(td * td * 262144.0);      // 2^PFANN_DENSE_STATS_SQ_SHIFT
+                                }
+                            }
                         }
                     }
 #pragma unroll
                     for (int o = 32; o > 0; o >>= 1) {
                         const unsigned long long v = __shfl_xor(best, o, 64);
                         best = v > best ? v : best;
+                        if constexpr (STATS) {
+                            full += __shfl_xor(full, o, 64);
+                            sum += __shfl_xor(sum, o, 64);
+                            sumsq += __shfl_xor(sumsq, o, 64);
+                        }
                     }
                     if (lane == 0 && best != 0) atomicMax(&s_best[i], best);
+                    if constexpr (STATS) {
+                        if (lane == 0 && full != 0) {
+                            atomicAdd(&s_full[i], full);
+                            atomicAdd(&s_sum[2 * i], (unsigned long long)sum);
+                            atomicAdd(&s_sum[2 * i + 1], (unsigned long long)sumsq);
+                        }
+                    }
                 }
             }
             __syncthreads();
@@ -297,6 +334,15 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(typename std
                 if (x != 0) {                                // (only window starts of the recording ever get a word)
                     const int64_t w = wf + (i0 + tid) / a.hop;
                     atomicMax(reinterpret_cast<unsigned long long *>(&a.results[w].score), x);
+                    if constexpr (STATS) {
+                        const int nf = s_full[tid];
+                        if (nf != 0) {                       // (a full piece is a candidate: x != 0 wherever there is one)
+                            unsigned long long *st = reinterpret_cast<unsigned long long *>(&a.stats[w]);
+                            atomicAdd(&st[0], (unsigned long long)nf);
+                            if (s_sum[2 * tid] != 0) atomicAdd(&st[1], s_sum[2 * tid]);
+                            if (s_sum[2 * tid + 1] != 0) atomicAdd(&st[2], s_sum[2 * tid + 1]);
+                        }
+                    }
                 }
             }
         }
@@ -341,24 +387,36 @@ __global__ void dense_decode_kernel(DenseArgs a, int64_t songs_with_rows) {
     a.results[w] = res;
 }
 
-int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipStream_t s) {
+// the unranked tile kernel, with or without the moments, and the decode; Args = what that instantiation takes
+template <bool STATS, class Args>
+static int launch_dense_tiles(const Args &a, int64_t songs_with_rows, const char *tag, hipStream_t s) {
     if (a.nR <= 0 || a.nW <= 0) return 0;
     // every slot's running best starts empty (word 0: no number has the ordered bits 0)
     PF_HIP(hipMemsetAsync(a.results, 0, (size_t)a.nW * sizeof(pfann_match_result), s));
+    if constexpr (STATS) PF_HIP(hipMemsetAsync(a.stats, 0, (size_t)a.nW * sizeof(pfann_dense_stats), s));
     if (a.ntotal > 0) {
         const int SI = DN_T - (a.window - 1);
         const int64_t n_slots = a.nW * a.hop / SI + a.nR;
         const int64_t NJ = (a.ntotal + a.window - 1 + SI - 1) / SI;
         const int64_t n_items = n_slots * NJ;
         const double rows = (double)a.nW * a.hop + (double)a.nR * a.window;
-        if (ensure_dyn_lds((const void *)match_windows_dense_kernel<false>, DN_S_BYTES)) return -1;
-        ProfScope ps("seq_match_windows_dense", s, 2.0 * rows * (double)a.ntotal * a.d);
-        PF_LAUNCH(match_windows_dense_kernel<false>, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
+        const auto kernel = match_windows_dense_kernel<false, STATS>;
+        if (ensure_dyn_lds((const void *)kernel, DN_S_BYTES)) return -1;
+        ProfScope ps(tag, s, 2.0 * rows * (double)a.ntotal * a.d);
+        PF_LAUNCH(kernel, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
         PF_HIP(hipGetLastError());
     }
-    PF_LAUNCH(dense_decode_kernel, dim3((unsigned)cdiv(a.nW, 256)), dim3(256), 0, s, a, songs_with_rows);
+    PF_LAUNCH(dense_decode_kernel, dim3((unsigned)cdiv(a.nW, 256)), dim3(256), 0, s, static_cast<const DenseArgs &>(a), songs_with_rows);
     PF_HIP(hipGetLastError());
     return 0;
+}
+
+int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipStream_t s) {
+    return launch_dense_tiles<false>(a, songs_with_rows, "seq_match_windows_dense", s);
+}
+
+int launch_match_windows_dense_stats(const DenseStatsArgs &a, int64_t songs_with_rows, hipStream_t s) {
+    return launch_dense_tiles<true>(a, songs_with_rows, "seq_match_windows_dense_stats", s);
 }
 
 // ---- ranked: ws -> the n best songs of every window of the chunk (pfann_match_windows_dense_topn) --------------------------

@@ -174,6 +174,11 @@ struct DenseArgs {
 };
 // songs_with_rows: songs of the database with len > 0 (n_cand)
 int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipStream_t s);
+// pfann_match_windows_dense_stats: the same answer, and per window the count and the two fixed-point sums of its full pieces
+struct DenseStatsArgs : DenseArgs {
+    pfann_dense_stats *stats;   // [nW], zeroed by the launcher
+};
+int launch_match_windows_dense_stats(const DenseStatsArgs &a, int64_t songs_with_rows, hipStream_t s);
 // pfann_match_windows_dense_topn: one chunk of row-tile slots [slot_lo, slot_lo + slot_n) of the call (results unused).  The
 // tile kernel leaves every song's best packed word of every window of the chunk in ws, the select kernel ranks them.
 struct DenseTopnArgs : DenseArgs {

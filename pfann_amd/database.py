@@ -458,6 +458,45 @@ class DeviceIndex:
                                                         res.data_ptr(), self._stream()), "pfann_match_windows_dense")
         return (self.results_to_host(res) if to_host else res), wfirst
 
+    def match_windows_dense_stats(self, q, rstart, rlen, window, hop, exclude_song=None, to_host=True):
+        """match_windows_dense with the background statistics of every window (pfann_match_windows_dense_stats): the count and
+        the two fixed-point sums of the totals of its full candidates, significance.STATS_DTYPE, from the same pass.
+        -> ((results, stats), wfirst): results byte for byte match_windows_dense's; with to_host=False the device tensors
+        (uint8 [nW, 24], int64 [nW, 3])."""
+        window, hop = int(window), int(hop)
+        if window < 1 or hop < 1:
+            raise ValueError("match_windows_dense_stats: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
+        q = q.to(self.device, torch.float32).contiguous()
+        rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
+        nR = int(rl_np.shape[0])
+        assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
+        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
+        nW = int(wfirst[-1])
+        res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        stats = torch.empty((nW, 3), device=self.device, dtype=torch.int64)
+        ex = None
+        if exclude_song is not None:
+            ex_np = np.ascontiguousarray(exclude_song, dtype=np.int32)
+            if ex_np.shape != (nR,):
+                raise ValueError("match_windows_dense_stats: exclude_song wants one song id per recording (%d), got %r" % (nR, ex_np.shape))
+            ex = _l.upload_async(ex_np, self.device, np.int32)
+        if nW:
+            rs, rl = self._upload_ranges(rs_np, rl_np)
+            wf = _l.upload_async(wfirst, self.device, np.int64)
+            _l.check(self.lib.pfann_match_windows_dense_stats(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
+                                                              wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
+                                                              res.data_ptr(), stats.data_ptr(), self._stream()),
+                     "pfann_match_windows_dense_stats")
+        if not to_host:
+            return (res, stats), wfirst
+        return (self.results_to_host(res), self.stats_to_host(stats)), wfirst
+
+    @staticmethod
+    def stats_to_host(stats_dev):
+        """device statistics (int64 [nW, 3]) -> significance.STATS_DTYPE array"""
+        from .significance import STATS_DTYPE
+        return np.ascontiguousarray(stats_dev.cpu().numpy()).view(STATS_DTYPE).reshape(-1)
+
     def match_windows_dense_topn(self, q, rstart, rlen, window, hop, n, exclude_song=None, want_song_scores=False, to_host=True):
         """Ranked dense answers (pfann_match_windows_dense_topn): the n best songs of every window over EVERY alignment, and
         with want_song_scores the per-song block [nW, n_songs, 2] of (float32 score, best offset in frames; zeros where the
@@ -938,16 +977,42 @@ class Database:
         ev[2].record()
         return dict(out, ev=ev, keep=(emb, None), mode=0)
 
-    def monitor_dense_launch(self, emb, rstart, rlen, window, hop, edge_window=0):
+    def monitor_dense_launch(self, emb, rstart, rlen, window, hop, edge_window=0, stats=False):
         """monitor_launch on the dense matcher (pfann_match_windows_dense): no search, every alignment of every song is a
-        candidate of every window (and of every short window of the edge pass).  -> what monitor_finish reads."""
+        candidate of every window (and of every short window of the edge pass).  -> what monitor_finish reads.
+        stats=True: the long windows go through pfann_match_windows_dense_stats and the launch carries their background
+        statistics for monitor_dense_stats_finish; the edge pass stays as it is (its rows only place edges)."""
         self._dense_check("monitor_dense_launch")
 
         def match():
             windows = lambda w, h: self.index.match_windows_dense(emb, rstart, rlen, w, h, to_host=False)
-            res, wfirst = windows(window, hop)
-            return {"res": res, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None, "hop": int(hop)}
+            out = {}
+            if stats:
+                (res, out["stats"]), wfirst = self.index.match_windows_dense_stats(emb, rstart, rlen, window, hop, to_host=False)
+                out["rows_of"] = (int(window), np.asarray(rlen, dtype=np.int64))
+            else:
+                res, wfirst = windows(window, hop)
+            return dict(out, res=res, wfirst=wfirst, fine=windows(edge_window, 1) if edge_window > 0 else None, hop=int(hop))
         return self._launch_dense(emb, match)
+
+    def monitor_dense_stats_finish(self, p):
+        """Second half of monitor_dense_launch(stats=True): -> (what monitor_finish returns, per recording a float64 array
+        log10_fa aligned with its rows): log10 of the chance that the best of the window's candidates reaches its score when
+        the window holds nothing of the database, from the window's own background (pfann_amd/significance.py); 0 where that
+        cannot be said."""
+        from . import significance as sg
+        raw = self._read_back(p)[0]                      # (the statistics are complete behind the same event)
+        stats = self.index.stats_to_host(p["stats"])
+        window, rlen = p["rows_of"]
+        wfirst, fsm = p["wfirst"], self.frame_shift_mul
+        rows = monitor_rows(raw, wfirst, p["hop"], p["mode"], fsm, self.hop_size)
+        self._edge_finish(p, fsm)
+        song_len = np.diff(self.song_pos)
+        if getattr(self, "_overlap_hists", None) is None or not np.array_equal(self._overlap_hists.song_len, song_len):
+            self._overlap_hists = sg.OverlapHistograms(song_len)
+        fa = [sg.log10_false_alarms(raw[a:b], stats[a:b], min(window, int(L)), -1, self._overlap_hists, song_len)
+              for a, b, L in zip(wfirst[:-1], wfirst[1:], rlen)]
+        return rows, fa
 
     def monitor_dense_topn_launch(self, emb, rstart, rlen, window, hop, n, edge_window=0):
         """monitor_topn_launch on the ranked dense matcher (pfann_match_windows_dense_topn): no search, the n best songs of every
@@ -1024,11 +1089,14 @@ class Database:
 
     def _windows_finish(self, p, fsm):
         out = monitor_rows(self._read_back(p)[0], p["wfirst"], p["hop"], p["mode"], fsm, self.hop_size)
+        self._edge_finish(p, fsm)
+        return out
+
+    def _edge_finish(self, p, fsm):
         if p.get("fine") is not None:                    # (complete behind the same event; the timer has its split already)
             edge, efirst = p["fine"]
             edge = self._read_back({"res": edge, "ev": p["ev"][-1:]})[0]
             p["edge_rows"] = monitor_rows(edge, efirst, 1, p["mode"], fsm, self.hop_size)
-        return out
 
     def monitor_topn_launch(self, emb, rstart, rlen, window, hop, n, edge_window=0):
         """monitor_launch with ranked answers (pfann_match_windows_topn): the n best songs of every window, and of every

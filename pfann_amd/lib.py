@@ -95,6 +95,8 @@ SYMBOLS = {
                                          c_float, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "pfann_match_windows_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
                                           c_void_p, c_void_p, c_void_p]),
+    "pfann_match_windows_dense_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
+                                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "pfann_match_windows_dense_topn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
                                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pfann_db_owned_songs": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),

@@ -1,5 +1,5 @@
 """Monitor mode: go through long recordings and say what played when.
-    python monitor.py <recording list> <database dir> <result file> [--window N] [--hop N] [--min-score X] [--max-gap N] [--min-windows N] [--edge-window N] [--top N] [--dense]
+    python monitor.py <recording list> <database dir> <result file> [--window N] [--hop N] [--min-score X] [--max-gap N] [--min-windows N] [--edge-window N] [--top N] [--dense] [--max-fa X]
 
 Every recording is embedded once, all its rows are searched once, and the windowed sequence matcher
 (pfann_match_windows, csrc/monitor.hip) answers every window of `--window` segments, `--hop` segments apart, exactly as
@@ -23,9 +23,17 @@ of every song is a candidate of every window, so the answers do not depend on th
 columns; windows of at most 64 segments; not together with `--top N` > 1 here: ranked dense answers exist
 (pfann_match_windows_dense_topn, Database.monitor_dense_topn_launch / monitor_dense_topn_finish), this tool does not route
 `--dense --top N` to them yet.
+
+`--max-fa X` (with `--dense`, 0 < X <= 1) replaces the fixed `--min-score` by a threshold calibrated per window: the dense
+matcher also returns the mean and the variance of the window's other alignments (pfann_match_windows_dense_stats), and
+pfann_amd/significance.py turns the best score into log10_fa, log10 of the chance that the best of that many chance alignments
+scores as high.  A window then counts when it names a song and log10_fa <= log10(X); `--min-score` is not consulted.  The
+windows file gets a seventh column, log10_fa, and the detections file a ninth, min_log10_fa: the most significant member
+window.  What score chance reaches depends on the window length, the size of the database and the model; X does not.
 """
 import argparse
 import csv
+import math
 import os
 import sys
 
@@ -51,7 +59,7 @@ def default_window(params):
 
 
 def merge_windows(rows, window, hop, hop_size, min_score=DEFAULT_MIN_SCORE, max_gap=0, refine=True, min_windows=1, edge_rows=None,
-                  edge_window=0):
+                  edge_window=0, good=None):
     """Per-window answers of ONE recording -> detections.  Pure host code.
 
     rows: sequence of (w0, score, song, time_s) in ascending w0 (Database.monitor_finish), w0 = first segment of the window,
@@ -71,25 +79,31 @@ def merge_windows(rows, window, hop, hop_size, min_score=DEFAULT_MIN_SCORE, max_
     asks for DEFAULT_MIN_WINDOWS).
     refine: a window that only partly overlaps the song scores about that part of the full score (the other rows add ~0),
     so the first / last window of a run place the edges at w0 + window * (1 - s / best) and w0 + window * s / best instead
-    of at the windows' own edges; the start is also clipped to where the song begins."""
-    return [det for det, _ in _merge_runs(rows, window, hop, hop_size, min_score, max_gap, refine, min_windows, edge_rows, edge_window)]
+    of at the windows' own edges; the start is also clipped to where the song begins.
+    good: one truth value per row that replaces the test score >= min_score (a window still has to name a song)."""
+    return [det for det, _, _ in _merge_runs(rows, window, hop, hop_size, min_score, max_gap, refine, min_windows, edge_rows, edge_window,
+                                             good)]
 
 
-def _merge_runs(rows, window, hop, hop_size, min_score, max_gap, refine, min_windows, edge_rows, edge_window):
-    """merge_windows' work -> [(detection, (first, last))]: the detection and the rows[] range its run spans"""
+def _merge_runs(rows, window, hop, hop_size, min_score, max_gap, refine, min_windows, edge_rows, edge_window, good=None):
+    """merge_windows' work -> [(detection, (first, last), members)]: the detection, the rows[] range its run spans and the
+    indices of its member windows"""
     del hop                                              # (the spacing is in the w0 column; kept for the call's symmetry)
     tol = 1e-3 * hop_size
     tab = [(int(w0), float(score), int(song), float(time_s)) for w0, score, song, time_s in rows]
+    passes = [score >= min_score for _, score, _, _ in tab] if good is None else [bool(g) for g in good]
+    assert len(passes) == len(tab), "good wants one value per row"
     runs, cur, i = [], None, 0
     while i < len(tab):
         w0, score, song, time_s = tab[i]
         diag = time_s - w0 * hop_size
-        good = song >= 0 and score >= min_score
+        ok = song >= 0 and passes[i]
         if cur is None:
-            if good:
-                cur = {"song": song, "diag": diag, "w": [(w0, score)], "first": i, "last": i}
-        elif good and song == cur["song"] and abs(diag - cur["diag"]) <= tol:
+            if ok:
+                cur = {"song": song, "diag": diag, "w": [(w0, score)], "idx": [i], "first": i, "last": i}
+        elif ok and song == cur["song"] and abs(diag - cur["diag"]) <= tol:
             cur["w"].append((w0, score))
+            cur["idx"].append(i)
             cur["last"] = i
         elif i - cur["last"] > max_gap:
             # too many disagreeing windows: the run ended at its last member, and what follows it starts over
@@ -122,7 +136,7 @@ def _merge_runs(rows, window, hop, hop_size, min_score, max_gap, refine, min_win
         start_s, end_s = lo * hop_size, hi * hop_size
         start_s = max(start_s, -run["diag"])             # the song cannot have begun before its first second
         det = (start_s, end_s, run["song"], run["diag"] + start_s, float(sc.mean()), best, run["last"] - run["first"] + 1)
-        out.append((det, (run["first"], run["last"])))
+        out.append((det, (run["first"], run["last"]), run["idx"]))
     return out
 
 
@@ -178,7 +192,7 @@ def merge_window_tracks(ranked_rows, window, hop, hop_size, min_score=DEFAULT_MI
     for song, diag in tracks:
         seq, rank = restrict(tab, song, diag)
         eseq = restrict(edge, song, diag)[0] if edge is not None else None
-        for det, (first, last) in _merge_runs(seq, window, hop, hop_size, min_score, max_gap, refine, min_windows, eseq, edge_window):
+        for det, (first, last), _ in _merge_runs(seq, window, hop, hop_size, min_score, max_gap, refine, min_windows, eseq, edge_window):
             members = [rank[i] for i in range(first, last + 1) if rank[i] and seq[i][1] >= min_score]
             out.append(det + (min(members),))
     return sorted(out, key=lambda det: (det[0], det[2]))
@@ -218,6 +232,9 @@ def parse_args(argv):
     ap.add_argument("--dense", action="store_true",
                     help="score every alignment of every song in every window instead of the ones a top-k search nominates "
                          "(window <= 64, --top 1)")
+    ap.add_argument("--max-fa", type=float, default=None,
+                    help="with --dense: a window counts when the chance that its best score is a chance alignment is at most X "
+                         "(0 < X <= 1), judged from the window's own background; replaces --min-score")
     return ap.parse_args(argv[1:])
 
 
@@ -239,6 +256,12 @@ def main(argv=None):
         return 2
     if args.dense and args.window is not None and args.window > DENSE_MAX_WINDOW:
         print("monitor: --dense takes windows of at most %d segments" % DENSE_MAX_WINDOW, file=sys.stderr)
+        return 2
+    if args.max_fa is not None and not args.dense:
+        print("monitor: --max-fa judges a window by the background of the dense matcher; it needs --dense", file=sys.stderr)
+        return 2
+    if args.max_fa is not None and not 0.0 < args.max_fa <= 1.0:
+        print("monitor: --max-fa is a false-alarm probability, 0 < X <= 1", file=sys.stderr)
         return 2
     import torch
     from .builder import embed_file_batches
@@ -267,7 +290,7 @@ def main(argv=None):
     with open(args.result, "w", encoding="utf8", newline="\n") as fout, \
             open(stem + "_windows.csv", "w", encoding="utf8", newline="\n") as fwin:
         wcsv = csv.writer(fwin)
-        wcsv.writerow(WINDOWS_HEADER + (["rank", "votes"] if args.top > 1 else []))
+        wcsv.writerow(WINDOWS_HEADER + (["rank", "votes"] if args.top > 1 else []) + (["log10_fa"] if args.max_fa is not None else []))
 
         def launch(items):
             good = [(i, n, e) for i, n, e in items if n]
@@ -277,7 +300,8 @@ def main(argv=None):
                 rlen = [n for _, n, _ in good]
                 rstart = np.concatenate([[0], np.cumsum(rlen)[:-1]])
                 if args.dense:
-                    p = db.monitor_dense_launch(emb, rstart, rlen, window, args.hop, edge_window=edge_window)
+                    p = db.monitor_dense_launch(emb, rstart, rlen, window, args.hop, edge_window=edge_window,
+                                                stats=args.max_fa is not None)
                 elif args.top > 1:
                     p = db.monitor_topn_launch(emb, rstart, rlen, window, args.hop, args.top, edge_window=edge_window)
                 else:
@@ -287,7 +311,11 @@ def main(argv=None):
         def finish(launched):
             nonlocal n_windows, n_det
             items, good, p = launched
-            if p is not None and args.top > 1:
+            fa = {}
+            if p is not None and args.max_fa is not None:
+                rows, log10_fa = db.monitor_dense_stats_finish(p)
+                per, fa = dict(zip([i for i, _, _ in good], rows)), dict(zip([i for i, _, _ in good], log10_fa))
+            elif p is not None and args.top > 1:
                 per = dict(zip([i for i, _, _ in good], db.monitor_topn_finish(p)[0]))
             else:
                 per = dict(zip([i for i, _, _ in good], db.monitor_finish(p))) if p is not None else {}
@@ -296,7 +324,7 @@ def main(argv=None):
                 name = dataset.files[i]
                 if n == 0:
                     fout.write("%s\terror\n" % name)
-                    wcsv.writerow([name, "error", "", "", -1e999, 0])
+                    wcsv.writerow([name, "error", "", "", -1e999, 0] + ([0.0] if args.max_fa is not None else []))
                     continue
                 rows = per[i]
                 if args.top > 1:
@@ -306,6 +334,18 @@ def main(argv=None):
                             rows, min(window, n), args.hop, seg_step_s, args.min_score, args.max_gap, min_windows=args.min_windows,
                             edge_rows=edge.get(i), edge_window=min(edge_window, n)):
                         fout.write("%s\t%.3f\t%.3f\t%s\t%.3f\t%.6f\t%.6f\t%d\t%d\n" % (name, d0, d1, db.songList[song], s0, mean, best, nw, rank))
+                        n_det += 1
+                    continue
+                if args.max_fa is not None:              # the calibrated threshold: --min-score is not consulted
+                    for (w0, score, song, time_s), x in zip(rows, fa[i]):
+                        wcsv.writerow([name, int(w0), int(w0) * seg_step_s, db.songList[int(song)] if song >= 0 else "",
+                                       float(score), float(time_s), float(x)])
+                    n_windows += len(rows)
+                    for (d0, d1, song, s0, mean, best, nw), _, members in _merge_runs(
+                            rows, min(window, n), args.hop, seg_step_s, args.min_score, args.max_gap, True, args.min_windows,
+                            edge.get(i), min(edge_window, n), good=fa[i] <= math.log10(args.max_fa)):
+                        fout.write("%s\t%.3f\t%.3f\t%s\t%.3f\t%.6f\t%.6f\t%d\t%.3f\n"
+                                   % (name, d0, d1, db.songList[song], s0, mean, best, nw, min(float(fa[i][j]) for j in members)))
                         n_det += 1
                     continue
                 for w0, score, song, time_s in rows:
