@@ -22,6 +22,7 @@
  *   pfann_match_windows_dense  database.py:129-163 with every row's label list = the whole database (no counterpart)
  *   pfann_match_windows_dense_stats  the same answer, and the moments of every window's full candidates (no counterpart)
  *   pfann_match_windows_dense_topn  the same candidates, the n best songs per window and the per-song block (no counterpart)
+ *   pfann_match_windows_dense_part / _merge, _topn_part / _topn_merge  the three above over song-sharded handles (no counterpart)
  */
 #ifndef PFANN_AMD_H
 #define PFANN_AMD_H
@@ -574,6 +575,69 @@ int pfann_match_windows_dense_topn(pfann_db *db, const float *q_dev,
                                    int32_t *n_found_dev /* [n_windows] or NULL */,
                                    float *song_scores_dev /* [n_windows][n_songs][2] or NULL */,
                                    void *stream);
+
+/* Song-sharded dense matcher (csrc/dense.hip): the three calls above refuse a handle that holds a shard; these four split them
+ * into a PART per handle and a MERGE, so that N handles that cut the song list into contiguous ranges -- N GPUs, each with 1/N
+ * of the rows -- give, byte for byte, what one handle of the whole database gives.
+ * WHY THE MERGE IS EXACT.  A candidate is (song, offset) and songs are never split, so every candidate belongs to exactly one
+ * part.  Its total adds the row dots of rows of its own song only, in the summation order above: the part computes the very
+ * float the whole database computes.  The packed word is (order-preserving bits of the total, 0xFFFFFFFF - id) with id formed
+ * from the GLOBAL song_pos and song number, which every handle carries: words of different parts compare as they do inside one
+ * handle, and the largest over the parts is the word the whole database's atomicMax leaves, ties included.  The statistics
+ * are 64-bit integer sums over full candidates; their sum over the parts is the whole sum, bit for bit.
+ *
+ * pfann_match_windows_dense_part: any fp32 handle -- a shard (label_base, owned songs, global song_pos) or a whole database.
+ * Recordings, windows, wfirst_dev, n_windows, short and empty recordings, excl_song_dev, the summation order and the asynchrony
+ * follow pfann_match_windows_dense; the candidates are that call's, restricted to the handle's owned songs.  The tile kernel's
+ * columns run over the handle's global rows [label_base, label_base + n): tile j starts at label_base + j * SI - (window-1),
+ * SI = 128 - (window-1); rows outside the range are zeros without a song.  words_dev[n_windows] gets the raw running-best
+ * word of every window (0: no candidate here), stats_dev[n_windows] (or NULL) the three integers over this handle's full
+ * candidates.  A handle without rows launches no tile: zeros.
+ *
+ * pfann_match_windows_dense_merge: any handle of the database (only its song_pos is read).  words_dev[n_parts][n_windows],
+ * part_stats_dev[n_parts][n_windows] or NULL; stats_dev is NULL exactly when part_stats_dev is.  One small kernel, one thread
+ * per window: the maximum word, the two's-complement sums, then pfann_match_windows_dense's decode, n_cand from the global
+ * sizes.  CONTRACT: for any cut of the song list into contiguous ranges, the parts in any order, results_dev and stats_dev get
+ * the 24 + 24 bytes per window that pfann_match_windows_dense / _stats write for the same arguments on the whole database.
+ *
+ * pfann_match_windows_dense_topn_part: the ranked form over the handle's owned songs: workspace [windows of a chunk][owned
+ * songs], top_dev[n_windows][n] with global song ids and n_cand = len_s + n_rows - 1, n_found_dev (or NULL) = the owned songs
+ * with rows, not counting the excluded one.  No per-song block.  Chunks, PFANN_DENSE_TOPN_WINDOWS and the one wait when the
+ * workspace grows follow pfann_match_windows_dense_topn.
+ *
+ * pfann_match_windows_dense_topn_merge: tops_dev[n_parts][n_windows][n], n_found_parts_dev[n_parts][n_windows] or NULL (exactly
+ * when n_found_dev is).  Per window the n best of the n_parts * n entries by score descending, then song ascending, padding
+ * last; n_found = the sum.  That order is the word order of the whole database's select: (double)total / (double)n_rows is
+ * injective on fp32 totals for n_rows <= 64, so equal scores are equal totals, and the songs of different parts are disjoint, so
+ * between equal totals the lower song is the smaller id.  CONTRACT: the bytes of pfann_match_windows_dense_topn on the whole
+ * database, the prefix rule and "entry 0 equals the merged unranked answer" included.
+ *
+ * All four return -1 with a message, launch nothing and write nothing, when an output (or words_dev / tops_dev) is NULL, the
+ * stats / n_found pair is mismatched, n_parts < 1, n is outside 1..64, window is outside 1..64, hop < 1, or the id bound fails on
+ * the GLOBAL sizes, song_pos[n_songs] + n_songs * (window - 1) >= 2^32; the parts also when the storage is fp16-only or
+ * d % 4 != 0. */
+int pfann_match_windows_dense_part(pfann_db *db, const float *q_dev,
+                                   const int64_t *rstart_dev, const int32_t *rlen_dev, int64_t nR,
+                                   int window, int hop, const int64_t *wfirst_dev, int64_t n_windows,
+                                   const int32_t *excl_song_dev /* [nR] or NULL */,
+                                   uint64_t *words_dev /* [n_windows] */,
+                                   pfann_dense_stats *stats_dev /* [n_windows] or NULL */, void *stream);
+int pfann_match_windows_dense_merge(pfann_db *db, const uint64_t *words_dev /* [n_parts][n_windows] */,
+                                    const pfann_dense_stats *part_stats_dev /* [n_parts][n_windows] or NULL */, int n_parts,
+                                    const int32_t *rlen_dev, int64_t nR, int window, const int64_t *wfirst_dev,
+                                    int64_t n_windows, const int32_t *excl_song_dev /* [nR] or NULL */,
+                                    pfann_match_result *results_dev,
+                                    pfann_dense_stats *stats_dev /* NULL exactly when part_stats_dev is */, void *stream);
+int pfann_match_windows_dense_topn_part(pfann_db *db, const float *q_dev,
+                                        const int64_t *rstart_dev, const int32_t *rlen_dev, int64_t nR,
+                                        int window, int hop, const int64_t *wfirst_dev, int64_t n_windows,
+                                        const int32_t *excl_song_dev /* [nR] or NULL */, int n,
+                                        pfann_match_result *top_dev /* [n_windows][n] */,
+                                        int32_t *n_found_dev /* [n_windows] or NULL */, void *stream);
+int pfann_match_windows_dense_topn_merge(pfann_db *db, const pfann_match_result *tops_dev /* [n_parts][n_windows][n] */,
+                                         const int32_t *n_found_parts_dev /* [n_parts][n_windows] or NULL */, int n_parts,
+                                         int64_t n_windows, int n, pfann_match_result *top_dev /* [n_windows][n] */,
+                                         int32_t *n_found_dev /* [n_windows] or NULL */, void *stream);
 
 /* Songs whose rows all live in this shard: [*song_lo, *song_hi) (either pointer may be NULL); returns their number. */
 int pfann_db_owned_songs(pfann_db *db, int *song_lo, int *song_hi);

@@ -1405,6 +1405,134 @@ int pfann_match_windows_dense_topn(pfann_db *db, const float *q, const int64_t *
     return 0;
 }
 
+// ---- song-sharded dense matcher: parts on any fp32 handle, merges on any handle of the database ------------------------------
+// the refusals every one of the four calls shares; the id bound is that of the WHOLE database (every handle has its song_pos)
+static int dense_shard_check(const char *what, pfann_db *db, int window, bool needs_rows) {
+    if (db->song_pos_h.empty()) { set_error("%s: no database loaded", what); return -1; }
+    if (needs_rows && (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr))) {
+        set_error("%s: fp16-only storage (the dense matcher scores fp32 rows)", what);
+        return -1;
+    }
+    if (needs_rows && db->d % 4 != 0) { set_error("%s: d %% 4 != 0 (d=%d)", what, db->d); return -1; }
+    if (window < 1 || window > 64) { set_error("%s: window=%d outside 1..64", what, window); return -1; }
+    if (db->song_pos_h.back() + (int64_t)db->n_songs * (window - 1) >= (1ll << 32)) {
+        set_error("%s: %lld rows and %d songs at window %d do not fit the 32-bit alignment id", what, (long long)db->song_pos_h.back(),
+                  db->n_songs, window);
+        return -1;
+    }
+    // the owned songs span exactly the handle's rows (pfann_db_load, pfann_db_set_owned_songs): the ranked workspace relies on it
+    if (needs_rows && (db->song_lo < 0 || db->song_hi < db->song_lo || db->song_hi > db->n_songs ||
+                       db->song_pos_h[db->song_lo] != db->label_base || db->song_pos_h[db->song_hi] != db->label_base + db->n)) {
+        set_error("%s: the handle's rows [%lld,%lld) are not its songs [%d,%d)", what, (long long)db->label_base,
+                  (long long)(db->label_base + db->n), db->song_lo, db->song_hi);
+        return -1;
+    }
+    return 0;
+}
+
+int pfann_match_windows_dense_part(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
+                                   int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, uint64_t *words,
+                                   pfann_dense_stats *stats, void *stream) {
+    const char *what = "match_windows_dense_part";
+    PF_HIP(hipSetDevice(db->device));
+    if (words == nullptr) { set_error("%s: words_dev is null", what); return -1; }
+    if (dense_shard_check(what, db, window, true)) return -1;
+    if (hop < 1 || nR < 0 || n_windows < 0) {
+        set_error("%s: hop=%d nR=%lld n_windows=%lld", what, hop, (long long)nR, (long long)n_windows);
+        return -1;
+    }
+    if (nR == 0 || n_windows == 0) return 0;
+    DensePartArgs a;
+    a.db = db->emb; a.ntotal = db->song_pos_h.back(); a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+    a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
+    a.nW = n_windows; a.excl = excl_song; a.results = nullptr; a.stats = stats;
+    a.row_lo = db->label_base; a.nrows = db->n; a.words = reinterpret_cast<unsigned long long *>(words);
+    return launch_match_windows_dense_part(a, (hipStream_t)stream);
+}
+
+int pfann_match_windows_dense_merge(pfann_db *db, const uint64_t *words, const pfann_dense_stats *part_stats, int n_parts,
+                                    const int32_t *rlen, int64_t nR, int window, const int64_t *wfirst, int64_t n_windows,
+                                    const int32_t *excl_song, pfann_match_result *results, pfann_dense_stats *stats, void *stream) {
+    const char *what = "match_windows_dense_merge";
+    PF_HIP(hipSetDevice(db->device));
+    if (words == nullptr || results == nullptr) { set_error("%s: words_dev or results_dev is null", what); return -1; }
+    if ((part_stats == nullptr) != (stats == nullptr)) {
+        set_error("%s: part_stats_dev and stats_dev go together (both or neither)", what);
+        return -1;
+    }
+    if (n_parts < 1) { set_error("%s: n_parts=%d", what, n_parts); return -1; }
+    if (dense_shard_check(what, db, window, false)) return -1;
+    if (nR < 0 || n_windows < 0) { set_error("%s: nR=%lld n_windows=%lld", what, (long long)nR, (long long)n_windows); return -1; }
+    if (nR == 0 || n_windows == 0) return 0;
+    DenseMergeArgs a;
+    a.song_pos = db->song_pos; a.n_songs = db->n_songs; a.ntotal = db->song_pos_h.back(); a.songs_with_rows = 0;
+    for (int s = 0; s < db->n_songs; ++s) a.songs_with_rows += db->song_pos_h[s + 1] > db->song_pos_h[s];
+    a.words = reinterpret_cast<const unsigned long long *>(words); a.part_stats = part_stats; a.n_parts = n_parts;
+    a.rlen = rlen; a.nR = nR; a.window = window; a.wfirst = wfirst; a.nW = n_windows; a.excl = excl_song;
+    a.results = results; a.stats = stats;
+    return launch_dense_merge(a, (hipStream_t)stream);
+}
+
+int pfann_match_windows_dense_topn_part(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR,
+                                        int window, int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
+                                        int n, pfann_match_result *top, int32_t *n_found, void *stream) {
+    const char *what = "match_windows_dense_topn_part";
+    PF_HIP(hipSetDevice(db->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 1 || n > 64) { set_error("%s: n=%d outside 1..64", what, n); return -1; }
+    if (top == nullptr) { set_error("%s: top_dev is null", what); return -1; }
+    if (dense_shard_check(what, db, window, true)) return -1;
+    if (hop < 1 || nR < 0 || n_windows < 0) {
+        set_error("%s: hop=%d nR=%lld n_windows=%lld", what, hop, (long long)nR, (long long)n_windows);
+        return -1;
+    }
+    if (nR == 0 || n_windows == 0) return 0;
+    // the chunks of pfann_match_windows_dense_topn, over the owned songs
+    const int wps = dense_topn_wps(window, hop);
+    const int64_t n_slots = dense_topn_slots(n_windows, nR, window, hop);
+    const int n_owned = db->song_hi - db->song_lo;
+    const int64_t songs = std::max(n_owned, 1);
+    int64_t cap = (256ll << 20) / (8 * songs);
+    const char *env = getenv("PFANN_DENSE_TOPN_WINDOWS");
+    if (env != nullptr && env[0] != 0 && atoll(env) > 0) cap = std::min<int64_t>(cap, atoll(env));
+    const int64_t step = std::min(n_slots, std::max<int64_t>(1, cap / wps));
+    const size_t need = (size_t)step * wps * songs * 8;
+    if (db->dense_ws_bytes < need) {                 // grow, then free: a failed allocation leaves the handle as it was
+        PF_HIP(hipStreamSynchronize(st));
+        void *grown = nullptr;
+        PF_HIP(hipMalloc(&grown, need));
+        if (db->dense_ws) (void)hipFree(db->dense_ws);
+        db->dense_ws = grown;
+        db->dense_ws_bytes = need;
+    }
+    DenseTopnPartArgs a;
+    a.db = db->emb; a.ntotal = db->song_pos_h.back(); a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+    a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
+    a.nW = n_windows; a.excl = excl_song; a.results = nullptr;
+    a.ws = reinterpret_cast<unsigned long long *>(db->dense_ws); a.wps = wps;
+    a.n = n; a.top = top; a.n_found = n_found; a.song_scores = nullptr;
+    a.row_lo = db->label_base; a.nrows = db->n; a.song_lo = db->song_lo; a.n_owned = n_owned;
+    for (int64_t s0 = 0; s0 < n_slots; s0 += step) {
+        a.slot_lo = s0; a.slot_n = std::min(step, n_slots - s0);
+        if (launch_match_windows_dense_topn_part(a, st)) return -1;
+    }
+    return 0;
+}
+
+int pfann_match_windows_dense_topn_merge(pfann_db *db, const pfann_match_result *tops, const int32_t *n_found_parts, int n_parts,
+                                         int64_t n_windows, int n, pfann_match_result *top, int32_t *n_found, void *stream) {
+    const char *what = "match_windows_dense_topn_merge";
+    PF_HIP(hipSetDevice(db->device));
+    if (n < 1 || n > 64) { set_error("%s: n=%d outside 1..64", what, n); return -1; }
+    if (tops == nullptr || top == nullptr) { set_error("%s: tops_dev or top_dev is null", what); return -1; }
+    if ((n_found_parts == nullptr) != (n_found == nullptr)) {
+        set_error("%s: n_found_parts_dev and n_found_dev go together (both or neither)", what);
+        return -1;
+    }
+    if (n_parts < 1 || n_windows < 0) { set_error("%s: n_parts=%d n_windows=%lld", what, n_parts, (long long)n_windows); return -1; }
+    return launch_dense_topn_merge(tops, n_found_parts, n_parts, n_windows, n, top, n_found, (hipStream_t)stream);
+}
+
 int pfann_match_windows_topn(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart, const int32_t *rlen,
                              int64_t nR, int window, int hop, int frame_shift_mul, float score_alpha, int mode,
                              const int64_t *wfirst, int n, pfann_match_result *top, int32_t *n_found, void *stream) {

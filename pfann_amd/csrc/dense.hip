@@ -27,6 +27,12 @@
 // fp32; no sliding or prefix sums.
 // BYTE CONTRACT.  A window's 24 result bytes are a function of the window's rows, the database and its recording's
 // excluded song alone: not of hop, the other windows or recordings of the call, the tiling or the run.
+//
+// SONG-SHARDED (pfann_match_windows_dense_part / _merge, _topn_part / _topn_merge).  A candidate is (song, offset) and songs are
+// never split, so it belongs to exactly one shard; its total adds rows of its own song only, so the shard computes the very
+// float; and the id is formed from the GLOBAL song_pos, which every handle carries, so words of different shards compare as they
+// do inside one handle: the maximum over the shards' words is the word the whole database leaves, ties included, and the sum of
+// the shards' integer statistics is the whole sum.  N handles give the bytes of one (kernel: SHARD below; merges further down).
 #include "kernels.h"
 #include "match_common.h"
 #include <algorithm>
@@ -66,9 +72,22 @@ __device__ __forceinline__ int dn_windows_of(int L, int window, int hop) {
 // are exact in double, so the rounding is the only rounding, and everything after it -- wave shuffles, one LDS entry per
 // window start, one global 64-bit atomicAdd per non-zero entry -- is integer addition: the three sums of a window are, like
 // its result bytes, a function of its rows, the database and the excluded song alone.
-template <bool RANKED, bool STATS = false>
-__global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(
-        typename std::conditional<RANKED, DenseTopnArgs, typename std::conditional<STATS, DenseStatsArgs, DenseArgs>::type>::type a) {
+//
+// SHARD (pfann_match_windows_dense_part / _topn_part): the handle holds the global rows [row_lo, row_lo + nrows) of a song-sharded
+// database, whole songs only, and the global song_pos.  The db tiles run over that range -- tile jt starts at global row
+// row_lo + jt * SI - (window-1) --, rows outside it are zeros without a song (what a tile of the whole database reads past
+// either end), and the song lookup, s_head and the id stay global: a candidate belongs to exactly one shard and gets there the
+// word it gets from the whole database.  The unranked form leaves the raw words (no decode), the ranked form indexes its
+// workspace by song - song_lo.  No new LDS; the instantiations without SHARD are the code they were before it existed.
+template <bool SHARD, bool RANKED, bool STATS> struct DenseKernelArgs {
+    typedef typename std::conditional<RANKED, DenseTopnArgs, typename std::conditional<STATS, DenseStatsArgs, DenseArgs>::type>::type type;
+};
+template <bool RANKED, bool STATS> struct DenseKernelArgs<true, RANKED, STATS> {
+    typedef typename std::conditional<RANKED, DenseTopnPartArgs, DensePartArgs>::type type;
+};
+
+template <bool RANKED, bool STATS = false, bool SHARD = false>
+__global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(typename DenseKernelArgs<SHARD, RANKED, STATS>::type a) {
     static_assert(!(RANKED && STATS), "the moments are kept by the unranked form");
     // S[DN_T][DN_LDS]; while the product runs its first bytes are the two K tiles As, Bs [DN_T][DN_LDK]
     extern __shared__ __attribute__((aligned(16))) float s_S[];          // DN_S_BYTES, dynamic: past the static 64 KB
@@ -85,7 +104,9 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lhalf = lane >> 5;
     const int SI = DN_T - (a.window - 1);                // window starts / alignments a tile owns per edge
     const int64_t n_slots = a.nW * a.hop / SI + a.nR;    // recording r owns the row-tile slots from wfirst[r] * hop / SI + r
-    const int64_t NJ = (a.ntotal + a.window - 1 + SI - 1) / SI;
+    int64_t row_lo = 0, row_n = a.ntotal;                // the global rows this handle holds
+    if constexpr (SHARD) { row_lo = a.row_lo; row_n = a.nrows; }
+    const int64_t NJ = (row_n + a.window - 1 + SI - 1) / SI;
     int64_t slot_lo = 0, slot_n = n_slots;
     if constexpr (RANKED) { slot_lo = a.slot_lo; slot_n = a.slot_n; }
     const int64_t n_items = slot_n * NJ;
@@ -106,13 +127,13 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(
         const int64_t I0 = (slot - (wf * a.hop / SI + r)) * SI;          // first recording row of the tile
         if (nw <= 0 || I0 > (int64_t)(nw - 1) * a.hop) continue;         // (the whole workgroup: a spare slot)
         const int wl = min(a.window, L);                 // rows of a window: `window`, or all rows of a shorter recording
-        const int64_t J0 = jt * SI - (a.window - 1);     // db row of the tile's column 0 (negative in the first tile)
+        const int64_t J0 = row_lo + jt * SI - (a.window - 1);   // db row of the tile's column 0 (before the rows in the first tile)
         const int excl = a.excl != nullptr ? a.excl[r] : -1;
         const int i0 = (int)I0;
 
         if (tid < DN_T) {
             const int64_t g = J0 + tid;
-            s_song[tid] = g >= 0 && g < a.ntotal ? song_of_label(a.song_pos, a.n_songs, s_cpos, cshift, n_coarse, g) : -1;
+            s_song[tid] = g >= row_lo && g < row_lo + row_n ? song_of_label(a.song_pos, a.n_songs, s_cpos, cshift, n_coarse, g) : -1;
             s_best[tid] = 0;
             if constexpr (RANKED) {                      // the song's first column in the tile (a column without a song: itself)
                 const int sg = s_song[tid];
@@ -131,7 +152,7 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(
             const int row = srow + 64 * u;
             qp[u] = i0 + row < L ? a.q + (a.rstart[r] + i0 + row) * (int64_t)a.d : nullptr;
             const int64_t g = J0 + row;
-            dp[u] = g >= 0 && g < a.ntotal ? a.db + g * (int64_t)a.d : nullptr;
+            dp[u] = g >= row_lo && g < row_lo + row_n ? a.db + (g - row_lo) * (int64_t)a.d : nullptr;
         }
         dn_f32x4 ra[2][2], rb[2][2];
         auto load_tile = [&](int k0) {
@@ -260,7 +281,8 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(
                     const unsigned long long x = tab[j];             // entry j: the song whose first column is j
                     if (x != 0) {                                    // (only a half with a window start has any)
                         tab[j] = 0;
-                        atomicMax(&a.ws[(ws_row0 + (i0 + i) / a.hop) * a.n_songs + s_song[j]], x);
+                        if constexpr (SHARD) atomicMax(&a.ws[(ws_row0 + (i0 + i) / a.hop) * a.n_owned + (s_song[j] - a.song_lo)], x);
+                        else atomicMax(&a.ws[(ws_row0 + (i0 + i) / a.hop) * a.n_songs + s_song[j]], x);
                     }
                 }
                 __syncthreads();                                     // the tables are empty again
@@ -333,7 +355,8 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(
                 const unsigned long long x = s_best[tid];
                 if (x != 0) {                                // (only window starts of the recording ever get a word)
                     const int64_t w = wf + (i0 + tid) / a.hop;
-                    atomicMax(reinterpret_cast<unsigned long long *>(&a.results[w].score), x);
+                    if constexpr (SHARD) atomicMax(&a.words[w], x);
+                    else atomicMax(reinterpret_cast<unsigned long long *>(&a.results[w].score), x);
                     if constexpr (STATS) {
                         const int nf = s_full[tid];
                         if (nf != 0) {                       // (a full piece is a candidate: x != 0 wherever there is one)
@@ -350,41 +373,89 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(
     }
 }
 
-// packed words -> results, in place.  n_cand = sum over songs with rows (without the excluded one) of len_s + n - 1
-__global__ void dense_decode_kernel(DenseArgs a, int64_t songs_with_rows) {
-    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= a.nW) return;
+// the recording of window w, the rows n of its windows and its excluded song (Args: anything with nR, wfirst, rlen, window, excl)
+template <class Args>
+__device__ __forceinline__ void dn_window_of(const Args &a, int64_t w, int &n, int &excl) {
     int64_t lo = 0, hi = a.nR - 1;                       // first recording whose windows end after w
     while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
         if (a.wfirst[mid + 1] <= w) lo = mid + 1; else hi = mid;
     }
-    const int n = min(a.window, a.rlen[lo]);
-    const int excl = a.excl != nullptr ? a.excl[lo] : -1;
-    int64_t ncand = a.ntotal + songs_with_rows * (n - 1);
-    if (excl >= 0 && excl < a.n_songs) {
-        const int64_t len = a.song_pos[excl + 1] - a.song_pos[excl];
+    n = min(a.window, a.rlen[lo]);
+    excl = a.excl != nullptr ? a.excl[lo] : -1;
+}
+
+// a window's packed word -> its result.  n_cand = sum over songs with rows (without the excluded one) of len_s + n - 1; ntotal,
+// song_pos and songs_with_rows are those of the WHOLE database
+__device__ __forceinline__ pfann_match_result dn_decode_word(unsigned long long x, int n, int excl, const int64_t *song_pos,
+                                                             int n_songs, int64_t ntotal, int64_t songs_with_rows) {
+    int64_t ncand = ntotal + songs_with_rows * (n - 1);
+    if (excl >= 0 && excl < n_songs) {
+        const int64_t len = song_pos[excl + 1] - song_pos[excl];
         if (len > 0) ncand -= len + n - 1;
     }
-    const unsigned long long x = *reinterpret_cast<const unsigned long long *>(&a.results[w].score);
     pfann_match_result res;
     if (x != 0) {
         const int64_t id = (int64_t)(0xFFFFFFFFu - (unsigned)x);
-        int sl = 0, sh = a.n_songs;                      // largest s with song_pos[s] + s * (n-1) <= id
+        int sl = 0, sh = n_songs;                        // largest s with song_pos[s] + s * (n-1) <= id
         while (sl < sh) {
             const int mid = (sl + sh) >> 1;
-            if (a.song_pos[mid] + (int64_t)mid * (n - 1) <= id) sl = mid + 1; else sh = mid;
+            if (song_pos[mid] + (int64_t)mid * (n - 1) <= id) sl = mid + 1; else sh = mid;
         }
         const int s = sl - 1;
         res.song = s;
-        res.offset = (int)(id - a.song_pos[s] - (int64_t)(s + 1) * (n - 1));
+        res.offset = (int)(id - song_pos[s] - (int64_t)(s + 1) * (n - 1));
         res.shift = 0;
         res.n_cand = (int)ncand;
         res.score = (double)dn_ordered_float((unsigned)(x >> 32)) / (double)n;
     } else {
         res.song = -1; res.offset = 0; res.shift = 0; res.n_cand = 0; res.score = -INFINITY;
     }
-    a.results[w] = res;
+    return res;
+}
+
+// packed words -> results, in place
+__global__ void dense_decode_kernel(DenseArgs a, int64_t songs_with_rows) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= a.nW) return;
+    int n, excl;
+    dn_window_of(a, w, n, excl);
+    const unsigned long long x = *reinterpret_cast<const unsigned long long *>(&a.results[w].score);
+    a.results[w] = dn_decode_word(x, n, excl, a.song_pos, a.n_songs, a.ntotal, songs_with_rows);
+}
+
+// pfann_match_windows_dense_merge, one thread per window: the largest word of the parts (ids are global, so it is the word the
+// whole database leaves in the slot, ties included), the sum of the parts' integers (every full candidate is in exactly one
+// part), and dense_decode_kernel's decode
+__global__ void dense_merge_kernel(DenseMergeArgs a) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= a.nW) return;
+    int n, excl;
+    dn_window_of(a, w, n, excl);
+    unsigned long long x = 0;
+    for (int p = 0; p < a.n_parts; ++p) {
+        const unsigned long long v = a.words[(int64_t)p * a.nW + w];
+        x = v > x ? v : x;
+    }
+    a.results[w] = dn_decode_word(x, n, excl, a.song_pos, a.n_songs, a.ntotal, a.songs_with_rows);
+    if (a.stats != nullptr) {
+        unsigned long long nf = 0, sum = 0, sumsq = 0;   // two's complement: unsigned addition
+        for (int p = 0; p < a.n_parts; ++p) {
+            const pfann_dense_stats st = a.part_stats[(int64_t)p * a.nW + w];
+            nf += (unsigned long long)st.n_full; sum += (unsigned long long)st.sum_q; sumsq += (unsigned long long)st.sumsq_q;
+        }
+        pfann_dense_stats out;
+        out.n_full = (int64_t)nf; out.sum_q = (int64_t)sum; out.sumsq_q = (int64_t)sumsq;
+        a.stats[w] = out;
+    }
+}
+
+int launch_dense_merge(const DenseMergeArgs &a, hipStream_t s) {
+    if (a.nR <= 0 || a.nW <= 0) return 0;
+    ProfScope ps("seq_dense_merge", s, (double)a.nW * a.n_parts * (a.stats != nullptr ? 32.0 : 8.0));
+    PF_LAUNCH(dense_merge_kernel, dim3((unsigned)cdiv(a.nW, 256)), dim3(256), 0, s, a);
+    PF_HIP(hipGetLastError());
+    return 0;
 }
 
 // the unranked tile kernel, with or without the moments, and the decode; Args = what that instantiation takes
@@ -419,6 +490,30 @@ int launch_match_windows_dense_stats(const DenseStatsArgs &a, int64_t songs_with
     return launch_dense_tiles<true>(a, songs_with_rows, "seq_match_windows_dense_stats", s);
 }
 
+// the raw words (and moments) of the handle's rows; no decode: pfann_match_windows_dense_merge does it over all parts
+template <bool STATS>
+static int launch_dense_part_tiles(const DensePartArgs &a, hipStream_t s) {
+    PF_HIP(hipMemsetAsync(a.words, 0, (size_t)a.nW * sizeof(unsigned long long), s));
+    if constexpr (STATS) PF_HIP(hipMemsetAsync(a.stats, 0, (size_t)a.nW * sizeof(pfann_dense_stats), s));
+    if (a.nrows <= 0) return 0;                          // a shard without rows: no tile
+    const int SI = DN_T - (a.window - 1);
+    const int64_t n_slots = a.nW * a.hop / SI + a.nR;
+    const int64_t NJ = (a.nrows + a.window - 1 + SI - 1) / SI;
+    const int64_t n_items = n_slots * NJ;
+    const double rows = (double)a.nW * a.hop + (double)a.nR * a.window;
+    const auto kernel = match_windows_dense_kernel<false, STATS, true>;
+    if (ensure_dyn_lds((const void *)kernel, DN_S_BYTES)) return -1;
+    ProfScope ps("seq_match_windows_dense_part", s, 2.0 * rows * (double)a.nrows * a.d);
+    PF_LAUNCH(kernel, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
+    PF_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_match_windows_dense_part(const DensePartArgs &a, hipStream_t s) {
+    if (a.nR <= 0 || a.nW <= 0) return 0;
+    return a.stats != nullptr ? launch_dense_part_tiles<true>(a, s) : launch_dense_part_tiles<false>(a, s);
+}
+
 // ---- ranked: ws -> the n best songs of every window of the chunk (pfann_match_windows_dense_topn) --------------------------
 // One workgroup per (slot of the chunk, window start of the slot); a pair that is no window of the call ends at once.  A
 // song's word holds its best candidate; word order IS the ranking (higher total first, equal totals to the smaller id: the
@@ -427,7 +522,9 @@ int launch_match_windows_dense_stats(const DenseStatsArgs &a, int64_t songs_with
 // it looks for its next largest word below it.
 static constexpr int DN_SEL_NT = 256;
 
-__global__ __launch_bounds__(DN_SEL_NT) void dense_select_kernel(DenseTopnArgs a) {
+// SHARD: the words of the handle's owned songs, ws[..][song - song_lo]; entries carry the global song; no per-song block.
+template <bool SHARD>
+__global__ __launch_bounds__(DN_SEL_NT) void dense_select_kernel(typename std::conditional<SHARD, DenseTopnPartArgs, DenseTopnArgs>::type a) {
     __shared__ unsigned long long s_max[2][DN_SEL_NT / 64];
     __shared__ int s_cnt[DN_SEL_NT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -449,7 +546,9 @@ __global__ __launch_bounds__(DN_SEL_NT) void dense_select_kernel(DenseTopnArgs a
     if (wi * a.hop >= I0 + SI || wi >= nw) return;
     const int64_t w = wf + wi;
     const int n = min(a.window, L);
-    const unsigned long long *row = a.ws + (int64_t)blockIdx.x * a.n_songs;
+    int s_base = 0, n_sel = a.n_songs;                   // the songs of the workspace: mine_s and s below are song - s_base
+    if constexpr (SHARD) { s_base = a.song_lo; n_sel = a.n_owned; }
+    const unsigned long long *row = a.ws + (int64_t)blockIdx.x * n_sel;
     pfann_match_result *top = a.top + w * a.n;
     auto offset_of = [&](unsigned long long x, int s) {
         return (int)((int64_t)(0xFFFFFFFFu - (unsigned)x) - a.song_pos[s] - (int64_t)(s + 1) * (n - 1));
@@ -458,15 +557,17 @@ __global__ __launch_bounds__(DN_SEL_NT) void dense_select_kernel(DenseTopnArgs a
 
     unsigned long long mine = 0;                         // the largest word of this thread's songs not yet listed
     int mine_s = -1, cnt = 0;
-    for (int s = tid; s < a.n_songs; s += DN_SEL_NT) {
+    for (int s = tid; s < n_sel; s += DN_SEL_NT) {
         const unsigned long long x = row[s];
         cnt += x != 0;
         if (x > mine) { mine = x; mine_s = s; }
-        if (a.song_scores != nullptr) {                  // the reference's block records only scores above its zeros
-            const float f = x != 0 ? (float)score_of(x) : 0.f;
-            float2 v = {0.f, 0.f};
-            if (f > 0.f) { v.x = f; v.y = (float)offset_of(x, s); }
-            reinterpret_cast<float2 *>(a.song_scores)[w * a.n_songs + s] = v;
+        if constexpr (!SHARD) {
+            if (a.song_scores != nullptr) {              // the reference's block records only scores above its zeros
+                const float f = x != 0 ? (float)score_of(x) : 0.f;
+                float2 v = {0.f, 0.f};
+                if (f > 0.f) { v.x = f; v.y = (float)offset_of(x, s); }
+                reinterpret_cast<float2 *>(a.song_scores)[w * a.n_songs + s] = v;
+            }
         }
     }
     if (a.n_found != nullptr) {
@@ -501,15 +602,16 @@ __global__ __launch_bounds__(DN_SEL_NT) void dense_select_kernel(DenseTopnArgs a
         }
         if (mine == best) {                              // words are distinct: exactly one thread
             pfann_match_result res;
-            res.song = mine_s;
-            res.offset = offset_of(best, mine_s);
+            const int sg = s_base + mine_s;
+            res.song = sg;
+            res.offset = offset_of(best, sg);
             res.shift = 0;
-            res.n_cand = (int)(a.song_pos[mine_s + 1] - a.song_pos[mine_s]) + n - 1;
+            res.n_cand = (int)(a.song_pos[sg + 1] - a.song_pos[sg]) + n - 1;
             res.score = score_of(best);
             top[e] = res;
             mine = 0; mine_s = -1;
             if (e + 1 < a.n)
-                for (int s = tid; s < a.n_songs; s += DN_SEL_NT) {
+                for (int s = tid; s < n_sel; s += DN_SEL_NT) {
                     const unsigned long long x = row[s];
                     if (x < best && x > mine) { mine = x; mine_s = s; }
                 }
@@ -534,11 +636,99 @@ int launch_match_windows_dense_topn(const DenseTopnArgs &a, hipStream_t s) {
         PF_HIP(hipGetLastError());
     }
     ProfScope ps("seq_dense_select", s, (double)rows * a.n_songs * 8.0);
-    PF_LAUNCH(dense_select_kernel, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);
+    PF_LAUNCH(dense_select_kernel<false>, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);
     PF_HIP(hipGetLastError());
     return 0;
 }
 
+int launch_match_windows_dense_topn_part(const DenseTopnPartArgs &a, hipStream_t s) {
+    if (a.nR <= 0 || a.nW <= 0 || a.slot_n <= 0) return 0;
+    const int SI = DN_T - (a.window - 1);
+    const int64_t rows = a.slot_n * a.wps;
+    if (a.n_owned > 0) PF_HIP(hipMemsetAsync(a.ws, 0, (size_t)rows * a.n_owned * sizeof(unsigned long long), s));
+    if (a.nrows > 0) {
+        const int64_t NJ = (a.nrows + a.window - 1 + SI - 1) / SI;
+        const int64_t n_items = a.slot_n * NJ;
+        const auto kernel = match_windows_dense_kernel<true, false, true>;
+        if (ensure_dyn_lds((const void *)kernel, DN_S_BYTES)) return -1;
+        ProfScope ps("seq_match_windows_dense_topn_part", s, 2.0 * (double)a.slot_n * DN_T * (double)a.nrows * a.d);
+        PF_LAUNCH(kernel, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
+        PF_HIP(hipGetLastError());
+    }
+    ProfScope ps("seq_dense_select", s, (double)rows * a.n_owned * 8.0);
+    PF_LAUNCH(dense_select_kernel<true>, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);
+    PF_HIP(hipGetLastError());
+    return 0;
+}
+
+// pfann_match_windows_dense_topn_merge, one wave per window: the n best of the parts' n_parts * n entries by score descending,
+// then song ascending, padding last.  This IS the word order of the whole database's select: (double)total / (double)n_rows is
+// injective on fp32 totals for n_rows <= 64 (the quotient of two different floats by a divisor below 2^7 keeps more than the 24
+// bits that tell them apart), so equal scores are equal totals, and between different songs the smaller id is the lower song;
+// the songs of different parts are disjoint, so every (score, song) is there once.  Entry e = the best entry after entry e-1.
+static constexpr int DN_MRG_NT = 256;
+
+__global__ __launch_bounds__(DN_MRG_NT) void dense_topn_merge_kernel(const pfann_match_result *tops, const int32_t *nf_parts,
+                                                                     int n_parts, int64_t nW, int n, pfann_match_result *top,
+                                                                     int32_t *n_found) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * (DN_MRG_NT / 64) + (threadIdx.x >> 6);
+    if (w >= nW) return;                                 // (whole waves; no barrier below)
+    const int E = n_parts * n;
+    auto entry = [&](int i) -> const pfann_match_result & {
+        const int p = i / n;
+        return tops[((int64_t)p * nW + w) * n + (i - p * n)];
+    };
+    auto before = [](double sa, int ga, double sb, int gb) { return sa > sb || (sa == sb && ga < gb); };
+    if (n_found != nullptr) {
+        int c = 0;
+        for (int p = lane; p < n_parts; p += 64) c += nf_parts[(int64_t)p * nW + w];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if (lane == 0) n_found[w] = c;
+    }
+    double last_sc = 0.0;
+    int last_sg = -1;                                    // the entry listed last (-1: none yet)
+    for (int e = 0; e < n; ++e) {
+        double bs = 0.0;
+        int bg = -1, bi = -1;
+        for (int i = lane; i < E; i += 64) {
+            const pfann_match_result &r = entry(i);
+            if (r.song < 0) continue;
+            if (last_sg >= 0 && !before(last_sc, last_sg, r.score, r.song)) continue;
+            if (bi < 0 || before(r.score, r.song, bs, bg)) { bs = r.score; bg = r.song; bi = i; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double vs = __shfl_xor(bs, o, 64);
+            const int vg = __shfl_xor(bg, o, 64), vi = __shfl_xor(bi, o, 64);
+            if (vi >= 0 && (bi < 0 || before(vs, vg, bs, bg))) { bs = vs; bg = vg; bi = vi; }
+        }
+        if (bi < 0) {                                    // nothing left: padding
+            for (int i = e + lane; i < n; i += 64) {
+                pfann_match_result res;
+                res.song = -1; res.offset = 0; res.shift = 0; res.n_cand = 0; res.score = -INFINITY;
+                top[w * n + i] = res;
+            }
+            return;
+        }
+        if (lane == 0) top[w * n + e] = entry(bi);
+        last_sc = bs; last_sg = bg;
+    }
+}
+
+int launch_dense_topn_merge(const pfann_match_result *tops, const int32_t *nf_parts, int n_parts, int64_t nW, int n,
+                            pfann_match_result *top, int32_t *n_found, hipStream_t s) {
+    if (nW <= 0) return 0;
+    ProfScope ps("seq_dense_topn_merge", s, (double)nW * n_parts * n * 24.0);
+    PF_LAUNCH(dense_topn_merge_kernel, dim3((unsigned)cdiv(nW, DN_MRG_NT / 64)), dim3(DN_MRG_NT), 0, s, tops, nf_parts, n_parts, nW, n,
+              top, n_found);
+    PF_HIP(hipGetLastError());
+    return 0;
+}
+
+// one launch loads the code object of this translation unit: every instantiation of the tile kernel (the SHARD ones included),
+// both selects, the decode and the two merges
 __global__ void noop_dense_kernel() {}
 int prewarm_dense() {
     hipLaunchKernelGGL(noop_dense_kernel, dim3(1), dim3(1), 0, 0);

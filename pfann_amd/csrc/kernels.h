@@ -191,6 +191,30 @@ struct DenseTopnArgs : DenseArgs {
 int dense_topn_wps(int window, int hop);
 int64_t dense_topn_slots(int64_t nW, int64_t nR, int window, int hop);
 int launch_match_windows_dense_topn(const DenseTopnArgs &a, hipStream_t s);
+// Song-sharded parts (pfann_match_windows_dense_part / _topn_part): db holds the GLOBAL rows [row_lo, row_lo + nrows), whole
+// songs; song_pos, n_songs and ntotal stay those of the whole database.
+struct DensePartArgs : DenseStatsArgs {     // results unused; stats null: no moments
+    int64_t row_lo, nrows;
+    unsigned long long *words;  // [nW] raw running-best words, zeroed by the launcher; not decoded
+};
+int launch_match_windows_dense_part(const DensePartArgs &a, hipStream_t s);
+struct DenseTopnPartArgs : DenseTopnArgs {  // song_scores unused; ws is [slot_n][wps][n_owned], indexed by song - song_lo
+    int64_t row_lo, nrows;
+    int song_lo, n_owned;
+};
+int launch_match_windows_dense_topn_part(const DenseTopnPartArgs &a, hipStream_t s);
+// pfann_match_windows_dense_merge: words[n_parts][nW] (and part_stats[n_parts][nW], or both stats pointers null) -> what the
+// whole database's call writes; every size is global
+struct DenseMergeArgs {
+    const int64_t *song_pos; int n_songs; int64_t ntotal, songs_with_rows;
+    const unsigned long long *words; const pfann_dense_stats *part_stats; int n_parts;
+    const int32_t *rlen; int64_t nR; int window; const int64_t *wfirst; int64_t nW; const int32_t *excl;
+    pfann_match_result *results; pfann_dense_stats *stats;
+};
+int launch_dense_merge(const DenseMergeArgs &a, hipStream_t s);
+// pfann_match_windows_dense_topn_merge: tops[n_parts][nW][n], nf_parts[n_parts][nW] (null exactly when n_found is)
+int launch_dense_topn_merge(const pfann_match_result *tops, const int32_t *nf_parts, int n_parts, int64_t nW, int n,
+                            pfann_match_result *top, int32_t *n_found, hipStream_t s);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is per device
 int ensure_dyn_lds(const void *func, int bytes);
 

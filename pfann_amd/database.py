@@ -535,6 +535,104 @@ class DeviceIndex:
             return (top, n_found, ss), wfirst
         return self.topn_to_host(top, n_found) + (ss.cpu().numpy() if ss is not None else None,), wfirst
 
+    # ---- the dense matcher over song-sharded handles: a part per handle, one merge (include/pfann_amd.h) ----------------
+    def _dense_windows(self, what, rstart, rlen, window, hop, exclude_song):
+        """the windowed arguments the four sharded dense calls share -> (window, hop, nR, nW, wfirst, device rstart, rlen,
+        wfirst, exclude_song or None)"""
+        window, hop = int(window), int(hop)
+        if window < 1 or hop < 1:
+            raise ValueError("%s: window and hop are positive numbers of segments (got %r, %r)" % (what, window, hop))
+        rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
+        nR = int(rl_np.shape[0])
+        assert rs_np.shape[0] == nR, "one start per recording"
+        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
+        ex = None
+        if exclude_song is not None:
+            ex_np = np.ascontiguousarray(exclude_song, dtype=np.int32)
+            if ex_np.shape != (nR,):
+                raise ValueError("%s: exclude_song wants one song id per recording (%d), got %r" % (what, nR, ex_np.shape))
+            ex = _l.upload_async(ex_np, self.device, np.int32)
+        rs, rl = self._upload_ranges(rs_np, rl_np)
+        return window, hop, nR, int(wfirst[-1]), wfirst, rs, rl, _l.upload_async(wfirst, self.device, np.int64), ex
+
+    def match_windows_dense_part(self, q, rstart, rlen, window, hop, exclude_song=None, stats=False):
+        """This handle's part of match_windows_dense / _stats (pfann_match_windows_dense_part): the handle may hold a shard.
+        -> ((words int64 [nW]: the bit patterns of the windows' raw running-best words, 0 where this handle has no candidate;
+        the statistics int64 [nW, 3] over this handle's full candidates, or None), wfirst); device tensors for dense_merge."""
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_windows("match_windows_dense_part", rstart, rlen, window, hop,
+                                                                          exclude_song)
+        q = q.to(self.device, torch.float32).contiguous()
+        assert nR == 0 or int((np.asarray(rstart, dtype=np.int64) + np.asarray(rlen, dtype=np.int64)).max()) <= q.shape[0], \
+            "recordings exceed the rows given"
+        words = torch.empty((nW,), device=self.device, dtype=torch.int64)
+        st = torch.empty((nW, 3), device=self.device, dtype=torch.int64) if stats else None
+        if nW:
+            _l.check(self.lib.pfann_match_windows_dense_part(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
+                                                             wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
+                                                             words.data_ptr(), st.data_ptr() if st is not None else None,
+                                                             self._stream()), "pfann_match_windows_dense_part")
+        return (words, st), wfirst
+
+    def dense_merge(self, words, part_stats, rlen, window, hop, exclude_song=None):
+        """words int64 [parts, nW] (and part_stats int64 [parts, nW, 3] or None) of match_windows_dense_part over handles that cut
+        the song list, in any order -> (results uint8 [nW, 24], statistics int64 [nW, 3] or None): byte for byte what
+        match_windows_dense / _stats give on one handle of the whole database (pfann_match_windows_dense_merge).  Any handle of
+        the database can merge."""
+        window, hop, nR, nW, wfirst, _, rl, wf, ex = self._dense_windows("dense_merge", np.zeros(len(rlen), dtype=np.int64), rlen,
+                                                                         window, hop, exclude_song)
+        words = words.to(self.device, torch.int64).contiguous()
+        parts = int(words.shape[0])
+        assert tuple(words.shape) == (parts, nW), "words is [parts, windows]"
+        if part_stats is not None:
+            part_stats = part_stats.to(self.device, torch.int64).contiguous()
+            assert tuple(part_stats.shape) == (parts, nW, 3), "part_stats is [parts, windows, 3]"
+        res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        st = torch.empty((nW, 3), device=self.device, dtype=torch.int64) if part_stats is not None else None
+        if nW:
+            _l.check(self.lib.pfann_match_windows_dense_merge(self.handle, words.data_ptr(),
+                                                              part_stats.data_ptr() if part_stats is not None else None, parts,
+                                                              rl.data_ptr(), nR, window, wf.data_ptr(), nW,
+                                                              ex.data_ptr() if ex is not None else None, res.data_ptr(),
+                                                              st.data_ptr() if st is not None else None, self._stream()),
+                     "pfann_match_windows_dense_merge")
+        return res, st
+
+    def match_windows_dense_topn_part(self, q, rstart, rlen, window, hop, n, exclude_song=None):
+        """This handle's part of match_windows_dense_topn (pfann_match_windows_dense_topn_part): the n best of its owned songs for
+        every window, no per-song block.  -> ((top uint8 [nW, n, 24], n_found int32 [nW]), wfirst); device tensors."""
+        n = int(n)
+        if not 1 <= n <= 64:
+            raise _l.PfannError("match_windows_dense_topn_part: n=%d outside 1..64" % n)
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_windows("match_windows_dense_topn_part", rstart, rlen, window, hop,
+                                                                          exclude_song)
+        q = q.to(self.device, torch.float32).contiguous()
+        assert nR == 0 or int((np.asarray(rstart, dtype=np.int64) + np.asarray(rlen, dtype=np.int64)).max()) <= q.shape[0], \
+            "recordings exceed the rows given"
+        top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
+        if nW:
+            _l.check(self.lib.pfann_match_windows_dense_topn_part(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window,
+                                                                  hop, wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
+                                                                  n, top.data_ptr(), n_found.data_ptr(), self._stream()),
+                     "pfann_match_windows_dense_topn_part")
+        return (top, n_found), wfirst
+
+    def dense_topn_merge(self, tops, n_found_parts):
+        """tops uint8 [parts, nW, n, 24] and n_found_parts int32 [parts, nW] of match_windows_dense_topn_part, parts in any order
+        -> (top uint8 [nW, n, 24], n_found int32 [nW]): byte for byte match_windows_dense_topn on one handle of the whole
+        database (pfann_match_windows_dense_topn_merge)."""
+        tops = tops.to(self.device, torch.uint8).contiguous()
+        n_found_parts = n_found_parts.to(self.device, torch.int32).contiguous()
+        parts, nW, n = int(tops.shape[0]), int(tops.shape[1]), int(tops.shape[2])
+        assert tops.shape[3] == ctypes.sizeof(_l.MatchResult) and tuple(n_found_parts.shape) == (parts, nW)
+        top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
+        if nW:
+            _l.check(self.lib.pfann_match_windows_dense_topn_merge(self.handle, tops.data_ptr(), n_found_parts.data_ptr(), parts, nW,
+                                                                   n, top.data_ptr(), n_found.data_ptr(), self._stream()),
+                     "pfann_match_windows_dense_topn_merge")
+        return top, n_found
+
 
 def window_counts(rlen, window, hop):
     """windows per recording (include/pfann_amd.h, pfann_match_windows): starts 0, hop, 2*hop, .. while w0 + window <= L;
@@ -889,7 +987,8 @@ class Database:
         return out, land
 
     def _answers(self, res, mode, tuples=result_tuples):
-        return tuples(res, mode, self.frame_shift_mul, self.hop_size, empty_db=self.index.ntotal == 0)
+        # (the WHOLE database: under ranks a shard may be empty while the answers are those of all shards)
+        return tuples(res, mode, self.frame_shift_mul, self.hop_size, empty_db=int(self.song_pos[-1]) == 0)
 
     def query_finish(self, p, reuse_buffers=False):
         """Second half: wait for that group only and return the list of (score, (song, time), song_score|None).
@@ -957,16 +1056,30 @@ class Database:
         return self._launch(emb, match)
 
     def _dense_check(self, what):
-        """the dense matcher is defined for the default family only: whole database, mode 0, frame_shift_mul 1, score_alpha 0"""
-        if self.sharded is not None:
-            raise _l.PfannError("%s: the dense matcher is not song-sharded: the whole database sits on one handle (run without "
-                                "PFANN_GPUS / ranks)" % what)
+        """the dense matcher is defined for the default family only: mode 0, frame_shift_mul 1, score_alpha 0.  Under ranks its
+        windowed forms are collective (dist.ShardedIndex.dense_windows_global / dense_windows_topn_global)."""
         if self.frame_shift_mul != 1:
             raise _l.PfannError("%s: the dense matcher needs frame_shift_mul 1 (the database has %r)" % (what, self.frame_shift_mul))
         if self.score_alpha != 0:
             raise _l.PfannError("%s: the dense matcher needs score_alpha 0 (the database has %r)" % (what, self.score_alpha))
         if default_mode() != 0:
             raise _l.PfannError("%s: the dense matcher is the python path's form; the native mode (cpp_accelerate) is in effect" % what)
+
+    def _dense_windows(self, emb, rstart, rlen, window, hop, stats=False):
+        """-> ((results, statistics or None), wfirst) on the device: one handle, or under ranks part + all-gather + merge"""
+        if self.sharded is not None:
+            return self.sharded.dense_windows_global(emb, rstart, rlen, window, hop, stats=stats)
+        if stats:
+            return self.index.match_windows_dense_stats(emb, rstart, rlen, window, hop, to_host=False)
+        res, wfirst = self.index.match_windows_dense(emb, rstart, rlen, window, hop, to_host=False)
+        return (res, None), wfirst
+
+    def _dense_windows_topn(self, emb, rstart, rlen, window, hop, n, want_song_scores=False):
+        """-> ((top, n_found, block or None), wfirst) on the device, as _dense_windows; no per-song block under ranks"""
+        if self.sharded is not None:
+            (top, n_found), wfirst = self.sharded.dense_windows_topn_global(emb, rstart, rlen, window, hop, n)
+            return (top, n_found, None), wfirst
+        return self.index.match_windows_dense_topn(emb, rstart, rlen, window, hop, n, want_song_scores=want_song_scores, to_host=False)
 
     def _launch_dense(self, emb, match):
         """_launch without a search: the three timed events with an empty search stage, mode 0"""
@@ -985,10 +1098,12 @@ class Database:
         self._dense_check("monitor_dense_launch")
 
         def match():
-            windows = lambda w, h: self.index.match_windows_dense(emb, rstart, rlen, w, h, to_host=False)
+            def windows(w, h):
+                (res, _), wfirst = self._dense_windows(emb, rstart, rlen, w, h)
+                return res, wfirst
             out = {}
             if stats:
-                (res, out["stats"]), wfirst = self.index.match_windows_dense_stats(emb, rstart, rlen, window, hop, to_host=False)
+                (res, out["stats"]), wfirst = self._dense_windows(emb, rstart, rlen, window, hop, stats=True)
                 out["rows_of"] = (int(window), np.asarray(rlen, dtype=np.int64))
             else:
                 res, wfirst = windows(window, hop)
@@ -1021,7 +1136,7 @@ class Database:
 
         def match():
             def windows(w, h):
-                (top, n_found, _), wfirst = self.index.match_windows_dense_topn(emb, rstart, rlen, w, h, n, to_host=False)
+                (top, n_found, _), wfirst = self._dense_windows_topn(emb, rstart, rlen, w, h, n)
                 return (top, n_found), wfirst
             (top, n_found), wfirst = windows(window, hop)
             return {"res": top, "n_found": n_found, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None,
@@ -1040,14 +1155,16 @@ class Database:
         exactly one window over all its rows, and by the byte contract its answer does not depend on what it was batched with.
         No search.  The per-song block is converted to seconds where it lives, as query_launch does."""
         self._dense_check("query_dense_launch")
+        if want_song_scores and self.sharded is not None:
+            raise _l.PfannError("query_dense_launch: the per-song block is not song-sharded (want_song_scores=True needs the whole "
+                                "database on one handle: run without PFANN_GPUS / ranks)")
         ql = np.ascontiguousarray(qlen, dtype=np.int32)
         if ql.shape[0] and (int(ql.min()) < 1 or int(ql.max()) > 64):
             raise _l.PfannError("query_dense_launch: a query has 1..64 segments (got %d..%d)" % (int(ql.min()), int(ql.max())))
         window = int(ql.max()) if ql.shape[0] else 1
 
         def match():
-            (top, n_found, ss), wfirst = self.index.match_windows_dense_topn(emb, qstart, ql, window, 1, n,
-                                                                             want_song_scores=want_song_scores, to_host=False)
+            (top, n_found, ss), wfirst = self._dense_windows_topn(emb, qstart, ql, window, 1, n, want_song_scores)
             assert int(wfirst[-1]) == ql.shape[0]
             self.index.song_scores_to_seconds(ss, 1, self.hop_size)
             return {"res": top, "n_found": n_found, "ss": ss}
@@ -1212,6 +1329,9 @@ class Database:
             raise _l.PfannError("self_match: top=%d outside 1..64" % top)
         if dense:
             self._dense_check("self_match")
+        if dense and self.sharded is not None:
+            raise _l.PfannError("self_match: the dense self-match is not song-sharded: the whole database sits on one handle (run "
+                                "without PFANN_GPUS / ranks)")
         if self.sharded is not None:
             raise _l.PfannError("self-match is not song-sharded: the whole database sits on one handle (run without "
                                 "PFANN_GPUS / ranks)")

@@ -338,6 +338,26 @@ class ShardedIndex:
         allk = self._timed("key_allgather", all_gather_rows, keys, self.group)
         return self.b.pick_winner(allk, to_host=False), ss
 
+    def dense_windows_global(self, q, rstart, rlen, window, hop, exclude_song=None, stats=False):
+        """The dense matcher over every window of the recordings, song-sharded: q [rows, d] (identical on all ranks) ->
+        ((results uint8 [nW, 24], statistics int64 [nW, 3] or None), wfirst), device tensors identical on all ranks and byte
+        for byte what one handle of the whole database gives (pfann_match_windows_dense_part / _merge: the words carry global
+        ids, the statistics are integer sums).  Every rank scores its own songs' rows only; the words travel as int64 bit
+        patterns, 8 (with statistics 32) bytes per window and rank.  Nothing is read back."""
+        (words, st), wfirst = self.b.match_windows_dense_part(q, rstart, rlen, window, hop, exclude_song, stats)
+        allw = self._timed("dense_allgather", all_gather_rows, words, self.group)
+        alls = self._timed("dense_allgather", all_gather_rows, st, self.group) if stats else None
+        return self._timed("dense_merge", self.b.dense_merge, allw, alls, rlen, window, hop, exclude_song), wfirst
+
+    def dense_windows_topn_global(self, q, rstart, rlen, window, hop, n, exclude_song=None):
+        """The ranked dense matcher, song-sharded: -> ((top uint8 [nW, n, 24], n_found int32 [nW]), wfirst), device tensors
+        identical on all ranks, the bytes of pfann_match_windows_dense_topn on the whole database: every rank lists the n best
+        of its own songs, the lists are all-gathered (24 n bytes per window and rank) and merged on every rank."""
+        (top, n_found), wfirst = self.b.match_windows_dense_topn_part(q, rstart, rlen, window, hop, n, exclude_song)
+        allt = self._timed("dense_allgather", all_gather_rows, top, self.group)
+        alln = self._timed("dense_allgather", all_gather_rows, n_found, self.group)
+        return self._timed("dense_merge", self.b.dense_topn_merge, allt, alln), wfirst
+
     def query_batch(self, q, qstart, qlen, to_host=True):
         """-> structured array (song, offset, shift, score) per query, identical on all ranks.
         Everything between the search and the final result stays on the device: the owner-side results are packed

@@ -24,6 +24,12 @@ columns; windows of at most 64 segments; not together with `--top N` > 1 here: r
 (pfann_match_windows_dense_topn, Database.monitor_dense_topn_launch / monitor_dense_topn_finish), this tool does not route
 `--dense --top N` to them yet.
 
+`PFANN_GPUS=N python monitor.py ... --dense [--max-fa X]` (or the same command under torch.distributed.run) shards the
+database by whole songs over N GPUs: every rank scores every window against its own songs' rows only
+(pfann_match_windows_dense_part), the ranks' words and integer sums are all-gathered and merged
+(pfann_match_windows_dense_merge), and rank 0 writes both files -- byte for byte the files of one process.  Without `--dense`
+several ranks are refused (status 2): the nominated forms are not song-sharded.
+
 `--max-fa X` (with `--dense`, 0 < X <= 1) replaces the fixed `--min-score` by a threshold calibrated per window: the dense
 matcher also returns the mean and the variance of the window's other alignments (pfann_match_windows_dense_stats), and
 pfann_amd/significance.py turns the best score into log10_fa, log10 of the chance that the best of that many chance alignments
@@ -241,7 +247,8 @@ def parse_args(argv):
 def main(argv=None):
     argv = sys.argv if argv is None else argv
     args = parse_args(argv)
-    if int(os.environ.get("PFANN_GPUS", "1") or 1) > 1 or int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+    several = int(os.environ.get("PFANN_GPUS", "1") or 1) > 1 or int(os.environ.get("WORLD_SIZE", "1") or 1) > 1
+    if several and not args.dense:                       # (only the dense matcher merges song shards: pfann_amd/dist.py)
         print("monitor: a recording is matched on ONE GPU against the whole database; song-sharded multi-GPU monitor mode "
               "is not supported (unset PFANN_GPUS)", file=sys.stderr)
         return 2
@@ -263,32 +270,45 @@ def main(argv=None):
     if args.max_fa is not None and not 0.0 < args.max_fa <= 1.0:
         print("monitor: --max-fa is a false-alarm probability, 0 < X <= 1", file=sys.stderr)
         return 2
+    from .dist import self_launch_if_asked
+    rc = self_launch_if_asked(argv)                      # PFANN_GPUS=N: N ranks of this command, one per GPU
+    if rc is not None:
+        return rc
     import torch
-    from .builder import embed_file_batches
+    from .builder import embed_file_batches, gather_round
     from .database import Database, launch_ahead
+    from .dist import finish_ranks, init_ranks
     from .engine import Engine
     from .musicdata import MusicDataset
     from .utils import StageTimer, init_logger, read_config
 
+    # several ranks (--dense only): every rank holds the rows of its own songs, reads and embeds its share of the recordings,
+    # gets the others' fingerprints (gather_round) and takes part in every launch; all ranks hold the same answers and rank 0
+    # writes them -- byte for byte the files of a single process
+    ranks = init_ranks()                                 # None: a plain single-process run
+    multi = ranks is not None and ranks.world > 1
+    rank0 = ranks is None or ranks.rank == 0
+    dev = ranks.device if ranks is not None else 0
     params = read_config(os.path.join(args.db, "configs.json"))
-    init_logger("monitor")
+    if rank0:
+        init_logger("monitor")
     window = args.window if args.window is not None else default_window(params)
     edge_window = args.edge_window if args.edge_window is not None else window // 3 + 1
     fsm = params["indexer"].get("frame_shift_mul", 1)
     seg_step_s = params["hop_size"] / fsm                # seconds between two segments
     max_batch = int(os.environ.get("PFANN_MAX_BATCH", "9728"))
     dataset = MusicDataset(args.recordings, params)
-    engine = Engine(params, 0, max_batch=max_batch)
-    engine.set_plan_batch(max_batch)
+    engine = Engine(params, dev, max_batch=max_batch)
+    engine.set_plan_batch(max_batch)                     # (fingerprint bits do not depend on the batch a recording is embedded in)
     if not engine.weights_loaded:
         engine.load_state_dict(torch.load(os.path.join(args.db, "model.pt"), map_location="cpu"))
-    db = Database(args.db, params["indexer"], params["hop_size"], device=0, d=params["model"]["d"])
+    db = Database(args.db, params["indexer"], params["hop_size"], device=dev, d=params["model"]["d"], ranks=ranks)
     timer = StageTimer()
     db.timer = timer
     stem = os.path.splitext(args.result)[0]
     n_windows = n_det = 0
-    with open(args.result, "w", encoding="utf8", newline="\n") as fout, \
-            open(stem + "_windows.csv", "w", encoding="utf8", newline="\n") as fwin:
+    with open(args.result if rank0 else os.devnull, "w", encoding="utf8", newline="\n") as fout, \
+            open(stem + "_windows.csv" if rank0 else os.devnull, "w", encoding="utf8", newline="\n") as fwin:
         wcsv = csv.writer(fwin)
         wcsv.writerow(WINDOWS_HEADER + (["rank", "votes"] if args.top > 1 else []) + (["log10_fa"] if args.max_fa is not None else []))
 
@@ -358,12 +378,17 @@ def main(argv=None):
                     fout.write("%s\t%.3f\t%.3f\t%s\t%.3f\t%.6f\t%.6f\t%d\n" % (name, d0, d1, db.songList[song], s0, mean, best, nw))
                     n_det += 1
 
-        for launched in launch_ahead(embed_file_batches(engine, dataset, dataset.hop, batch_windows=max_batch, timer=timer), launch):
+        groups = embed_file_batches(engine, dataset, dataset.hop, batch_windows=max_batch, timer=timer, ranks=ranks)
+        if multi:
+            groups = (gather_round(ranks, rnd, engine.d, engine.device) for rnd in groups)
+        for launched in launch_ahead(groups, launch):
             finish(launched)
     timer.resolve(wait=True)
-    for name, secs in timer.t.items():
-        print("%s %.6fs" % (name, secs))
-    print("monitor: %d recordings, %d windows (window %d, hop %d), %d detections" % (len(dataset), n_windows, window, args.hop, n_det))
+    if rank0:
+        for name, secs in timer.t.items():
+            print("%s %.6fs" % (name, secs))
+        print("monitor: %d recordings, %d windows (window %d, hop %d), %d detections" % (len(dataset), n_windows, window, args.hop, n_det))
+    finish_ranks(ranks)
     return 0
 
 
