@@ -1238,6 +1238,16 @@ int pfann_match_topn(pfann_db *db, const float *q, const int64_t *labels, int k,
                       nullptr, n, top, n_found, stream);
 }
 
+// a recording is matched against ALL songs by one GPU: a shard of a song-sharded database cannot answer
+static bool db_is_whole(const pfann_db *db) {
+    return db->label_base == 0 && db->song_lo == 0 && db->song_hi == db->n_songs && !db->song_pos_h.empty() &&
+           db->song_pos_h.back() == db->n;
+}
+static int refuse_shard() {
+    set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
+    return -1;
+}
+
 int pfann_match_windows(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart, const int32_t *rlen,
                         int64_t nR, int window, int hop, int frame_shift_mul, float score_alpha, int mode,
                         const int64_t *wfirst, pfann_match_result *results, void *stream) {
@@ -1246,12 +1256,7 @@ int pfann_match_windows(pfann_db *db, const float *q, const int64_t *labels, int
     if (db->d % 4 != 0) { set_error("match_windows: d %% 4 != 0 (d=%d)", db->d); return -1; }
     if (window < 1 || hop < 1 || k < 1 || nR < 0) { set_error("match_windows: window=%d hop=%d k=%d nR=%lld", window, hop, k, (long long)nR); return -1; }
     if (mode != 0 && mode != 1) { set_error("match_windows: unknown mode %d", mode); return -1; }
-    // a recording is matched against ALL songs by one GPU: a shard of a song-sharded database cannot answer
-    if (db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
-        db->song_pos_h.empty() || db->song_pos_h.back() != db->n) {
-        set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
-        return -1;
-    }
+    if (!db_is_whole(db)) return refuse_shard();
     if (nR == 0) return 0;
     const int C = match_windows_chunk(k, window, hop);
     // PFANN_WINDOWS_GENERAL=1: every call takes the general path (A/B timing, tests); read per call, no process state
@@ -1296,89 +1301,122 @@ int pfann_match_windows(pfann_db *db, const float *q, const int64_t *labels, int
     return 0;
 }
 
-// pfann_match_windows_dense (stats == nullptr) and pfann_match_windows_dense_stats: one set of refusals, `what` names the call
-static int match_windows_dense_impl(const char *what, pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen,
-                                    int64_t nR, int window, int hop, const int64_t *wfirst, int64_t n_windows,
-                                    const int32_t *excl_song, pfann_match_result *results, pfann_dense_stats *stats, void *stream) {
-    PF_HIP(hipSetDevice(db->device));
-    if (db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
-        db->song_pos_h.empty() || db->song_pos_h.back() != db->n) {
-        set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
+// ---- dense matcher: the three calls on one handle of the whole database, the parts on any fp32 handle, the merges on any handle
+// The refusals the calls share, in the order each call has always reported them.  whole: the handle must hold the whole database,
+// and window, hop, nR and n_windows are one refusal; otherwise window is checked before the id bound and the rest after it.
+// needs_rows: the call reads the handle's rows (everything but pfann_match_windows_dense_merge, which passes hop 1).  The id
+// bound is that of the WHOLE database (every handle has its song_pos).
+static int dense_check(const char *what, pfann_db *db, int window, int hop, int64_t nR, int64_t n_windows, bool needs_rows, bool whole) {
+    if (whole) {
+        if (!db_is_whole(db)) return refuse_shard();
+    } else if (db->song_pos_h.empty()) {
+        set_error("%s: no database loaded", what);
         return -1;
     }
-    if (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr)) {
+    if (needs_rows && (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr))) {
         set_error("%s: fp16-only storage (the dense matcher scores fp32 rows)", what);
         return -1;
     }
-    if (db->d % 4 != 0) { set_error("%s: d %% 4 != 0 (d=%d)", what, db->d); return -1; }
-    if (window < 1 || window > 64 || hop < 1 || nR < 0 || n_windows < 0) {
+    if (needs_rows && db->d % 4 != 0) { set_error("%s: d %% 4 != 0 (d=%d)", what, db->d); return -1; }
+    const bool counts_bad = hop < 1 || nR < 0 || n_windows < 0;
+    // whole handles: window and the counts are ONE refusal, so of everything below only the id bound can still fire for them
+    if (whole && (window < 1 || window > 64 || counts_bad)) {
         set_error("%s: window=%d (1..64) hop=%d nR=%lld n_windows=%lld", what, window, hop, (long long)nR, (long long)n_windows);
         return -1;
     }
-    if (db->n + (int64_t)db->n_songs * (window - 1) >= (1ll << 32)) {
-        set_error("%s: %lld rows and %d songs at window %d do not fit the 32-bit alignment id", what, (long long)db->n,
+    // parts and the merge: window, the id bound, (parts) rows against songs, the counts
+    if (window < 1 || window > 64) { set_error("%s: window=%d outside 1..64", what, window); return -1; }
+    if (db->song_pos_h.back() + (int64_t)db->n_songs * (window - 1) >= (1ll << 32)) {
+        set_error("%s: %lld rows and %d songs at window %d do not fit the 32-bit alignment id", what, (long long)db->song_pos_h.back(),
                   db->n_songs, window);
         return -1;
     }
-    if (nR == 0 || n_windows == 0) return 0;
+    // the owned songs span exactly the handle's rows (pfann_db_load, pfann_db_set_owned_songs): the ranked workspace relies on it
+    // (a whole handle passed db_is_whole above, which says the same)
+    if (needs_rows && !whole && (db->song_lo < 0 || db->song_hi < db->song_lo || db->song_hi > db->n_songs ||
+                                 db->song_pos_h[db->song_lo] != db->label_base || db->song_pos_h[db->song_hi] != db->label_base + db->n)) {
+        set_error("%s: the handle's rows [%lld,%lld) are not its songs [%d,%d)", what, (long long)db->label_base,
+                  (long long)(db->label_base + db->n), db->song_lo, db->song_hi);
+        return -1;
+    }
+    if (counts_bad) {
+        if (needs_rows) set_error("%s: hop=%d nR=%lld n_windows=%lld", what, hop, (long long)nR, (long long)n_windows);
+        else set_error("%s: nR=%lld n_windows=%lld", what, (long long)nR, (long long)n_windows);
+        return -1;
+    }
+    return 0;
+}
+
+// songs of the database with len > 0 (n_cand)
+static int64_t songs_with_rows(const pfann_db *db) {
     int64_t with_rows = 0;
     for (int s = 0; s < db->n_songs; ++s) with_rows += db->song_pos_h[s + 1] > db->song_pos_h[s];
-    DenseStatsArgs a;
-    a.db = db->emb; a.ntotal = db->n; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+    return with_rows;
+}
+
+// what every form of the tile kernel takes from the handle and the call (after dense_check); the outputs of the form are the caller's
+static DenseArgs dense_args(const pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
+                            int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song) {
+    DenseArgs a = {};
+    a.db = db->emb; a.ntotal = db->song_pos_h.back(); a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
     a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
-    a.nW = n_windows; a.excl = excl_song; a.results = results; a.stats = stats;
-    if (stats != nullptr) return launch_match_windows_dense_stats(a, with_rows, (hipStream_t)stream);
-    return launch_match_windows_dense(a, with_rows, (hipStream_t)stream);
+    a.nW = n_windows; a.excl = excl_song;
+    a.row_lo = db->label_base; a.nrows = db->n; a.song_lo = db->song_lo; a.n_owned = db->song_hi - db->song_lo;
+    return a;
+}
+
+// the unranked calls: pfann_match_windows_dense / _stats (results, and stats or null) on a whole handle, _part (words, and stats
+// or null) on any fp32 handle; `what` names the call
+static int dense_unranked_call(const char *what, pfann_db *db, bool shard, const float *q, const int64_t *rstart, const int32_t *rlen,
+                               int64_t nR, int window, int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
+                               pfann_match_result *results, uint64_t *words, pfann_dense_stats *stats, void *stream) {
+    PF_HIP(hipSetDevice(db->device));
+    if (shard && words == nullptr) { set_error("%s: words_dev is null", what); return -1; }
+    if (dense_check(what, db, window, hop, nR, n_windows, true, !shard)) return -1;
+    if (nR == 0 || n_windows == 0) return 0;
+    DenseArgs a = dense_args(db, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song);
+    a.results = results; a.words = reinterpret_cast<unsigned long long *>(words); a.stats = stats;
+    return launch_dense_unranked(a, shard, shard ? 0 : songs_with_rows(db), (hipStream_t)stream);
 }
 
 int pfann_match_windows_dense(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
                               int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
                               pfann_match_result *results, void *stream) {
-    return match_windows_dense_impl("match_windows_dense", db, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song, results,
-                                    nullptr, stream);
+    return dense_unranked_call("match_windows_dense", db, false, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song,
+                               results, nullptr, nullptr, stream);
 }
 
 int pfann_match_windows_dense_stats(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
                                     int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
                                     pfann_match_result *results, pfann_dense_stats *stats, void *stream) {
     if (stats == nullptr) { set_error("match_windows_dense_stats: stats_dev is null"); return -1; }
-    return match_windows_dense_impl("match_windows_dense_stats", db, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song,
-                                    results, stats, stream);
+    return dense_unranked_call("match_windows_dense_stats", db, false, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song,
+                               results, nullptr, stats, stream);
 }
 
-int pfann_match_windows_dense_topn(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
-                                   int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, int n,
-                                   pfann_match_result *top, int32_t *n_found, float *song_scores, void *stream) {
+int pfann_match_windows_dense_part(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
+                                   int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, uint64_t *words,
+                                   pfann_dense_stats *stats, void *stream) {
+    return dense_unranked_call("match_windows_dense_part", db, true, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song,
+                               nullptr, words, stats, stream);
+}
+
+// the ranked calls: pfann_match_windows_dense_topn on a whole handle, _topn_part (no per-song block) on any fp32 handle.  Chunks of
+// whole row-tile slots: the workspace holds 8 bytes per (window the chunk's slots can hold, song of the handle), at most 256 MB
+// unless one slot alone needs more; PFANN_DENSE_TOPN_WINDOWS (read per call) lowers the windows per chunk
+static int dense_ranked_call(const char *what, pfann_db *db, bool shard, const float *q, const int64_t *rstart, const int32_t *rlen,
+                             int64_t nR, int window, int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, int n,
+                             pfann_match_result *top, int32_t *n_found, float *song_scores, void *stream) {
     PF_HIP(hipSetDevice(db->device));
     hipStream_t st = (hipStream_t)stream;
-    if (n < 1 || n > 64) { set_error("match_windows_dense_topn: n=%d outside 1..64", n); return -1; }
-    if (top == nullptr) { set_error("match_windows_dense_topn: top_dev is null"); return -1; }
-    if (db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
-        db->song_pos_h.empty() || db->song_pos_h.back() != db->n) {
-        set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
-        return -1;
-    }
-    if (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr)) {
-        set_error("match_windows_dense_topn: fp16-only storage (the dense matcher scores fp32 rows)");
-        return -1;
-    }
-    if (db->d % 4 != 0) { set_error("match_windows_dense_topn: d %% 4 != 0 (d=%d)", db->d); return -1; }
-    if (window < 1 || window > 64 || hop < 1 || nR < 0 || n_windows < 0) {
-        set_error("match_windows_dense_topn: window=%d (1..64) hop=%d nR=%lld n_windows=%lld", window, hop, (long long)nR,
-                  (long long)n_windows);
-        return -1;
-    }
-    if (db->n + (int64_t)db->n_songs * (window - 1) >= (1ll << 32)) {
-        set_error("match_windows_dense_topn: %lld rows and %d songs at window %d do not fit the 32-bit alignment id", (long long)db->n,
-                  db->n_songs, window);
-        return -1;
-    }
+    if (n < 1 || n > 64) { set_error("%s: n=%d outside 1..64", what, n); return -1; }
+    if (top == nullptr) { set_error("%s: top_dev is null", what); return -1; }
+    if (dense_check(what, db, window, hop, nR, n_windows, true, !shard)) return -1;
     if (nR == 0 || n_windows == 0) return 0;
-    // chunks of whole row-tile slots: the workspace holds 8 bytes per (window the chunk's slots can hold, song), at most 256 MB
-    // unless one slot alone needs more; PFANN_DENSE_TOPN_WINDOWS (read per call) lowers the windows per chunk
+    DenseArgs a = dense_args(db, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song);
     const int wps = dense_topn_wps(window, hop);
     const int64_t n_slots = dense_topn_slots(n_windows, nR, window, hop);
-    const int64_t songs = std::max(db->n_songs, 1);
+    const int64_t songs = std::max(shard ? a.n_owned : a.n_songs, 1);
     int64_t cap = (256ll << 20) / (8 * songs);
     const char *env = getenv("PFANN_DENSE_TOPN_WINDOWS");
     if (env != nullptr && env[0] != 0 && atoll(env) > 0) cap = std::min<int64_t>(cap, atoll(env));
@@ -1392,62 +1430,27 @@ int pfann_match_windows_dense_topn(pfann_db *db, const float *q, const int64_t *
         db->dense_ws = grown;
         db->dense_ws_bytes = need;
     }
-    DenseTopnArgs a;
-    a.db = db->emb; a.ntotal = db->n; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
-    a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
-    a.nW = n_windows; a.excl = excl_song; a.results = nullptr;
     a.ws = reinterpret_cast<unsigned long long *>(db->dense_ws); a.wps = wps;
     a.n = n; a.top = top; a.n_found = n_found; a.song_scores = song_scores;
     for (int64_t s0 = 0; s0 < n_slots; s0 += step) {
         a.slot_lo = s0; a.slot_n = std::min(step, n_slots - s0);
-        if (launch_match_windows_dense_topn(a, st)) return -1;
+        if (launch_dense_ranked(a, shard, st)) return -1;
     }
     return 0;
 }
 
-// ---- song-sharded dense matcher: parts on any fp32 handle, merges on any handle of the database ------------------------------
-// the refusals every one of the four calls shares; the id bound is that of the WHOLE database (every handle has its song_pos)
-static int dense_shard_check(const char *what, pfann_db *db, int window, bool needs_rows) {
-    if (db->song_pos_h.empty()) { set_error("%s: no database loaded", what); return -1; }
-    if (needs_rows && (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr))) {
-        set_error("%s: fp16-only storage (the dense matcher scores fp32 rows)", what);
-        return -1;
-    }
-    if (needs_rows && db->d % 4 != 0) { set_error("%s: d %% 4 != 0 (d=%d)", what, db->d); return -1; }
-    if (window < 1 || window > 64) { set_error("%s: window=%d outside 1..64", what, window); return -1; }
-    if (db->song_pos_h.back() + (int64_t)db->n_songs * (window - 1) >= (1ll << 32)) {
-        set_error("%s: %lld rows and %d songs at window %d do not fit the 32-bit alignment id", what, (long long)db->song_pos_h.back(),
-                  db->n_songs, window);
-        return -1;
-    }
-    // the owned songs span exactly the handle's rows (pfann_db_load, pfann_db_set_owned_songs): the ranked workspace relies on it
-    if (needs_rows && (db->song_lo < 0 || db->song_hi < db->song_lo || db->song_hi > db->n_songs ||
-                       db->song_pos_h[db->song_lo] != db->label_base || db->song_pos_h[db->song_hi] != db->label_base + db->n)) {
-        set_error("%s: the handle's rows [%lld,%lld) are not its songs [%d,%d)", what, (long long)db->label_base,
-                  (long long)(db->label_base + db->n), db->song_lo, db->song_hi);
-        return -1;
-    }
-    return 0;
+int pfann_match_windows_dense_topn(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
+                                   int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, int n,
+                                   pfann_match_result *top, int32_t *n_found, float *song_scores, void *stream) {
+    return dense_ranked_call("match_windows_dense_topn", db, false, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song, n, top,
+                             n_found, song_scores, stream);
 }
 
-int pfann_match_windows_dense_part(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
-                                   int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, uint64_t *words,
-                                   pfann_dense_stats *stats, void *stream) {
-    const char *what = "match_windows_dense_part";
-    PF_HIP(hipSetDevice(db->device));
-    if (words == nullptr) { set_error("%s: words_dev is null", what); return -1; }
-    if (dense_shard_check(what, db, window, true)) return -1;
-    if (hop < 1 || nR < 0 || n_windows < 0) {
-        set_error("%s: hop=%d nR=%lld n_windows=%lld", what, hop, (long long)nR, (long long)n_windows);
-        return -1;
-    }
-    if (nR == 0 || n_windows == 0) return 0;
-    DensePartArgs a;
-    a.db = db->emb; a.ntotal = db->song_pos_h.back(); a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
-    a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
-    a.nW = n_windows; a.excl = excl_song; a.results = nullptr; a.stats = stats;
-    a.row_lo = db->label_base; a.nrows = db->n; a.words = reinterpret_cast<unsigned long long *>(words);
-    return launch_match_windows_dense_part(a, (hipStream_t)stream);
+int pfann_match_windows_dense_topn_part(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR,
+                                        int window, int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
+                                        int n, pfann_match_result *top, int32_t *n_found, void *stream) {
+    return dense_ranked_call("match_windows_dense_topn_part", db, true, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song, n,
+                             top, n_found, nullptr, stream);
 }
 
 int pfann_match_windows_dense_merge(pfann_db *db, const uint64_t *words, const pfann_dense_stats *part_stats, int n_parts,
@@ -1461,62 +1464,14 @@ int pfann_match_windows_dense_merge(pfann_db *db, const uint64_t *words, const p
         return -1;
     }
     if (n_parts < 1) { set_error("%s: n_parts=%d", what, n_parts); return -1; }
-    if (dense_shard_check(what, db, window, false)) return -1;
-    if (nR < 0 || n_windows < 0) { set_error("%s: nR=%lld n_windows=%lld", what, (long long)nR, (long long)n_windows); return -1; }
+    if (dense_check(what, db, window, 1, nR, n_windows, false, false)) return -1;
     if (nR == 0 || n_windows == 0) return 0;
     DenseMergeArgs a;
-    a.song_pos = db->song_pos; a.n_songs = db->n_songs; a.ntotal = db->song_pos_h.back(); a.songs_with_rows = 0;
-    for (int s = 0; s < db->n_songs; ++s) a.songs_with_rows += db->song_pos_h[s + 1] > db->song_pos_h[s];
+    a.song_pos = db->song_pos; a.n_songs = db->n_songs; a.ntotal = db->song_pos_h.back(); a.songs_with_rows = songs_with_rows(db);
     a.words = reinterpret_cast<const unsigned long long *>(words); a.part_stats = part_stats; a.n_parts = n_parts;
     a.rlen = rlen; a.nR = nR; a.window = window; a.wfirst = wfirst; a.nW = n_windows; a.excl = excl_song;
     a.results = results; a.stats = stats;
     return launch_dense_merge(a, (hipStream_t)stream);
-}
-
-int pfann_match_windows_dense_topn_part(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR,
-                                        int window, int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
-                                        int n, pfann_match_result *top, int32_t *n_found, void *stream) {
-    const char *what = "match_windows_dense_topn_part";
-    PF_HIP(hipSetDevice(db->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (n < 1 || n > 64) { set_error("%s: n=%d outside 1..64", what, n); return -1; }
-    if (top == nullptr) { set_error("%s: top_dev is null", what); return -1; }
-    if (dense_shard_check(what, db, window, true)) return -1;
-    if (hop < 1 || nR < 0 || n_windows < 0) {
-        set_error("%s: hop=%d nR=%lld n_windows=%lld", what, hop, (long long)nR, (long long)n_windows);
-        return -1;
-    }
-    if (nR == 0 || n_windows == 0) return 0;
-    // the chunks of pfann_match_windows_dense_topn, over the owned songs
-    const int wps = dense_topn_wps(window, hop);
-    const int64_t n_slots = dense_topn_slots(n_windows, nR, window, hop);
-    const int n_owned = db->song_hi - db->song_lo;
-    const int64_t songs = std::max(n_owned, 1);
-    int64_t cap = (256ll << 20) / (8 * songs);
-    const char *env = getenv("PFANN_DENSE_TOPN_WINDOWS");
-    if (env != nullptr && env[0] != 0 && atoll(env) > 0) cap = std::min<int64_t>(cap, atoll(env));
-    const int64_t step = std::min(n_slots, std::max<int64_t>(1, cap / wps));
-    const size_t need = (size_t)step * wps * songs * 8;
-    if (db->dense_ws_bytes < need) {                 // grow, then free: a failed allocation leaves the handle as it was
-        PF_HIP(hipStreamSynchronize(st));
-        void *grown = nullptr;
-        PF_HIP(hipMalloc(&grown, need));
-        if (db->dense_ws) (void)hipFree(db->dense_ws);
-        db->dense_ws = grown;
-        db->dense_ws_bytes = need;
-    }
-    DenseTopnPartArgs a;
-    a.db = db->emb; a.ntotal = db->song_pos_h.back(); a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
-    a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst;
-    a.nW = n_windows; a.excl = excl_song; a.results = nullptr;
-    a.ws = reinterpret_cast<unsigned long long *>(db->dense_ws); a.wps = wps;
-    a.n = n; a.top = top; a.n_found = n_found; a.song_scores = nullptr;
-    a.row_lo = db->label_base; a.nrows = db->n; a.song_lo = db->song_lo; a.n_owned = n_owned;
-    for (int64_t s0 = 0; s0 < n_slots; s0 += step) {
-        a.slot_lo = s0; a.slot_n = std::min(step, n_slots - s0);
-        if (launch_match_windows_dense_topn_part(a, st)) return -1;
-    }
-    return 0;
 }
 
 int pfann_match_windows_dense_topn_merge(pfann_db *db, const pfann_match_result *tops, const int32_t *n_found_parts, int n_parts,
@@ -1543,11 +1498,7 @@ int pfann_match_windows_topn(pfann_db *db, const float *q, const int64_t *labels
     if (db->d % 4 != 0) { set_error("match_windows_topn: d %% 4 != 0 (d=%d)", db->d); return -1; }
     if (window < 1 || hop < 1 || k < 1 || nR < 0) { set_error("match_windows_topn: window=%d hop=%d k=%d nR=%lld", window, hop, k, (long long)nR); return -1; }
     if (mode != 0 && mode != 1) { set_error("match_windows_topn: unknown mode %d", mode); return -1; }
-    if (db->label_base != 0 || db->song_lo != 0 || db->song_hi != db->n_songs ||
-        db->song_pos_h.empty() || db->song_pos_h.back() != db->n) {
-        set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
-        return -1;
-    }
+    if (!db_is_whole(db)) return refuse_shard();
     if (nR == 0) return 0;
     // the routing of pfann_match_windows, so that entry 0 and its answer come from the same summation order
     const int C = match_windows_chunk(k, window, hop);

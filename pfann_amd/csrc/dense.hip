@@ -36,7 +36,6 @@
 #include "kernels.h"
 #include "match_common.h"
 #include <algorithm>
-#include <type_traits>
 
 namespace pfann {
 
@@ -79,15 +78,11 @@ __device__ __forceinline__ int dn_windows_of(int L, int window, int hop) {
 // either end), and the song lookup, s_head and the id stay global: a candidate belongs to exactly one shard and gets there the
 // word it gets from the whole database.  The unranked form leaves the raw words (no decode), the ranked form indexes its
 // workspace by song - song_lo.  No new LDS; the instantiations without SHARD are the code they were before it existed.
-template <bool SHARD, bool RANKED, bool STATS> struct DenseKernelArgs {
-    typedef typename std::conditional<RANKED, DenseTopnArgs, typename std::conditional<STATS, DenseStatsArgs, DenseArgs>::type>::type type;
-};
-template <bool RANKED, bool STATS> struct DenseKernelArgs<true, RANKED, STATS> {
-    typedef typename std::conditional<RANKED, DenseTopnPartArgs, DensePartArgs>::type type;
-};
-
+//
+// All six instantiations take the one DenseArgs (kernels.h) and read only the groups of their form; launch_dense_unranked and
+// launch_dense_ranked, further down, pick the instantiation from (shard, stats != nullptr).
 template <bool RANKED, bool STATS = false, bool SHARD = false>
-__global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(typename DenseKernelArgs<SHARD, RANKED, STATS>::type a) {
+__global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a) {
     static_assert(!(RANKED && STATS), "the moments are kept by the unranked form");
     // S[DN_T][DN_LDS]; while the product runs its first bytes are the two K tiles As, Bs [DN_T][DN_LDK]
     extern __shared__ __attribute__((aligned(16))) float s_S[];          // DN_S_BYTES, dynamic: past the static 64 KB
@@ -458,60 +453,42 @@ int launch_dense_merge(const DenseMergeArgs &a, hipStream_t s) {
     return 0;
 }
 
-// the unranked tile kernel, with or without the moments, and the decode; Args = what that instantiation takes
-template <bool STATS, class Args>
-static int launch_dense_tiles(const Args &a, int64_t songs_with_rows, const char *tag, hipStream_t s) {
-    if (a.nR <= 0 || a.nW <= 0) return 0;
-    // every slot's running best starts empty (word 0: no number has the ordered bits 0)
-    PF_HIP(hipMemsetAsync(a.results, 0, (size_t)a.nW * sizeof(pfann_match_result), s));
-    if constexpr (STATS) PF_HIP(hipMemsetAsync(a.stats, 0, (size_t)a.nW * sizeof(pfann_dense_stats), s));
-    if (a.ntotal > 0) {
-        const int SI = DN_T - (a.window - 1);
-        const int64_t n_slots = a.nW * a.hop / SI + a.nR;
-        const int64_t NJ = (a.ntotal + a.window - 1 + SI - 1) / SI;
-        const int64_t n_items = n_slots * NJ;
-        const double rows = (double)a.nW * a.hop + (double)a.nR * a.window;
-        const auto kernel = match_windows_dense_kernel<false, STATS>;
-        if (ensure_dyn_lds((const void *)kernel, DN_S_BYTES)) return -1;
-        ProfScope ps(tag, s, 2.0 * rows * (double)a.ntotal * a.d);
-        PF_LAUNCH(kernel, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
-        PF_HIP(hipGetLastError());
-    }
-    PF_LAUNCH(dense_decode_kernel, dim3((unsigned)cdiv(a.nW, 256)), dim3(256), 0, s, static_cast<const DenseArgs &>(a), songs_with_rows);
-    PF_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipStream_t s) {
-    return launch_dense_tiles<false>(a, songs_with_rows, "seq_match_windows_dense", s);
-}
-
-int launch_match_windows_dense_stats(const DenseStatsArgs &a, int64_t songs_with_rows, hipStream_t s) {
-    return launch_dense_tiles<true>(a, songs_with_rows, "seq_match_windows_dense_stats", s);
-}
-
-// the raw words (and moments) of the handle's rows; no decode: pfann_match_windows_dense_merge does it over all parts
-template <bool STATS>
-static int launch_dense_part_tiles(const DensePartArgs &a, hipStream_t s) {
-    PF_HIP(hipMemsetAsync(a.words, 0, (size_t)a.nW * sizeof(unsigned long long), s));
-    if constexpr (STATS) PF_HIP(hipMemsetAsync(a.stats, 0, (size_t)a.nW * sizeof(pfann_dense_stats), s));
-    if (a.nrows <= 0) return 0;                          // a shard without rows: no tile
+// the tile kernel of one form over the rows this handle holds; work_rows: the recording rows of the profile's figure
+template <bool RANKED, bool STATS, bool SHARD>
+static int launch_dense_tiles(const DenseArgs &a, int64_t slot_n, const char *tag, double work_rows, hipStream_t s) {
+    const int64_t rows = SHARD ? a.nrows : a.ntotal;
+    if (rows <= 0) return 0;                             // a database or a shard without rows: no tile
     const int SI = DN_T - (a.window - 1);
-    const int64_t n_slots = a.nW * a.hop / SI + a.nR;
-    const int64_t NJ = (a.nrows + a.window - 1 + SI - 1) / SI;
-    const int64_t n_items = n_slots * NJ;
-    const double rows = (double)a.nW * a.hop + (double)a.nR * a.window;
-    const auto kernel = match_windows_dense_kernel<false, STATS, true>;
+    const int64_t NJ = (rows + a.window - 1 + SI - 1) / SI;
+    const int64_t n_items = slot_n * NJ;
+    const auto kernel = match_windows_dense_kernel<RANKED, STATS, SHARD>;
     if (ensure_dyn_lds((const void *)kernel, DN_S_BYTES)) return -1;
-    ProfScope ps("seq_match_windows_dense_part", s, 2.0 * rows * (double)a.nrows * a.d);
+    ProfScope ps(tag, s, 2.0 * work_rows * (double)rows * a.d);
     PF_LAUNCH(kernel, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
     PF_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_match_windows_dense_part(const DensePartArgs &a, hipStream_t s) {
+// the unranked forms.  A whole handle's words are decoded in place; a shard's stay raw: pfann_match_windows_dense_merge decodes
+// the maximum over all parts
+int launch_dense_unranked(const DenseArgs &a, bool shard, int64_t songs_with_rows, hipStream_t s) {
     if (a.nR <= 0 || a.nW <= 0) return 0;
-    return a.stats != nullptr ? launch_dense_part_tiles<true>(a, s) : launch_dense_part_tiles<false>(a, s);
+    // every slot's running best starts empty (word 0: no number has the ordered bits 0)
+    if (shard) PF_HIP(hipMemsetAsync(a.words, 0, (size_t)a.nW * sizeof(unsigned long long), s));
+    else PF_HIP(hipMemsetAsync(a.results, 0, (size_t)a.nW * sizeof(pfann_match_result), s));
+    const bool stats = a.stats != nullptr;
+    if (stats) PF_HIP(hipMemsetAsync(a.stats, 0, (size_t)a.nW * sizeof(pfann_dense_stats), s));
+    const int64_t n_slots = dense_topn_slots(a.nW, a.nR, a.window, a.hop);
+    const double work = (double)a.nW * a.hop + (double)a.nR * a.window;
+    int rc;
+    if (shard) rc = stats ? launch_dense_tiles<false, true, true>(a, n_slots, "seq_match_windows_dense_part", work, s)
+                          : launch_dense_tiles<false, false, true>(a, n_slots, "seq_match_windows_dense_part", work, s);
+    else rc = stats ? launch_dense_tiles<false, true, false>(a, n_slots, "seq_match_windows_dense_stats", work, s)
+                    : launch_dense_tiles<false, false, false>(a, n_slots, "seq_match_windows_dense", work, s);
+    if (rc || shard) return rc;
+    PF_LAUNCH(dense_decode_kernel, dim3((unsigned)cdiv(a.nW, 256)), dim3(256), 0, s, a, songs_with_rows);
+    PF_HIP(hipGetLastError());
+    return 0;
 }
 
 // ---- ranked: ws -> the n best songs of every window of the chunk (pfann_match_windows_dense_topn) --------------------------
@@ -524,7 +501,7 @@ static constexpr int DN_SEL_NT = 256;
 
 // SHARD: the words of the handle's owned songs, ws[..][song - song_lo]; entries carry the global song; no per-song block.
 template <bool SHARD>
-__global__ __launch_bounds__(DN_SEL_NT) void dense_select_kernel(typename std::conditional<SHARD, DenseTopnPartArgs, DenseTopnArgs>::type a) {
+__global__ __launch_bounds__(DN_SEL_NT) void dense_select_kernel(DenseArgs a) {
     __shared__ unsigned long long s_max[2][DN_SEL_NT / 64];
     __shared__ int s_cnt[DN_SEL_NT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -622,41 +599,18 @@ __global__ __launch_bounds__(DN_SEL_NT) void dense_select_kernel(typename std::c
 int dense_topn_wps(int window, int hop) { return (DN_T - (window - 1) + hop - 1) / hop; }
 int64_t dense_topn_slots(int64_t nW, int64_t nR, int window, int hop) { return nW * hop / (DN_T - (window - 1)) + nR; }
 
-int launch_match_windows_dense_topn(const DenseTopnArgs &a, hipStream_t s) {
+int launch_dense_ranked(const DenseArgs &a, bool shard, hipStream_t s) {
     if (a.nR <= 0 || a.nW <= 0 || a.slot_n <= 0) return 0;
-    const int SI = DN_T - (a.window - 1);
     const int64_t rows = a.slot_n * a.wps;               // windows the chunk's slots can hold
-    if (a.n_songs > 0) PF_HIP(hipMemsetAsync(a.ws, 0, (size_t)rows * a.n_songs * sizeof(unsigned long long), s));
-    if (a.ntotal > 0) {
-        const int64_t NJ = (a.ntotal + a.window - 1 + SI - 1) / SI;
-        const int64_t n_items = a.slot_n * NJ;
-        if (ensure_dyn_lds((const void *)match_windows_dense_kernel<true>, DN_S_BYTES)) return -1;
-        ProfScope ps("seq_match_windows_dense_topn", s, 2.0 * (double)a.slot_n * DN_T * (double)a.ntotal * a.d);
-        PF_LAUNCH(match_windows_dense_kernel<true>, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
-        PF_HIP(hipGetLastError());
-    }
-    ProfScope ps("seq_dense_select", s, (double)rows * a.n_songs * 8.0);
-    PF_LAUNCH(dense_select_kernel<false>, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);
-    PF_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_match_windows_dense_topn_part(const DenseTopnPartArgs &a, hipStream_t s) {
-    if (a.nR <= 0 || a.nW <= 0 || a.slot_n <= 0) return 0;
-    const int SI = DN_T - (a.window - 1);
-    const int64_t rows = a.slot_n * a.wps;
-    if (a.n_owned > 0) PF_HIP(hipMemsetAsync(a.ws, 0, (size_t)rows * a.n_owned * sizeof(unsigned long long), s));
-    if (a.nrows > 0) {
-        const int64_t NJ = (a.nrows + a.window - 1 + SI - 1) / SI;
-        const int64_t n_items = a.slot_n * NJ;
-        const auto kernel = match_windows_dense_kernel<true, false, true>;
-        if (ensure_dyn_lds((const void *)kernel, DN_S_BYTES)) return -1;
-        ProfScope ps("seq_match_windows_dense_topn_part", s, 2.0 * (double)a.slot_n * DN_T * (double)a.nrows * a.d);
-        PF_LAUNCH(kernel, dim3((unsigned)std::min<int64_t>(n_items, DN_GRID)), dim3(DN_NT), DN_S_BYTES, s, a);
-        PF_HIP(hipGetLastError());
-    }
-    ProfScope ps("seq_dense_select", s, (double)rows * a.n_owned * 8.0);
-    PF_LAUNCH(dense_select_kernel<true>, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);
+    const int songs = shard ? a.n_owned : a.n_songs;
+    if (songs > 0) PF_HIP(hipMemsetAsync(a.ws, 0, (size_t)rows * songs * sizeof(unsigned long long), s));
+    const double work = (double)a.slot_n * DN_T;
+    if (shard ? launch_dense_tiles<true, false, true>(a, a.slot_n, "seq_match_windows_dense_topn_part", work, s)
+              : launch_dense_tiles<true, false, false>(a, a.slot_n, "seq_match_windows_dense_topn", work, s))
+        return -1;
+    ProfScope ps("seq_dense_select", s, (double)rows * songs * 8.0);
+    if (shard) PF_LAUNCH(dense_select_kernel<true>, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);
+    else PF_LAUNCH(dense_select_kernel<false>, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);
     PF_HIP(hipGetLastError());
     return 0;
 }

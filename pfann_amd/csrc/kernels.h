@@ -161,8 +161,11 @@ int launch_expand_windows(const int64_t *rstart, const int32_t *rlen, int64_t nR
                           int64_t nW, int64_t *qstart, int32_t *qlen, hipStream_t s);
 
 // ---- dense.hip: every alignment of every window, no nomination (pfann_match_windows_dense) ----------------
+// One argument type for every form of the tile kernel (match_windows_dense_kernel<RANKED, STATS, SHARD>) and its select and
+// decode; an instantiation reads the groups of its form and nothing else.
 struct DenseArgs {
-    const float *db; int64_t ntotal; int d;     // fp32 rows of the WHOLE database
+    // ---- every call
+    const float *db; int64_t ntotal; int d;     // fp32 rows of this handle; ntotal, song_pos, n_songs: the WHOLE database
     const int64_t *song_pos; int n_songs;
     const float *q;
     const int64_t *rstart; const int32_t *rlen; int64_t nR;
@@ -170,39 +173,34 @@ struct DenseArgs {
     const int64_t *wfirst;  // [nR + 1]
     int64_t nW;             // wfirst[nR], from the caller
     const int32_t *excl;    // [nR] song whose alignments are no candidates (-1: none), or null
+    // ---- unranked: the running-best words go to results (whole handle: [nW], decoded in place) or to words (SHARD, below)
     pfann_match_result *results;
-};
-// songs_with_rows: songs of the database with len > 0 (n_cand)
-int launch_match_windows_dense(const DenseArgs &a, int64_t songs_with_rows, hipStream_t s);
-// pfann_match_windows_dense_stats: the same answer, and per window the count and the two fixed-point sums of its full pieces
-struct DenseStatsArgs : DenseArgs {
-    pfann_dense_stats *stats;   // [nW], zeroed by the launcher
-};
-int launch_match_windows_dense_stats(const DenseStatsArgs &a, int64_t songs_with_rows, hipStream_t s);
-// pfann_match_windows_dense_topn: one chunk of row-tile slots [slot_lo, slot_lo + slot_n) of the call (results unused).  The
-// tile kernel leaves every song's best packed word of every window of the chunk in ws, the select kernel ranks them.
-struct DenseTopnArgs : DenseArgs {
-    unsigned long long *ws; // [slot_n][wps][n_songs] packed words, zeroed by the launcher
+    pfann_dense_stats *stats;   // [nW] the count and the two fixed-point sums of every window's full pieces, or null: no moments
+    // ---- SHARD only (pfann_match_windows_dense_part / _topn_part): db holds the GLOBAL rows [row_lo, row_lo + nrows), whole
+    // songs [song_lo, song_lo + n_owned).  A whole handle has row_lo = 0, nrows = ntotal, song_lo = 0, n_owned = n_songs.
+    int64_t row_lo, nrows;
+    unsigned long long *words;  // unranked: [nW] raw running-best words, not decoded.  It stands here, behind results, stats,
+                                // row_lo, nrows, because beside results the unranked part kernel compiles 0.3 % slower.
+                                // The members' ORDER decides the kernels' argument loads: after adding or moving a member, run
+                                // tools/ubench/match_windows_dense_ab.py against the build before it
+    int song_lo, n_owned;
+    // ---- ranked: one chunk of row-tile slots [slot_lo, slot_lo + slot_n) of the call.  The tile kernel leaves every song's best
+    // packed word of every window of the chunk in ws, the select kernel ranks them.
+    unsigned long long *ws; // [slot_n][wps][songs] packed words; songs = n_songs, or n_owned (indexed by song - song_lo) under SHARD
     int64_t slot_lo, slot_n;
     int wps;                // window starts one slot can hold: ceil((128 - (window-1)) / hop)
     int n; pfann_match_result *top; int32_t *n_found;   // top[nW][n]; n_found[nW] or null
-    float *song_scores;     // [nW][n_songs][2] or null
+    float *song_scores;     // [nW][n_songs][2] or null; whole handle only
 };
+// Both launchers zero what the kernels accumulate into (results or words, stats, ws); the rows and songs that size the work are
+// shard ? nrows : ntotal and shard ? n_owned : n_songs.
+// unranked: stats == nullptr picks the form without moments; a whole handle's words are decoded in place.  songs_with_rows:
+// songs of the whole database with len > 0 (n_cand; unused for a shard)
+int launch_dense_unranked(const DenseArgs &a, bool shard, int64_t songs_with_rows, hipStream_t s);
+// ranked: one chunk
+int launch_dense_ranked(const DenseArgs &a, bool shard, hipStream_t s);
 int dense_topn_wps(int window, int hop);
 int64_t dense_topn_slots(int64_t nW, int64_t nR, int window, int hop);
-int launch_match_windows_dense_topn(const DenseTopnArgs &a, hipStream_t s);
-// Song-sharded parts (pfann_match_windows_dense_part / _topn_part): db holds the GLOBAL rows [row_lo, row_lo + nrows), whole
-// songs; song_pos, n_songs and ntotal stay those of the whole database.
-struct DensePartArgs : DenseStatsArgs {     // results unused; stats null: no moments
-    int64_t row_lo, nrows;
-    unsigned long long *words;  // [nW] raw running-best words, zeroed by the launcher; not decoded
-};
-int launch_match_windows_dense_part(const DensePartArgs &a, hipStream_t s);
-struct DenseTopnPartArgs : DenseTopnArgs {  // song_scores unused; ws is [slot_n][wps][n_owned], indexed by song - song_lo
-    int64_t row_lo, nrows;
-    int song_lo, n_owned;
-};
-int launch_match_windows_dense_topn_part(const DenseTopnPartArgs &a, hipStream_t s);
 // pfann_match_windows_dense_merge: words[n_parts][nW] (and part_stats[n_parts][nW], or both stats pointers null) -> what the
 // whole database's call writes; every size is global
 struct DenseMergeArgs {

@@ -429,30 +429,44 @@ class DeviceIndex:
                      "pfann_match_windows_topn")
         return ((top, n_found) if not to_host else self.topn_to_host(top, n_found)), wfirst
 
+    @staticmethod
+    def _dense_window_hop(what, window, hop):
+        """-> (window, hop) as ints, or the ValueError every dense call raises first"""
+        window, hop = int(window), int(hop)
+        if window < 1 or hop < 1:
+            raise ValueError("%s: window and hop are positive numbers of segments (got %r, %r)" % (what, window, hop))
+        return window, hop
+
+    def _dense_args(self, what, rstart, rlen, window, hop, exclude_song, q_rows=None):
+        """the windowed arguments every dense call shares -> (window, hop, nR, nW, wfirst, device rstart, rlen, wfirst,
+        exclude_song or None).  q_rows: the rows of q that the recordings must lie in (None for dense_merge, which reads no q).
+        Order of refusals: window / hop, the two assertions, exclude_song's shape; the three arrays are uploaded even when
+        there is no window (the caller then makes no library call)."""
+        window, hop = self._dense_window_hop(what, window, hop)
+        rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
+        nR = int(rl_np.shape[0])
+        assert rs_np.shape[0] == nR, "one start per recording"
+        assert q_rows is None or nR == 0 or int((rs_np + rl_np).max()) <= q_rows, "recordings exceed the rows given"
+        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
+        ex = None
+        if exclude_song is not None:
+            ex_np = np.ascontiguousarray(exclude_song, dtype=np.int32)
+            if ex_np.shape != (nR,):
+                raise ValueError("%s: exclude_song wants one song id per recording (%d), got %r" % (what, nR, ex_np.shape))
+            ex = _l.upload_async(ex_np, self.device, np.int32)
+        rs, rl = self._upload_ranges(rs_np, rl_np)
+        return window, hop, nR, int(wfirst[-1]), wfirst, rs, rl, _l.upload_async(wfirst, self.device, np.int64), ex
+
     def match_windows_dense(self, q, rstart, rlen, window, hop, exclude_song=None, to_host=True):
         """Dense matcher over every window of nR recordings (pfann_match_windows_dense): no labels -- every alignment of
         every song is a candidate of every window, so the answer is what `match` gives for the slice when each row's label
         list is the whole database.  Recordings, windows and the return value (results, wfirst) are match_windows'.
         exclude_song: one song id per recording (-1: none) whose alignments are no candidates.  window <= 64, fp32 rows."""
-        window, hop = int(window), int(hop)
-        if window < 1 or hop < 1:
-            raise ValueError("match_windows_dense: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense", rstart, rlen, window, hop, exclude_song,
+                                                                       q.shape[0])
         q = q.to(self.device, torch.float32).contiguous()
-        rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
-        nR = int(rl_np.shape[0])
-        assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
-        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
-        nW = int(wfirst[-1])
         res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
-        ex = None
-        if exclude_song is not None:
-            ex_np = np.ascontiguousarray(exclude_song, dtype=np.int32)
-            if ex_np.shape != (nR,):
-                raise ValueError("match_windows_dense: exclude_song wants one song id per recording (%d), got %r" % (nR, ex_np.shape))
-            ex = _l.upload_async(ex_np, self.device, np.int32)
         if nW:
-            rs, rl = self._upload_ranges(rs_np, rl_np)
-            wf = _l.upload_async(wfirst, self.device, np.int64)
             _l.check(self.lib.pfann_match_windows_dense(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
                                                         wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
                                                         res.data_ptr(), self._stream()), "pfann_match_windows_dense")
@@ -463,26 +477,12 @@ class DeviceIndex:
         the two fixed-point sums of the totals of its full candidates, significance.STATS_DTYPE, from the same pass.
         -> ((results, stats), wfirst): results byte for byte match_windows_dense's; with to_host=False the device tensors
         (uint8 [nW, 24], int64 [nW, 3])."""
-        window, hop = int(window), int(hop)
-        if window < 1 or hop < 1:
-            raise ValueError("match_windows_dense_stats: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_stats", rstart, rlen, window, hop,
+                                                                       exclude_song, q.shape[0])
         q = q.to(self.device, torch.float32).contiguous()
-        rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
-        nR = int(rl_np.shape[0])
-        assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
-        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
-        nW = int(wfirst[-1])
         res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
         stats = torch.empty((nW, 3), device=self.device, dtype=torch.int64)
-        ex = None
-        if exclude_song is not None:
-            ex_np = np.ascontiguousarray(exclude_song, dtype=np.int32)
-            if ex_np.shape != (nR,):
-                raise ValueError("match_windows_dense_stats: exclude_song wants one song id per recording (%d), got %r" % (nR, ex_np.shape))
-            ex = _l.upload_async(ex_np, self.device, np.int32)
         if nW:
-            rs, rl = self._upload_ranges(rs_np, rl_np)
-            wf = _l.upload_async(wfirst, self.device, np.int64)
             _l.check(self.lib.pfann_match_windows_dense_stats(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
                                                               wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
                                                               res.data_ptr(), stats.data_ptr(), self._stream()),
@@ -503,29 +503,17 @@ class DeviceIndex:
         score is not > 0).  Recordings, windows and exclude_song as in match_windows_dense.
         -> ((top [nW, n] of RESULT_DTYPE, n_found int32 [nW], block or None), wfirst): entry 0 of a window is
         match_windows_dense's answer; with to_host=False the device tensors (uint8 [nW, n, 24], int32 [nW], float32 block)."""
-        window, hop, n = int(window), int(hop), int(n)
-        if window < 1 or hop < 1:
-            raise ValueError("match_windows_dense_topn: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
+        window, hop = self._dense_window_hop("match_windows_dense_topn", window, hop)
+        n = int(n)
         if not 1 <= n <= 64:
             raise _l.PfannError("match_windows_dense_topn: n=%d outside 1..64" % n)
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_topn", rstart, rlen, window, hop,
+                                                                       exclude_song, q.shape[0])
         q = q.to(self.device, torch.float32).contiguous()
-        rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
-        nR = int(rl_np.shape[0])
-        assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
-        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
-        nW = int(wfirst[-1])
         top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
         n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
         ss = torch.empty((nW, self.n_songs, 2), device=self.device, dtype=torch.float32) if want_song_scores else None
-        ex = None
-        if exclude_song is not None:
-            ex_np = np.ascontiguousarray(exclude_song, dtype=np.int32)
-            if ex_np.shape != (nR,):
-                raise ValueError("match_windows_dense_topn: exclude_song wants one song id per recording (%d), got %r" % (nR, ex_np.shape))
-            ex = _l.upload_async(ex_np, self.device, np.int32)
         if nW:
-            rs, rl = self._upload_ranges(rs_np, rl_np)
-            wf = _l.upload_async(wfirst, self.device, np.int64)
             _l.check(self.lib.pfann_match_windows_dense_topn(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
                                                              wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None, n,
                                                              top.data_ptr(), n_found.data_ptr(),
@@ -536,34 +524,13 @@ class DeviceIndex:
         return self.topn_to_host(top, n_found) + (ss.cpu().numpy() if ss is not None else None,), wfirst
 
     # ---- the dense matcher over song-sharded handles: a part per handle, one merge (include/pfann_amd.h) ----------------
-    def _dense_windows(self, what, rstart, rlen, window, hop, exclude_song):
-        """the windowed arguments the four sharded dense calls share -> (window, hop, nR, nW, wfirst, device rstart, rlen,
-        wfirst, exclude_song or None)"""
-        window, hop = int(window), int(hop)
-        if window < 1 or hop < 1:
-            raise ValueError("%s: window and hop are positive numbers of segments (got %r, %r)" % (what, window, hop))
-        rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
-        nR = int(rl_np.shape[0])
-        assert rs_np.shape[0] == nR, "one start per recording"
-        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
-        ex = None
-        if exclude_song is not None:
-            ex_np = np.ascontiguousarray(exclude_song, dtype=np.int32)
-            if ex_np.shape != (nR,):
-                raise ValueError("%s: exclude_song wants one song id per recording (%d), got %r" % (what, nR, ex_np.shape))
-            ex = _l.upload_async(ex_np, self.device, np.int32)
-        rs, rl = self._upload_ranges(rs_np, rl_np)
-        return window, hop, nR, int(wfirst[-1]), wfirst, rs, rl, _l.upload_async(wfirst, self.device, np.int64), ex
-
     def match_windows_dense_part(self, q, rstart, rlen, window, hop, exclude_song=None, stats=False):
         """This handle's part of match_windows_dense / _stats (pfann_match_windows_dense_part): the handle may hold a shard.
         -> ((words int64 [nW]: the bit patterns of the windows' raw running-best words, 0 where this handle has no candidate;
         the statistics int64 [nW, 3] over this handle's full candidates, or None), wfirst); device tensors for dense_merge."""
-        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_windows("match_windows_dense_part", rstart, rlen, window, hop,
-                                                                          exclude_song)
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_part", rstart, rlen, window, hop,
+                                                                       exclude_song, q.shape[0])
         q = q.to(self.device, torch.float32).contiguous()
-        assert nR == 0 or int((np.asarray(rstart, dtype=np.int64) + np.asarray(rlen, dtype=np.int64)).max()) <= q.shape[0], \
-            "recordings exceed the rows given"
         words = torch.empty((nW,), device=self.device, dtype=torch.int64)
         st = torch.empty((nW, 3), device=self.device, dtype=torch.int64) if stats else None
         if nW:
@@ -578,8 +545,8 @@ class DeviceIndex:
         the song list, in any order -> (results uint8 [nW, 24], statistics int64 [nW, 3] or None): byte for byte what
         match_windows_dense / _stats give on one handle of the whole database (pfann_match_windows_dense_merge).  Any handle of
         the database can merge."""
-        window, hop, nR, nW, wfirst, _, rl, wf, ex = self._dense_windows("dense_merge", np.zeros(len(rlen), dtype=np.int64), rlen,
-                                                                         window, hop, exclude_song)
+        window, hop, nR, nW, wfirst, _, rl, wf, ex = self._dense_args("dense_merge", np.zeros(len(rlen), dtype=np.int64), rlen,
+                                                                      window, hop, exclude_song)
         words = words.to(self.device, torch.int64).contiguous()
         parts = int(words.shape[0])
         assert tuple(words.shape) == (parts, nW), "words is [parts, windows]"
@@ -603,11 +570,9 @@ class DeviceIndex:
         n = int(n)
         if not 1 <= n <= 64:
             raise _l.PfannError("match_windows_dense_topn_part: n=%d outside 1..64" % n)
-        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_windows("match_windows_dense_topn_part", rstart, rlen, window, hop,
-                                                                          exclude_song)
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_topn_part", rstart, rlen, window, hop,
+                                                                       exclude_song, q.shape[0])
         q = q.to(self.device, torch.float32).contiguous()
-        assert nR == 0 or int((np.asarray(rstart, dtype=np.int64) + np.asarray(rlen, dtype=np.int64)).max()) <= q.shape[0], \
-            "recordings exceed the rows given"
         top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
         n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
         if nW:

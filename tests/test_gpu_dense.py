@@ -201,7 +201,8 @@ def test_refusals_leave_the_results_untouched(torch_cuda):
     rc, _, untouched = call(whole, 5, 1)                 # the control: the same call on a good handle writes
     assert rc == 0 and not untouched
     for idx, window, hop, word in ((shard, 5, 1, "shard"), (half, 5, 1, "fp16"), (whole, 0, 1, "window"), (whole, 65, 1, "window"),
-                                   (whole, 5, 0, "hop")):
+                                   (whole, 5, 0, "hop"),
+                                   (shard, 65, 1, "shard")):         # two refusals at once: the first one is reported
         rc, msg, untouched = call(idx, window, hop)
         assert rc == -1 and word in msg and untouched, (window, hop, word, rc, msg, untouched)
     with pytest.raises(L.PfannError, match="shard"):

@@ -331,6 +331,10 @@ def test_refusals_write_nothing(torch_cuda):
         (merge(shard, 5, null="part_stats"), "go together"), (merge(shard, 5, null="stats"), "go together"),
         (topn_merge(shard, null="n_found_parts"), "go together"), (topn_merge(shard, null="n_found"), "go together"),
         (part(huge, 5, 1), "32-bit"), (topn_part(huge, 5, 1), "32-bit"), (merge(huge, 5), "32-bit"),
+        # two refusals at once: the first one, in the order of the call's checks, is reported
+        (part(shard, 65, 1, null="words"), "null"), (part(half, 65, 1), "fp16"), (part(shard, 65, 0), "window=65"),
+        (topn_part(shard, 5, 1, n=65, null="top"), "n=65"), (merge(shard, 0, n_parts=0), "n_parts"),
+        (part(odd, 65, 1, qq=q6), "d % 4"), (part(huge, 5, 0), "32-bit"), (topn_part(huge, 5, 0), "32-bit"),
     ]
     for i, ((rc, msg, untouched, _), word) in enumerate(refused):
         assert rc == -1 and word in msg and untouched, (i, word, rc, msg, untouched)

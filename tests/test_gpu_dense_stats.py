@@ -244,7 +244,8 @@ def test_refusals_leave_both_outputs_untouched(torch_cuda):
     rc, _, res_untouched, stats_untouched = call(whole, 5, 1)        # the control: the same call on a good handle writes both
     assert rc == 0 and not res_untouched and not stats_untouched
     for idx, window, hop, null_stats, word in ((shard, 5, 1, False, "shard"), (half, 5, 1, False, "fp16"), (whole, 0, 1, False, "window"),
-                                               (whole, 65, 1, False, "window"), (whole, 5, 0, False, "hop"), (whole, 5, 1, True, "stats_dev")):
+                                               (whole, 65, 1, False, "window"), (whole, 5, 0, False, "hop"), (whole, 5, 1, True, "stats_dev"),
+                                               (shard, 65, 1, False, "shard")):  # two refusals at once: the first one is reported
         rc, msg, res_untouched, stats_untouched = call(idx, window, hop, null_stats)
         assert rc == -1 and word in msg and res_untouched and stats_untouched, (window, hop, word, rc, msg, res_untouched, stats_untouched)
     with pytest.raises(L.PfannError, match="shard"):

@@ -253,6 +253,8 @@ def test_refusals_leave_the_outputs_untouched(torch_cuda):
     shard = DeviceIndex(D, 0)
     shard.load(db[pos[lo]:pos[hi]], pos, int(pos[lo]), song_range=(lo, hi))
     half = _index("std", db, pos, "f16")
+    half_shard = DeviceIndex(D, 0, "f16")
+    half_shard.load(db[pos[lo]:pos[hi]], pos, int(pos[lo]), song_range=(lo, hi))
     q = torch.as_tensor(db[:30]).cuda()
     rs = torch.zeros(1, dtype=torch.int64).cuda()
     rl = torch.full((1,), 30, dtype=torch.int32).cuda()
@@ -272,7 +274,8 @@ def test_refusals_leave_the_outputs_untouched(torch_cuda):
     rc, _, untouched = call(whole, 5, 1, 3)               # the control: the same call on a good handle writes all three
     assert rc == 0 and not any(untouched)
     for idx, window, hop, n, word in ((whole, 5, 1, 0, "n="), (whole, 5, 1, 65, "n="), (whole, 65, 1, 3, "window"), (whole, 0, 1, 3, "window"),
-                                      (whole, 5, 0, 3, "hop"), (half, 5, 1, 3, "fp16"), (shard, 5, 1, 3, "shard")):
+                                      (whole, 5, 0, 3, "hop"), (half, 5, 1, 3, "fp16"), (shard, 5, 1, 3, "shard"),
+                                      (shard, 5, 1, 0, "n=0"), (half_shard, 5, 1, 3, "shard")):   # two at once: the first one
         rc, msg, untouched = call(idx, window, hop, n)
         assert rc == -1 and msg and word in msg and all(untouched), (window, hop, n, word, rc, msg, untouched)
     try:

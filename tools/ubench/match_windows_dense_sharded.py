@@ -27,6 +27,81 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 
+D, SONG_ROWS = 128, 250
+
+
+def world(rows, dev, g):
+    """-> (db [n_rows, D] unit rows on the device, song_pos): songs of SONG_ROWS rows"""
+    import torch
+    n_songs = rows // SONG_ROWS
+    db = torch.nn.functional.normalize(torch.randn((n_songs * SONG_ROWS, D), device=dev, generator=g), dim=1)
+    return db, np.arange(n_songs + 1, dtype=np.int64) * SONG_ROWS
+
+
+def other_lib(path):
+    """another build's libpfann_amd.so, loaded beside this build's, with the prototypes of the calls it has"""
+    from pfann_amd import lib as L
+    plib = ctypes.CDLL(os.path.abspath(path))
+    for name, (res, args) in L.SYMBOLS.items():
+        if hasattr(plib, name):
+            fn = getattr(plib, name)
+            fn.restype, fn.argtypes = res, args
+    return plib
+
+
+def index_of(plib, dev):
+    """an empty fp32 DeviceIndex whose calls go to plib"""
+    from pfann_amd.database import DeviceIndex
+
+    class OtherIndex(DeviceIndex):
+        def __init__(self):
+            self.lib, self.d, self.device = plib, D, dev
+            self.handle = plib.pfann_db_create(D, 0)
+            assert self.handle and plib.pfann_db_set_storage(self.handle, 0) == 0
+            self.storage, self.ntotal, self.label_base, self.n_songs = "f32", 0, 0, 0
+            self._small_args, self._prefilter, self._host_res = {}, True, None
+    return OtherIndex()
+
+
+def recording(db, n, g):
+    """n noisy rows: stretches of 60 consecutive rows of random songs"""
+    import torch
+    dev, n_songs = db.device, db.shape[0] // SONG_ROWS
+    rows = []
+    while len(rows) < n:
+        s = int(torch.randint(0, n_songs, (1,), generator=g, device=dev))
+        o = int(torch.randint(0, SONG_ROWS - 60, (1,), generator=g, device=dev))
+        rows += list(range(s * SONG_ROWS + o, s * SONG_ROWS + o + 60))
+    r = torch.as_tensor(rows[:n], device=dev)
+    return torch.nn.functional.normalize(db[r] + 0.08 * torch.randn((n, D), device=dev, generator=g), dim=1)
+
+
+def shapes_of(spec):
+    """"1x7199,64x1199" -> [(name, rlen)]"""
+    shapes = []
+    for one in spec.split(","):
+        nrec, rows = (int(x) for x in one.split("x"))
+        shapes.append(("%d x %d rows" % (nrec, rows), [rows] * nrec))
+    return shapes
+
+
+def timed(fn, reps, warmup):
+    """-> (median ms of reps runs after warmup runs, the last run's value)"""
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=None)
@@ -40,37 +115,22 @@ def main():
     ap.add_argument("--out", default=None, help="also write the table to this file")
     a = ap.parse_args()
     import torch
-    from pfann_amd import lib as L
     from pfann_amd.database import DeviceIndex
     from pfann_amd.dist import shard_songs
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
     g.manual_seed(5)
-    d, song_rows = 128, 250
-    n_songs = a.rows // song_rows
-    n_rows = n_songs * song_rows
-    db = torch.nn.functional.normalize(torch.randn((n_rows, d), device=dev, generator=g), dim=1)
-    pos = np.arange(n_songs + 1, dtype=np.int64) * song_rows
+    d = D
+    db, pos = world(a.rows, dev, g)
+    n_rows, n_songs = int(db.shape[0]), len(pos) - 1
     idx = DeviceIndex(d, 0)
     idx.load(db, pos)
 
     parent = None
     if a.parent_lib:
-        plib = ctypes.CDLL(os.path.abspath(a.parent_lib))
+        plib = other_lib(a.parent_lib)
         assert not hasattr(plib, "pfann_match_windows_dense_part"), "--parent-lib already has the sharded calls: not the parent commit"
-        for name, (res, args) in L.SYMBOLS.items():
-            if hasattr(plib, name):
-                fn = getattr(plib, name)
-                fn.restype, fn.argtypes = res, args
-
-        class ParentIndex(DeviceIndex):
-            def __init__(self):
-                self.lib, self.d, self.device = plib, d, dev
-                self.handle = plib.pfann_db_create(d, 0)
-                assert self.handle and plib.pfann_db_set_storage(self.handle, 0) == 0
-                self.storage, self.ntotal, self.label_base, self.n_songs = "f32", 0, 0, 0
-                self._small_args, self._prefilter, self._host_res = {}, True, None
-        parent = ParentIndex()
+        parent = index_of(plib, dev)
         parent.load(db, pos)
 
     sharded = {}
@@ -82,34 +142,8 @@ def main():
             handles.append(ix)
         sharded[G] = handles
 
-    def recording(n):
-        rows = []
-        while len(rows) < n:
-            s = int(torch.randint(0, n_songs, (1,), generator=g, device=dev))
-            o = int(torch.randint(0, song_rows - 60, (1,), generator=g, device=dev))
-            rows += list(range(s * song_rows + o, s * song_rows + o + 60))
-        r = torch.as_tensor(rows[:n], device=dev)
-        return torch.nn.functional.normalize(db[r] + 0.08 * torch.randn((n, d), device=dev, generator=g), dim=1)
-
-    shapes = []
-    for spec in a.shapes.split(","):
-        nrec, rows = (int(x) for x in spec.split("x"))
-        shapes.append(("%d x %d rows" % (nrec, rows), [rows] * nrec))
-
-    def timed(fn):
-        for _ in range(a.warmup):
-            fn()
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1))
-        return float(np.median(ts)), out
-
+    shapes = shapes_of(a.shapes)
+    run = lambda fn: timed(fn, a.reps, a.warmup)
     lines = []
 
     def say(s):
@@ -124,7 +158,7 @@ def main():
         "median ms.  Nothing here is measured over xGMI: the all-gather of the words is not in the model."
         % ("the parent commit's library" if parent is not None else "this build", n_rows, n_songs, W, hop, a.reps, a.warmup))
     for name, rlen in shapes:
-        q = torch.cat([recording(n) for n in rlen])
+        q = torch.cat([recording(db, n, g) for n in rlen])
         rstart = np.concatenate([[0], np.cumsum(rlen)[:-1]])
         base_ix = parent if parent is not None else idx
         fns = {"baseline": lambda: base_ix.match_windows_dense(q, rstart, rlen, W, hop, to_host=False),
@@ -134,15 +168,15 @@ def main():
         merge_ms = {G: [] for G in sharded}
         for rnd in (1, 2):
             for p in ("baseline", "whole"):
-                med[(p, rnd)], out[p] = timed(fns[p])
+                med[(p, rnd)], out[p] = run(fns[p])
             for G, hs in sharded.items():
                 words = []
                 for r, ix in enumerate(hs):
-                    ms, ((w, _), _) = timed(lambda ix=ix: ix.match_windows_dense_part(q, rstart, rlen, W, hop))
+                    ms, ((w, _), _) = run(lambda ix=ix: ix.match_windows_dense_part(q, rstart, rlen, W, hop))
                     part_ms[G][r].append(ms)
                     words.append(w)
                 allw = torch.stack(words)
-                ms, (res, _) = timed(lambda: idx.dense_merge(allw, None, rlen, W, hop))
+                ms, (res, _) = run(lambda: idx.dense_merge(allw, None, rlen, W, hop))
                 merge_ms[G].append(ms)
                 assert res.cpu().numpy().tobytes() == out["whole"][0].cpu().numpy().tobytes(), "%d shards: the merge is not the whole answer" % G
         assert out["baseline"][0].cpu().numpy().tobytes() == out["whole"][0].cpu().numpy().tobytes(), "whole answers differently from the baseline"
