@@ -576,6 +576,39 @@ int pfann_match_windows_dense_topn(pfann_db *db, const float *q_dev,
                                    float *song_scores_dev /* [n_windows][n_songs][2] or NULL */,
                                    void *stream);
 
+/* Rescoring stage (csrc/dense_songs.hip): every alignment of the few songs a list names for each query, and nothing else.
+ * cand_dev has the layout pfann_match_topn writes, so the two calls chain without glue: the nominated matcher names up to m
+ * songs, this call scores each of them the way the dense matcher would.  Only the `song` field of an input entry is read.
+ * Query j owns rows [qstart[j], qstart[j] + qlen[j]) of q_dev.
+ *   listed songs  of query j: the distinct cand[j][i].song with 0 <= song < n_songs and at least one row.  Every other entry
+ *                 is ignored: padding -1, a refusal's -2, an id out of range, a song without rows.  A song listed twice
+ *                 counts once.  The list need not be sorted;
+ *   per song      for a listed song s and a query of n rows, 1 <= n <= PFANN_SONGS_DENSE_MAX_ROWS, the definition is that of
+ *                 pfann_match_windows_dense_topn for a window of those n rows: candidates are the offsets
+ *                 -(n-1) <= o <= len_s - 1; total(s, o) is +0 plus, in ascending t, every dot(Q[t], db[song_pos[s] + o + t])
+ *                 with 0 <= o + t < len_s, in fp32; a row dot is the fmaf chain from +0 over k = 0 .. d-1; the largest total
+ *                 wins, ties go to the smaller offset; the entry is {song s, offset o, shift 0, n_cand = len_s + n - 1,
+ *                 score = (double)total / (double)n};
+ *   output        top[j] holds the listed songs' entries by score descending, ties to the lower song -- the ranked dense
+ *                 matcher's order; the rest is padding {-1, 0, 0, 0, -inf}; n_found[j] = the number of listed songs;
+ *   qlen[j] == 0  all padding, n_found = 0;
+ *   qlen[j] > PFANN_SONGS_DENSE_MAX_ROWS   the query is not rescored: its m input entries are copied to its output unchanged
+ *                 and n_found = -1.
+ * BYTE CONTRACT: the bytes of a (query, song) entry are a function of the query's rows, the song's rows and n alone.  They do
+ * not depend on m, the position in the list, the other songs of the list, the other queries of the call, the launch shape or
+ * the run; they are the bytes pfann_match_windows_dense_topn gives that song for a one-window recording of the same rows.
+ * Asynchronous on `stream`, never synchronises with the host, and allocates nothing: between its two kernels a slot's
+ * running best lies in the score field of top_dev.  cand_dev and top_dev must not overlap.
+ * Returns -1 with a message, launches nothing and writes nothing -- the first of these that applies is reported --: the
+ * handle holds a shard (pfann_match_windows' message), the storage is fp16-only, m is outside 1..64; then d % 4 != 0, nQ < 0,
+ * a null cand_dev or top_dev, a song of 2^31 - 64 rows or more. */
+#define PFANN_SONGS_DENSE_MAX_ROWS 64
+int pfann_match_songs_dense(pfann_db *db, const float *q_dev,
+                            const int64_t *qstart_dev, const int32_t *qlen_dev, int64_t nQ,
+                            const pfann_match_result *cand_dev /* [nQ][m] */, int m,
+                            pfann_match_result *top_dev /* [nQ][m] */,
+                            int32_t *n_found_dev /* [nQ], may be NULL */, void *stream);
+
 /* Song-sharded dense matcher (csrc/dense.hip): the three calls above refuse a handle that holds a shard; these four split them
  * into a PART per handle and a MERGE, so that N handles that cut the song list into contiguous ranges -- N GPUs, each with 1/N
  * of the rows -- give, byte for byte, what one handle of the whole database gives.

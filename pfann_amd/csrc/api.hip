@@ -586,7 +586,7 @@ void pfann_debug_keep(pfann_ctx *c, int on) { c->keep = on != 0; }
 int pfann_prewarm(int device) {
     if (hipSetDevice(device) != hipSuccess) { set_error("pfann_prewarm: no HIP device %d", device); return -1; }
     int rc = launch_noop_api();
-    rc |= prewarm_mel() | prewarm_encoder() | prewarm_encoder_fused() | prewarm_search() | prewarm_search_f16() | prewarm_rerank() | prewarm_monitor() | prewarm_dense() | prewarm_dbstore();
+    rc |= prewarm_mel() | prewarm_encoder() | prewarm_encoder_fused() | prewarm_search() | prewarm_search_f16() | prewarm_rerank() | prewarm_monitor() | prewarm_dense() | prewarm_dense_songs() | prewarm_dbstore();
     if (hipDeviceSynchronize() != hipSuccess) rc = -1;
     return rc ? -1 : 0;
 }
@@ -1451,6 +1451,33 @@ int pfann_match_windows_dense_topn_part(pfann_db *db, const float *q, const int6
                                         int n, pfann_match_result *top, int32_t *n_found, void *stream) {
     return dense_ranked_call("match_windows_dense_topn_part", db, true, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song, n,
                              top, n_found, nullptr, stream);
+}
+
+// the rescoring stage: the listed songs of every query, every alignment (dense_songs.hip).  The packed words live in top_dev's
+// score fields between its two kernels, so the call needs no workspace
+int pfann_match_songs_dense(pfann_db *db, const float *q, const int64_t *qstart, const int32_t *qlen, int64_t nQ,
+                            const pfann_match_result *cand, int m, pfann_match_result *top, int32_t *n_found, void *stream) {
+    const char *what = "match_songs_dense";
+    PF_HIP(hipSetDevice(db->device));
+    if (!db_is_whole(db)) return refuse_shard();
+    if (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr)) {
+        set_error("%s: fp16-only storage (the dense matcher scores fp32 rows)", what);
+        return -1;
+    }
+    if (m < 1 || m > 64) { set_error("%s: m=%d outside 1..64", what, m); return -1; }
+    if (db->d % 4 != 0) { set_error("%s: d %% 4 != 0 (d=%d)", what, db->d); return -1; }
+    if (nQ < 0) { set_error("%s: nQ=%lld", what, (long long)nQ); return -1; }
+    if (cand == nullptr || top == nullptr) { set_error("%s: cand_dev or top_dev is null", what); return -1; }
+    // an alignment id is offset + n - 1 < len + 63, kept in 32 bits
+    if (db->max_song_rows + PFANN_SONGS_DENSE_MAX_ROWS >= (1ll << 31)) {
+        set_error("%s: a song of %lld rows does not fit the 32-bit alignment id", what, (long long)db->max_song_rows);
+        return -1;
+    }
+    if (nQ == 0) return 0;
+    SongsDenseArgs a;
+    a.db = db->emb; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+    a.q = q; a.qstart = qstart; a.qlen = qlen; a.nQ = nQ; a.cand = cand; a.m = m; a.top = top; a.n_found = n_found;
+    return launch_match_songs_dense(a, (hipStream_t)stream);
 }
 
 int pfann_match_windows_dense_merge(pfann_db *db, const uint64_t *words, const pfann_dense_stats *part_stats, int n_parts,

@@ -216,6 +216,19 @@ int launch_dense_topn_merge(const pfann_match_result *tops, const int32_t *nf_pa
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is per device
 int ensure_dyn_lds(const void *func, int bytes);
 
+// ---- dense_songs.hip: every alignment of the songs a query's list names (pfann_match_songs_dense) ----------------
+// Its own argument type: DenseArgs' member order is part of the tile kernel's timing (above).
+struct SongsDenseArgs {
+    const float *db; int d;                 // fp32 rows of the WHOLE database
+    const int64_t *song_pos; int n_songs;
+    const float *q;
+    const int64_t *qstart; const int32_t *qlen; int64_t nQ;
+    const pfann_match_result *cand; int m;  // [nQ][m]; only .song is read
+    pfann_match_result *top;                // [nQ][m]; between the two kernels the score fields hold the slots' packed words
+    int32_t *n_found;                       // [nQ] or null
+};
+int launch_match_songs_dense(const SongsDenseArgs &a, hipStream_t s);
+
 // ---- dbstore.hip: what an update of a loaded handle needs (pfann_db_append / pfann_db_remove_songs) ----------------
 struct DbRun { int64_t src, dst, len; };    // kept rows [src, src + len) go to [dst, dst + len), dst <= src
 // atomic maximum of the row norms (the per-row arithmetic of rows_to_half_kernel) into song_max[song - song_base]; row r of x
@@ -236,6 +249,7 @@ int prewarm_search_f16();
 int prewarm_rerank();
 int prewarm_monitor();
 int prewarm_dense();
+int prewarm_dense_songs();
 int prewarm_dbstore();
 
 }  // namespace pfann

@@ -523,6 +523,39 @@ class DeviceIndex:
             return (top, n_found, ss), wfirst
         return self.topn_to_host(top, n_found) + (ss.cpu().numpy() if ss is not None else None,), wfirst
 
+    def match_songs_dense(self, q, qstart, qlen, cand, to_host=True):
+        """Rescoring stage (pfann_match_songs_dense): every alignment of the songs `cand` lists for each of nQ queries, scored
+        as the dense matcher scores them.  cand: a device tensor in match_topn's raw layout (uint8 [nQ, m, 24]; only the song
+        fields are read), or a host int array [nQ, m] of song ids (-1: padding).  -> (structured array [nQ, m] of RESULT_DTYPE
+        ranked by score, n_found int32 [nQ]); entries past the listed songs are song -1 / score -inf; a query of more than 64
+        rows gets its input entries back and n_found -1.  With to_host=False the two device tensors, as match_topn."""
+        q = q.to(self.device, torch.float32).contiguous()
+        qs_np, ql_np = np.ascontiguousarray(qstart, dtype=np.int64), np.ascontiguousarray(qlen, dtype=np.int32)
+        nQ = int(ql_np.shape[0])
+        assert qs_np.shape[0] == nQ and (nQ == 0 or int((qs_np + ql_np).max()) <= q.shape[0]), "queries exceed the rows given"
+        rsz = ctypes.sizeof(_l.MatchResult)
+        if not torch.is_tensor(cand):
+            ids = np.asarray(cand)
+            if ids.ndim != 2 or ids.shape[0] != nQ:
+                raise ValueError("match_songs_dense: cand wants one row of song ids per query (%d), got %r" % (nQ, ids.shape))
+            host = np.zeros(ids.shape, dtype=self.RESULT_DTYPE)
+            host["song"] = ids
+            cand = torch.from_numpy(host.view(np.uint8).reshape(ids.shape + (rsz,))).to(self.device)
+        if cand.dtype != torch.uint8 or cand.dim() != 3 or cand.shape[0] != nQ or cand.shape[2] != rsz:
+            raise ValueError("match_songs_dense: cand wants uint8 [%d, m, %d], got %s %r" % (nQ, rsz, cand.dtype, tuple(cand.shape)))
+        cand = cand.to(self.device).contiguous()
+        m = int(cand.shape[1])
+        top = torch.empty((nQ, m, rsz), device=self.device, dtype=torch.uint8)
+        n_found = torch.empty((nQ,), device=self.device, dtype=torch.int32)
+        if nQ:
+            qs, ql = self._upload_ranges(qs_np, ql_np)
+            _l.check(self.lib.pfann_match_songs_dense(self.handle, q.data_ptr(), qs.data_ptr(), ql.data_ptr(), nQ, cand.data_ptr(), m,
+                                                      top.data_ptr(), n_found.data_ptr(), self._stream()),
+                     "pfann_match_songs_dense")
+        if not to_host:
+            return top, n_found
+        return self.topn_to_host(top, n_found)
+
     # ---- the dense matcher over song-sharded handles: a part per handle, one merge (include/pfann_amd.h) ----------------
     def match_windows_dense_part(self, q, rstart, rlen, window, hop, exclude_song=None, stats=False):
         """This handle's part of match_windows_dense / _stats (pfann_match_windows_dense_part): the handle may hold a shard.
@@ -1163,6 +1196,37 @@ class Database:
     def query_dense_batch(self, emb, qstart, qlen, n=1, want_song_scores=False):
         """emb: torch cuda [sum(qlen), d] unit-norm rows, queries of 1..64 segments -> (answers, ranked), see query_dense_finish"""
         return self.query_dense_finish(self.query_dense_launch(emb, qstart, qlen, n, want_song_scores))
+
+    # ---- rescored answers: the nominated matcher names n songs, the dense arithmetic scores every alignment of those ------
+    def query_rescore_launch(self, emb, qstart, qlen, n):
+        """First half of query_rescore_batch: search, then the n best nominated songs of every query (pfann_match_topn), then
+        every alignment of those songs (pfann_match_songs_dense), on the one stream; nothing is read back.  A song's rescored
+        entry is byte for byte the ranked dense matcher's entry for it, so the answer is query_dense_batch's wherever the dense
+        answer's song is among the n nominated ones.  A query of more than 64 segments keeps its nominated list."""
+        if self.ranks is not None:
+            raise _l.PfannError("query_rescore_launch: rescoring is not song-sharded: the nominated songs are scored on one GPU "
+                                "against the whole database (run without PFANN_GPUS / ranks)")
+        self._dense_check("query_rescore_launch")
+        n = int(n)
+        if not 1 <= n <= 64:
+            raise _l.PfannError("query_rescore_launch: n=%d outside 1..64" % n)
+
+        def match(I, mode):
+            out = self._match_topn(emb, I, qstart, qlen, n, mode)
+            top, n_found = self.index.match_songs_dense(emb, qstart, qlen, out["res"], to_host=False)
+            return {"res": top, "n_found": n_found}
+        return self._launch(emb, match, mode=0)
+
+    def query_rescore_finish(self, p):
+        """Second half: -> (answers, ranked) in query_dense_finish's form, without per-song blocks: answers
+        [(score, (song, time_s), None)] from entry 0, ranked per query up to n (score, (song, time_s)) best first."""
+        res = self._read_back(p)[0]
+        answers = [r + (None,) for r in self._answers(res[:, 0], 0)]
+        return answers, self._answers(res, 0, topn_tuples)
+
+    def query_rescore_batch(self, emb, qstart, qlen, n):
+        """emb: torch cuda [sum(qlen), d] unit-norm rows -> (answers, ranked), see query_rescore_finish"""
+        return self.query_rescore_finish(self.query_rescore_launch(emb, qstart, qlen, n))
 
     def monitor_finish(self, p):
         """Second half: -> per recording a structured array (w0, score, song, time_s), one entry per window: its first

@@ -126,3 +126,41 @@ def matcher_dense_flag(args):
     if dense and (int(os.environ.get("PFANN_GPUS", "1") or 1) > 1 or int(os.environ.get("WORLD_SIZE", "1") or 1) > 1):
         return dense, "matcher: --dense is not supported by a song-sharded multi-GPU run: the dense matcher holds the whole database on one GPU (unset PFANN_GPUS)"
     return dense, None
+
+
+RESCORE_MAX_SONGS = 64                                   # pfann_match_songs_dense: entries of a list
+RESCORE_MAX_SEGMENTS = 64                                # ... and rows of a query it rescores
+
+
+def matcher_rescore_flag(args):
+    """matcher.py's --rescore N among its optional arguments -> (N or 0, error message or None).  Beside matcher_flags and
+    matcher_dense_flag (whose signatures stay) for the same reason: every refusal ends the command with status 2 and one line
+    on stderr before anything heavy is imported.  Refused: N outside 1..64, --rescore with --dense, --rescore without --no-bin,
+    --top M > N, a song-sharded multi-GPU run (PFANN_GPUS / WORLD_SIZE > 1)."""
+    n, i = 0, 0
+    while i < len(args):
+        a = args[i]
+        if a == "--rescore" or a.startswith("--rescore="):
+            val = a[10:] if a.startswith("--rescore=") else (args[i + 1] if i + 1 < len(args) else "")
+            i += 0 if a.startswith("--rescore=") else 1
+            try:
+                n = int(val)
+            except ValueError:
+                n = 0
+            if not 1 <= n <= RESCORE_MAX_SONGS:
+                return 0, "matcher: --rescore takes a number of nominated songs from 1 to %d (got %r)" % (RESCORE_MAX_SONGS, val)
+        i += 1
+    if not n:
+        return 0, None
+    top, no_bin, _ = matcher_flags(args)
+    if "--dense" in args:
+        return n, "matcher: --rescore and --dense exclude each other: --dense already scores every alignment of every song"
+    if not no_bin:
+        return n, ("matcher: --rescore needs --no-bin: only the nominated songs are rescored, and a rescored per-song block "
+                   "(`.bin`) is out of scope")
+    if top > n:
+        return n, "matcher: --top %d with --rescore %d: the rescored list holds at most the %d nominated songs" % (top, n, n)
+    if int(os.environ.get("PFANN_GPUS", "1") or 1) > 1 or int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+        return n, ("matcher: --rescore is not supported by a song-sharded multi-GPU run: the nominated songs are rescored on one "
+                   "GPU against the whole database (unset PFANN_GPUS)")
+    return n, None

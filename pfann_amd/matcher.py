@@ -1,5 +1,5 @@
 """Matcher CLI, drop-in for the reference's matcher.py:
-    python matcher.py <query list> <database dir> <result file> [--top N] [--no-bin] [--dense]
+    python matcher.py <query list> <database dir> <result file> [--top N] [--no-bin] [--dense] [--rescore N]
 
 Same argv and outputs (matcher.py:34-42,84,158-163): `<result>` TSV "query\\tanswer",
 `<result-stem>_detail.csv` with header query,answer,score,time,part_scores, and
@@ -7,7 +7,7 @@ Same argv and outputs (matcher.py:34-42,84,158-163): `<result>` TSV "query\\tans
 an "error" row with -inf score and a zero block (matcher.py:94-107).  Queries are embedded,
 searched (exact flat IP top-k) and sequence-matched on the MI355X, many queries per launch.
 
-Two optional flags after the three positional arguments (without them every output is what it always was):
+Optional flags after the three positional arguments (without them every output is what it always was):
   --top N    (1..64) also write `<result-stem>_top.csv`, header query,rank,answer,score,time: up to N ranked songs per
              query, rank from 1, selected on the GPU (pfann_match_topn); an unreadable query gets one row name,1,error,-inf,0
   --no-bin   do not write `<result>.bin` and do not compute the per-song block; with --top no n_queries x n_songs array
@@ -17,6 +17,12 @@ Two optional flags after the three positional arguments (without them every outp
              columns: the TSV and _detail.csv from the best song, `.bin` from the per-song block, _top.csv from the ranked
              list.  Defined for frame_shift_mul 1, score_alpha 0 and the python path (anything else: exit status 2); a query
              of more than 64 segments gets the error row and one line on stderr.
+  --rescore N  (1..64, with --no-bin) the nominated matcher names its N best songs per query (pfann_match_topn) and EVERY
+             alignment of those N songs is then scored with the dense arithmetic (pfann_match_songs_dense, csrc/dense_songs.hip):
+             a song's rescored entry is byte for byte --dense's entry for it, at the cost of a few thousand database rows per
+             query.  The TSV, _detail.csv and (with --top M, M <= N) _top.csv come from the rescored list, same columns.  Needs
+             --no-bin (a rescored per-song block is out of scope), excludes --dense, and is defined where --dense is (anything
+             else: exit status 2); a query of more than 64 segments keeps its nominated answer and gets one line on stderr.
 None of them is supported by a song-sharded multi-GPU run (PFANN_GPUS / WORLD_SIZE > 1): exit status 2.
 """
 import csv
@@ -33,7 +39,7 @@ import torch
 from .builder import embed_file_batches, gather_round
 from .database import Database
 from .dist import finish_ranks, init_ranks, self_launch_if_asked
-from .launch import DENSE_MAX_SEGMENTS, matcher_dense_flag, matcher_flags
+from .launch import DENSE_MAX_SEGMENTS, RESCORE_MAX_SEGMENTS, matcher_dense_flag, matcher_flags, matcher_rescore_flag
 from .engine import Engine
 from .musicdata import MusicDataset
 from .utils import StageTimer, StartupClock, get_logger, init_logger, read_config
@@ -151,8 +157,9 @@ def main(argv=None):
         return 1
     top_n, no_bin, err = matcher_flags(argv[4:])
     dense, dense_err = matcher_dense_flag(argv[4:])
-    if err or dense_err:
-        print(err or dense_err, file=sys.stderr)
+    rescore, rescore_err = matcher_rescore_flag(argv[4:])
+    if err or dense_err or rescore_err:
+        print(err or dense_err or rescore_err, file=sys.stderr)
         return 2
     rc = self_launch_if_asked(argv)         # PFANN_GPUS=N: N ranks of this command, one per GPU
     if rc is not None:
@@ -216,6 +223,17 @@ def main(argv=None):
             wq = torch.zeros((19, db.d), device=db.index.device)
             wq[:, 0] = 1.0
             db.query_dense_batch(wq, [0], [19], max(top_n, 1), want_song_scores=not no_bin)
+    elif rescore:
+        try:
+            db._dense_check("matcher --rescore")
+        except Exception as x:                      # (PfannError: a config the dense form does not define)
+            print(str(x), file=sys.stderr)
+            return 2
+        db.warmup(rows=warm, want_song_scores=False, topn=rescore)
+        if int(db.song_pos[-1]):
+            wq = torch.zeros((19, db.d), device=db.index.device)
+            wq[:, 0] = 1.0
+            db.query_rescore_batch(wq, [0], [19], rescore)
     elif top_n or no_bin:
         db.warmup(rows=warm, want_song_scores=not no_bin, topn=top_n)
     else:
@@ -234,6 +252,9 @@ def main(argv=None):
         """items: one launch group of (index, n_seg, emb) in list order -> search + match in flight."""
         good = [(i, n, e) for i, n, e in items if n and not too_long(n)]
         for i, n, _ in items:
+            if rescore and n > RESCORE_MAX_SEGMENTS:
+                print("matcher: %s has %d segments; --rescore rescores queries of at most %d: it keeps its nominated answer"
+                      % (dataset.files[i], n, RESCORE_MAX_SEGMENTS), file=sys.stderr)
             if too_long(n):
                 print("matcher: %s has %d segments; --dense answers queries of at most %d: error row" % (dataset.files[i], n, DENSE_MAX_SEGMENTS),
                       file=sys.stderr)
@@ -244,6 +265,8 @@ def main(argv=None):
             qstart = np.concatenate([[0], np.cumsum(qlen)[:-1]])
             if dense:
                 ps = db.query_dense_launch_chunks(emb, qstart, qlen, max(top_n, 1), want_song_scores=not no_bin)
+            elif rescore:                          # search + top-N match + the listed songs' alignments: no per-song block
+                ps = [(0, len(good), db.query_rescore_launch(emb, qstart, qlen, rescore))]
             elif top_n and no_bin:                 # search + top-N match: no per-song block, so nothing to cut into chunks
                 ps = [(0, len(good), db.query_topn_launch(emb, qstart, qlen, top_n))]
             else:
@@ -259,6 +282,10 @@ def main(argv=None):
                 answers, ranked = db.query_dense_finish(p, reuse_buffers=True)
                 for (i, _, _), r, rows in zip(good[j0:j1], answers, ranked):
                     results[i] = r + (rows if top_n else None,)
+            elif rescore:
+                answers, ranked = db.query_rescore_finish(p)
+                for (i, _, _), r, rows in zip(good[j0:j1], answers, ranked):
+                    results[i] = r + (rows[:top_n] if top_n else None,)
             elif top_n and no_bin:
                 for (i, _, _), rows in zip(good[j0:j1], db.query_topn_finish(p)):
                     results[i] = rows[0] + (None, rows)
