@@ -22,6 +22,7 @@
  *   pfann_match_windows_dense  database.py:129-163 with every row's label list = the whole database (no counterpart)
  *   pfann_match_windows_dense_stats  the same answer, and the moments of every window's full candidates (no counterpart)
  *   pfann_match_windows_dense_topn  the same candidates, the n best songs per window and the per-song block (no counterpart)
+ *   pfann_match_windows_dense_topn_stats  the ranked lists and the moments from one pass (no counterpart)
  *   pfann_match_windows_dense_part / _merge, _topn_part / _topn_merge  the three above over song-sharded handles (no counterpart)
  */
 #ifndef PFANN_AMD_H
@@ -575,6 +576,35 @@ int pfann_match_windows_dense_topn(pfann_db *db, const float *q_dev,
                                    int32_t *n_found_dev /* [n_windows] or NULL */,
                                    float *song_scores_dev /* [n_windows][n_songs][2] or NULL */,
                                    void *stream);
+
+/* Dense matcher, ranked, with background statistics: pfann_match_windows_dense_topn's lists and pfann_match_windows_dense_stats'
+ * moments from ONE pass over the database (csrc/dense.hip: the ranked tile kernel also counts).  Arguments, the window rule,
+ * short and empty recordings, excl_song_dev, n and the chunking follow pfann_match_windows_dense_topn.
+ *   ranked outputs   top_dev, n_found_dev and song_scores_dev get, byte for byte, what pfann_match_windows_dense_topn writes for
+ *                    the same arguments;
+ *   statistics       stats_dev[n_windows] gets, byte for byte, what pfann_match_windows_dense_stats writes for them: n_full,
+ *                    sum_q, sumsq_q of every window's full candidates, as defined there.  A stretch of a tile's diagonal is a
+ *                    full candidate exactly when no song boundary cuts it, its song exists and is not the excluded one; it adds
+ *                    the integers 1, rint((double)total * 2^24), rint((double)total * (double)total * 2^18) from the very total
+ *                    that is packed into its word, by wave shuffles, one LDS entry per live window start and one 64-bit
+ *                    atomicAdd per non-zero entry of a (window, tile) into the window of the CALL.
+ * BYTE CONTRACT: both byte contracts carry over: a window's n * 24 result bytes, its n_found, its row of the block and its 24
+ * stats bytes are a function of the window's rows, the database, its recording's excluded song and n (through the prefix rule
+ * only) -- not of hop, the other windows or recordings of the call, the tiling, how the call was chunked
+ * (PFANN_DENSE_TOPN_WINDOWS), or the run.  Every (window, tile) pair belongs to exactly one chunk and everything after the rint
+ * is integer addition, so the call zeroes stats_dev ONCE, with hipMemsetAsync on `stream` before its first chunk.
+ * Asynchrony as for pfann_match_windows_dense_topn: the one wait when the workspace grows.  After pfann_db_append /
+ * pfann_db_remove_songs the call answers as a fresh handle would.
+ * Returns -1 with a message, launches nothing and writes nothing, when stats_dev is NULL and in every case in which
+ * pfann_match_windows_dense_topn does, in that call's order.  Whole handles only: there is no song-sharded form. */
+int pfann_match_windows_dense_topn_stats(pfann_db *db, const float *q_dev,
+                                         const int64_t *rstart_dev, const int32_t *rlen_dev, int64_t nR,
+                                         int window, int hop, const int64_t *wfirst_dev, int64_t n_windows,
+                                         const int32_t *excl_song_dev /* [nR] or NULL */, int n,
+                                         pfann_match_result *top_dev /* [n_windows][n] */,
+                                         int32_t *n_found_dev /* [n_windows] or NULL */,
+                                         float *song_scores_dev /* [n_windows][n_songs][2] or NULL */,
+                                         pfann_dense_stats *stats_dev /* [n_windows] */, void *stream);
 
 /* Rescoring stage (csrc/dense_songs.hip): every alignment of the few songs a list names for each query, and nothing else.
  * cand_dev has the layout pfann_match_topn writes, so the two calls chain without glue: the nominated matcher names up to m

@@ -1,11 +1,11 @@
 #!/usr/bin/env python
-"""Drop-in for the reference's `python matcher.py <query list> <db dir> <result file>` (optional: --top N, --no-bin)."""
+"""Drop-in for the reference's `python matcher.py <query list> <db dir> <result file>` (optional: --top N, --no-bin, --dense, --max-fa X, --rescore N)."""
 import sys
 
 from pfann_amd import launch, prewarm
 
 if __name__ == "__main__":
-    _err = launch.matcher_flags(sys.argv[4:])[2]       # a bad --top / --no-bin ends here, before anything is launched
+    _err = launch.matcher_flag_error(sys.argv[4:])     # a refused flag ends here, before anything is launched
     if _err:
         print(_err, file=sys.stderr)
         sys.exit(2)

@@ -1403,10 +1403,12 @@ int pfann_match_windows_dense_part(pfann_db *db, const float *q, const int64_t *
 
 // the ranked calls: pfann_match_windows_dense_topn on a whole handle, _topn_part (no per-song block) on any fp32 handle.  Chunks of
 // whole row-tile slots: the workspace holds 8 bytes per (window the chunk's slots can hold, song of the handle), at most 256 MB
-// unless one slot alone needs more; PFANN_DENSE_TOPN_WINDOWS (read per call) lowers the windows per chunk
+// unless one slot alone needs more; PFANN_DENSE_TOPN_WINDOWS (read per call) lowers the windows per chunk.  stats (whole handles
+// only, or null): pfann_match_windows_dense_topn_stats -- zeroed ONCE, before the first chunk: the tile kernel adds into the
+// windows of the call, and every (window, tile) pair belongs to exactly one chunk
 static int dense_ranked_call(const char *what, pfann_db *db, bool shard, const float *q, const int64_t *rstart, const int32_t *rlen,
                              int64_t nR, int window, int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, int n,
-                             pfann_match_result *top, int32_t *n_found, float *song_scores, void *stream) {
+                             pfann_match_result *top, int32_t *n_found, float *song_scores, pfann_dense_stats *stats, void *stream) {
     PF_HIP(hipSetDevice(db->device));
     hipStream_t st = (hipStream_t)stream;
     if (n < 1 || n > 64) { set_error("%s: n=%d outside 1..64", what, n); return -1; }
@@ -1431,7 +1433,8 @@ static int dense_ranked_call(const char *what, pfann_db *db, bool shard, const f
         db->dense_ws_bytes = need;
     }
     a.ws = reinterpret_cast<unsigned long long *>(db->dense_ws); a.wps = wps;
-    a.n = n; a.top = top; a.n_found = n_found; a.song_scores = song_scores;
+    a.n = n; a.top = top; a.n_found = n_found; a.song_scores = song_scores; a.stats = stats;
+    if (stats != nullptr) PF_HIP(hipMemsetAsync(stats, 0, (size_t)n_windows * sizeof(pfann_dense_stats), st));
     for (int64_t s0 = 0; s0 < n_slots; s0 += step) {
         a.slot_lo = s0; a.slot_n = std::min(step, n_slots - s0);
         if (launch_dense_ranked(a, shard, st)) return -1;
@@ -1443,14 +1446,23 @@ int pfann_match_windows_dense_topn(pfann_db *db, const float *q, const int64_t *
                                    int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, int n,
                                    pfann_match_result *top, int32_t *n_found, float *song_scores, void *stream) {
     return dense_ranked_call("match_windows_dense_topn", db, false, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song, n, top,
-                             n_found, song_scores, stream);
+                             n_found, song_scores, nullptr, stream);
+}
+
+int pfann_match_windows_dense_topn_stats(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR,
+                                         int window, int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
+                                         int n, pfann_match_result *top, int32_t *n_found, float *song_scores,
+                                         pfann_dense_stats *stats, void *stream) {
+    if (stats == nullptr) { set_error("match_windows_dense_topn_stats: stats_dev is null"); return -1; }
+    return dense_ranked_call("match_windows_dense_topn_stats", db, false, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song,
+                             n, top, n_found, song_scores, stats, stream);
 }
 
 int pfann_match_windows_dense_topn_part(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR,
                                         int window, int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song,
                                         int n, pfann_match_result *top, int32_t *n_found, void *stream) {
     return dense_ranked_call("match_windows_dense_topn_part", db, true, q, rstart, rlen, nR, window, hop, wfirst, n_windows, excl_song, n,
-                             top, n_found, nullptr, stream);
+                             top, n_found, nullptr, nullptr, stream);
 }
 
 // the rescoring stage: the listed songs of every query, every alignment (dense_songs.hip).  The packed words live in top_dev's

@@ -65,12 +65,16 @@ __device__ __forceinline__ int dn_windows_of(int L, int window, int hop) {
 // are reduced per SONG inside the tile -- s_best is then one table per half of the workgroup, indexed by the song's first
 // column in the tile (s_head) -- and every non-empty entry goes out with one atomicMax into ws[window of the chunk][song].
 //
-// STATS (pfann_match_windows_dense_stats, unranked only): beside the maximum, the first two moments of the window's FULL pieces --
+// STATS (pfann_match_windows_dense_stats; with RANKED pfann_match_windows_dense_topn_stats): beside the maximum, the first two moments of the window's FULL pieces --
 // stretches that no song boundary cuts, of a song that is not the excluded one: the candidates 0 <= o <= len_s - n.  A piece
 // with fp32 total tot adds the integers 1, rint((double)tot * 2^24) and rint((double)tot * (double)tot * 2^18); both products
 // are exact in double, so the rounding is the only rounding, and everything after it -- wave shuffles, one LDS entry per
 // window start, one global 64-bit atomicAdd per non-zero entry -- is integer addition: the three sums of a window are, like
-// its result bytes, a function of its rows, the database and the excluded song alone.
+// its result bytes, a function of its rows, the database and the excluded song alone.  RANKED + STATS: a thread's stretch is a
+// full piece exactly when the ranked walk never cut it (the unranked form's !cut), from the very tot that is packed into the
+// word; only the window starts ib, ib + 1 are live at a time, so the LDS entries are one per half of the workgroup, and the
+// global add goes to stats[wf + (i0 + i) / hop] -- the window of the CALL, not the chunk's workspace row: every (window, tile)
+// pair belongs to one chunk, the call zeroes stats once before its first chunk.  Whole handles only.
 //
 // SHARD (pfann_match_windows_dense_part / _topn_part): the handle holds the global rows [row_lo, row_lo + nrows) of a song-sharded
 // database, whole songs only, and the global song_pos.  The db tiles run over that range -- tile jt starts at global row
@@ -79,20 +83,21 @@ __device__ __forceinline__ int dn_windows_of(int L, int window, int hop) {
 // word it gets from the whole database.  The unranked form leaves the raw words (no decode), the ranked form indexes its
 // workspace by song - song_lo.  No new LDS; the instantiations without SHARD are the code they were before it existed.
 //
-// All six instantiations take the one DenseArgs (kernels.h) and read only the groups of their form; launch_dense_unranked and
+// All seven instantiations take the one DenseArgs (kernels.h) and read only the groups of their form; launch_dense_unranked and
 // launch_dense_ranked, further down, pick the instantiation from (shard, stats != nullptr).
 template <bool RANKED, bool STATS = false, bool SHARD = false>
 __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a) {
-    static_assert(!(RANKED && STATS), "the moments are kept by the unranked form");
+    static_assert(!(RANKED && STATS && SHARD), "the ranked moments are kept by whole handles");
     // S[DN_T][DN_LDS]; while the product runs its first bytes are the two K tiles As, Bs [DN_T][DN_LDK]
     extern __shared__ __attribute__((aligned(16))) float s_S[];          // DN_S_BYTES, dynamic: past the static 64 KB
     __shared__ long long s_cpos[1024];
     __shared__ int s_song[DN_T];
     __shared__ int s_head[RANKED ? DN_T : 1];
     __shared__ unsigned long long s_best[RANKED ? 2 * DN_T : DN_T];
-    // per window start of the tile: sum_q, sumsq_q and the number of full pieces (at most DN_T: 20 bytes per start)
-    __shared__ unsigned long long s_sum[STATS ? 2 * DN_T : 1];
-    __shared__ int s_full[STATS ? DN_T : 1];
+    // per window start of the tile: sum_q, sumsq_q and the number of full pieces (at most DN_T: 20 bytes per start); RANKED: per
+    // half of the workgroup (its one live window start)
+    __shared__ unsigned long long s_sum[STATS ? (RANKED ? 2 * (DN_NT / DN_T) : 2 * DN_T) : 1];
+    __shared__ int s_full[STATS ? (RANKED ? DN_NT / DN_T : DN_T) : 1];
     static_assert(2 * DN_T * DN_LDK <= DN_T * DN_LDS, "the K tiles fit under S");
     float *As = s_S, *Bs = s_S + DN_T * DN_LDK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -135,7 +140,10 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a)
                 s_head[tid] = sg >= 0 ? (int)max((int64_t)0, a.song_pos[sg] - J0) : tid;
                 s_best[DN_T + tid] = 0;
             }
-            if constexpr (STATS) { s_sum[2 * tid] = 0; s_sum[2 * tid + 1] = 0; s_full[tid] = 0; }
+            if constexpr (STATS && !RANKED) { s_sum[2 * tid] = 0; s_sum[2 * tid + 1] = 0; s_full[tid] = 0; }
+            if constexpr (STATS && RANKED) {
+                if (tid < DN_NT / DN_T) { s_sum[2 * tid] = 0; s_sum[2 * tid + 1] = 0; s_full[tid] = 0; }
+            }
         }
 
         // ---- S = Q tile x db tile^T.  Thread tid stages rows (tid >> 2) and (tid >> 2) + 64 of both operands, eight
@@ -243,6 +251,8 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a)
                 const int i = ib + half;
                 if (half ? act1 : act0) {                            // (whole waves)
                     unsigned long long x0 = 0;
+                    [[maybe_unused]] int full = 0;                   // STATS: this thread's stretch is a full piece
+                    [[maybe_unused]] long long sum = 0, sumsq = 0;
                     if (j < SI) {
                         int cur = s_song[j], head = head0;
                         bool first = true;
@@ -261,6 +271,27 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a)
                         }
                         const unsigned long long x = packed(cur, tot);
                         if (first) x0 = x; else if (x != 0) atomicMax(&tab[head], x);
+                        if constexpr (STATS) {
+                            if (first && x != 0) {                   // never cut, a song, not the excluded one
+                                const double td = (double)tot;
+                                full = 1;
+                                sum = __double2ll_rn(td * 16777216.0);           // 2^PFANN_DENSE_STATS_SUM_SHIFT
+                                sumsq = __double2ll_rn(td * td * 262144.0);      // 2^PFANN_DENSE_STATS_SQ_SHIFT
+                            }
+                        }
+                    }
+                    if constexpr (STATS) {
+#pragma unroll
+                        for (int o = 32; o > 0; o >>= 1) {
+                            full += __shfl_xor(full, o, 64);
+                            sum += __shfl_xor(sum, o, 64);
+                            sumsq += __shfl_xor(sumsq, o, 64);
+                        }
+                        if (lane == 0 && full != 0) {
+                            atomicAdd(&s_full[half], full);
+                            atomicAdd(&s_sum[2 * half], (unsigned long long)sum);
+                            atomicAdd(&s_sum[2 * half + 1], (unsigned long long)sumsq);
+                        }
                     }
 #pragma unroll
                     for (int o = 1; o < 64; o <<= 1) {               // lane l: the maximum of lanes l .. l + 2 o - 1 of its run
@@ -278,6 +309,18 @@ __global__ __launch_bounds__(DN_NT) void match_windows_dense_kernel(DenseArgs a)
                         tab[j] = 0;
                         if constexpr (SHARD) atomicMax(&a.ws[(ws_row0 + (i0 + i) / a.hop) * a.n_owned + (s_song[j] - a.song_lo)], x);
                         else atomicMax(&a.ws[(ws_row0 + (i0 + i) / a.hop) * a.n_songs + s_song[j]], x);
+                    }
+                }
+                if constexpr (STATS) {
+                    if (j == 0) {                                    // the half's entry: the window of the CALL, wf + (i0 + i) / hop
+                        const int nf = s_full[half];
+                        if (nf != 0) {                               // (only a half with a window start has any)
+                            unsigned long long *st = reinterpret_cast<unsigned long long *>(&a.stats[wf + (i0 + i) / a.hop]);
+                            atomicAdd(&st[0], (unsigned long long)nf);
+                            if (s_sum[2 * half] != 0) atomicAdd(&st[1], s_sum[2 * half]);
+                            if (s_sum[2 * half + 1] != 0) atomicAdd(&st[2], s_sum[2 * half + 1]);
+                            s_full[half] = 0; s_sum[2 * half] = 0; s_sum[2 * half + 1] = 0;
+                        }
                     }
                 }
                 __syncthreads();                                     // the tables are empty again
@@ -605,9 +648,11 @@ int launch_dense_ranked(const DenseArgs &a, bool shard, hipStream_t s) {
     const int songs = shard ? a.n_owned : a.n_songs;
     if (songs > 0) PF_HIP(hipMemsetAsync(a.ws, 0, (size_t)rows * songs * sizeof(unsigned long long), s));
     const double work = (double)a.slot_n * DN_T;
-    if (shard ? launch_dense_tiles<true, false, true>(a, a.slot_n, "seq_match_windows_dense_topn_part", work, s)
-              : launch_dense_tiles<true, false, false>(a, a.slot_n, "seq_match_windows_dense_topn", work, s))
-        return -1;
+    int rc;
+    if (shard) rc = launch_dense_tiles<true, false, true>(a, a.slot_n, "seq_match_windows_dense_topn_part", work, s);
+    else rc = a.stats != nullptr ? launch_dense_tiles<true, true, false>(a, a.slot_n, "seq_match_windows_dense_topn_stats", work, s)
+                                 : launch_dense_tiles<true, false, false>(a, a.slot_n, "seq_match_windows_dense_topn", work, s);
+    if (rc) return -1;
     ProfScope ps("seq_dense_select", s, (double)rows * songs * 8.0);
     if (shard) PF_LAUNCH(dense_select_kernel<true>, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);
     else PF_LAUNCH(dense_select_kernel<false>, dim3((unsigned)rows), dim3(DN_SEL_NT), 0, s, a);

@@ -176,6 +176,7 @@ struct DenseArgs {
     // ---- unranked: the running-best words go to results (whole handle: [nW], decoded in place) or to words (SHARD, below)
     pfann_match_result *results;
     pfann_dense_stats *stats;   // [nW] the count and the two fixed-point sums of every window's full pieces, or null: no moments
+                                // (also read by the ranked form of a whole handle: pfann_match_windows_dense_topn_stats)
     // ---- SHARD only (pfann_match_windows_dense_part / _topn_part): db holds the GLOBAL rows [row_lo, row_lo + nrows), whole
     // songs [song_lo, song_lo + n_owned).  A whole handle has row_lo = 0, nrows = ntotal, song_lo = 0, n_owned = n_songs.
     int64_t row_lo, nrows;
@@ -197,7 +198,8 @@ struct DenseArgs {
 // unranked: stats == nullptr picks the form without moments; a whole handle's words are decoded in place.  songs_with_rows:
 // songs of the whole database with len > 0 (n_cand; unused for a shard)
 int launch_dense_unranked(const DenseArgs &a, bool shard, int64_t songs_with_rows, hipStream_t s);
-// ranked: one chunk
+// ranked: one chunk.  stats != nullptr (whole handle) picks the form that also keeps the moments; the CALLER zeroes stats once,
+// before its first chunk: the kernel adds into the windows of the call
 int launch_dense_ranked(const DenseArgs &a, bool shard, hipStream_t s);
 int dense_topn_wps(int window, int hop);
 int64_t dense_topn_slots(int64_t nW, int64_t nR, int window, int hop);

@@ -523,6 +523,33 @@ class DeviceIndex:
             return (top, n_found, ss), wfirst
         return self.topn_to_host(top, n_found) + (ss.cpu().numpy() if ss is not None else None,), wfirst
 
+    def match_windows_dense_topn_stats(self, q, rstart, rlen, window, hop, n, exclude_song=None, want_song_scores=False, to_host=True):
+        """match_windows_dense_topn with the background statistics of every window from the same pass
+        (pfann_match_windows_dense_topn_stats): the ranked outputs byte for byte match_windows_dense_topn's, the statistics byte
+        for byte match_windows_dense_stats'.  Whole handles only.
+        -> ((top, n_found, block or None, stats), wfirst); with to_host=False the device tensors (.., int64 [nW, 3])."""
+        window, hop = self._dense_window_hop("match_windows_dense_topn_stats", window, hop)
+        n = int(n)
+        if not 1 <= n <= 64:
+            raise _l.PfannError("match_windows_dense_topn_stats: n=%d outside 1..64" % n)
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_topn_stats", rstart, rlen, window, hop,
+                                                                       exclude_song, q.shape[0])
+        q = q.to(self.device, torch.float32).contiguous()
+        top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
+        ss = torch.empty((nW, self.n_songs, 2), device=self.device, dtype=torch.float32) if want_song_scores else None
+        stats = torch.empty((nW, 3), device=self.device, dtype=torch.int64)
+        if nW:
+            _l.check(self.lib.pfann_match_windows_dense_topn_stats(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window,
+                                                                   hop, wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None, n,
+                                                                   top.data_ptr(), n_found.data_ptr(),
+                                                                   ss.data_ptr() if ss is not None else None, stats.data_ptr(),
+                                                                   self._stream()),
+                     "pfann_match_windows_dense_topn_stats")
+        if not to_host:
+            return (top, n_found, ss, stats), wfirst
+        return self.topn_to_host(top, n_found) + (ss.cpu().numpy() if ss is not None else None, self.stats_to_host(stats)), wfirst
+
     def match_songs_dense(self, q, qstart, qlen, cand, to_host=True):
         """Rescoring stage (pfann_match_songs_dense): every alignment of the songs `cand` lists for each of nQ queries, scored
         as the dense matcher scores them.  cand: a device tensor in match_topn's raw layout (uint8 [nQ, m, 24]; only the song
@@ -1147,12 +1174,17 @@ class Database:
         return self._windows_topn_finish(p, self.frame_shift_mul)
 
     # ---- plain queries through the dense form: every query is one recording and one window ----------------------------
-    def query_dense_launch(self, emb, qstart, qlen, n=1, want_song_scores=False):
+    def query_dense_launch(self, emb, qstart, qlen, n=1, want_song_scores=False, stats=False):
         """First half of query_dense_batch: the ranked dense matcher (pfann_match_windows_dense_topn) with window = the longest
         query of the call (at most 64 segments; every query has at least one), so that by the short-recording rule every query is
         exactly one window over all its rows, and by the byte contract its answer does not depend on what it was batched with.
-        No search.  The per-song block is converted to seconds where it lives, as query_launch does."""
+        No search.  The per-song block is converted to seconds where it lives, as query_launch does.
+        stats=True: the same outputs and every query's background statistics from the one pass
+        (pfann_match_windows_dense_topn_stats), for query_dense_stats_finish; not song-sharded."""
         self._dense_check("query_dense_launch")
+        if stats and self.ranks is not None:
+            raise _l.PfannError("query_dense_launch: the ranked statistics are not song-sharded (stats=True needs the whole database "
+                                "on one handle: run without PFANN_GPUS / ranks)")
         if want_song_scores and self.sharded is not None:
             raise _l.PfannError("query_dense_launch: the per-song block is not song-sharded (want_song_scores=True needs the whole "
                                 "database on one handle: run without PFANN_GPUS / ranks)")
@@ -1162,13 +1194,19 @@ class Database:
         window = int(ql.max()) if ql.shape[0] else 1
 
         def match():
-            (top, n_found, ss), wfirst = self._dense_windows_topn(emb, qstart, ql, window, 1, n, want_song_scores)
+            out = {}
+            if stats:
+                (top, n_found, ss, out["stats"]), wfirst = self.index.match_windows_dense_topn_stats(
+                    emb, qstart, ql, window, 1, n, want_song_scores=want_song_scores, to_host=False)
+                out["rows_of"] = ql.astype(np.int64)
+            else:
+                (top, n_found, ss), wfirst = self._dense_windows_topn(emb, qstart, ql, window, 1, n, want_song_scores)
             assert int(wfirst[-1]) == ql.shape[0]
             self.index.song_scores_to_seconds(ss, 1, self.hop_size)
-            return {"res": top, "n_found": n_found, "ss": ss}
+            return dict(out, res=top, n_found=n_found, ss=ss)
         return self._launch_dense(emb, match)
 
-    def query_dense_launch_chunks(self, emb, qstart, qlen, n=1, want_song_scores=False):
+    def query_dense_launch_chunks(self, emb, qstart, qlen, n=1, want_song_scores=False, stats=False):
         """query_dense_launch cut by the score-block budget, lazily, exactly as query_launch_chunks cuts query_launch"""
         nq = len(qlen)
         step = max(1, nq) if not want_song_scores else max(1, min(nq, self.max_score_pairs // max(len(self.songList), 1)))
@@ -1178,24 +1216,52 @@ class Database:
             r0 = int(qstart[j0])
             r1 = int(qstart[j1 - 1]) + int(qlen[j1 - 1])
             sub = emb if (j0 == 0 and j1 == nq) else emb[r0:r1]
-            return self.query_dense_launch(sub, qstart[j0:j1] - r0, qlen[j0:j1], n, want_song_scores)
+            return self.query_dense_launch(sub, qstart[j0:j1] - r0, qlen[j0:j1], n, want_song_scores, stats)
         return LazyLaunches([(j0, min(j0 + step, nq)) for j0 in range(0, nq, step)], launch)
 
     def query_dense_finish(self, p, reuse_buffers=False):
         """Second half: -> (answers, ranked): answers as query_finish gives them, [(score, (song, time_s), song_score|None)]
         from entry 0, and ranked as query_topn_finish gives them, per query up to n (score, (song, time_s)) best first; both
         through the one read-back and the one formatter.  reuse_buffers: as in query_finish."""
+        return self._dense_answers(p, reuse_buffers)[1:]
+
+    def _dense_answers(self, p, reuse_buffers):
+        """the read-back of a query_dense_launch -> (raw ranked lists RESULT_DTYPE [nQ, n], answers, ranked)"""
         res, land = self._read_back(p)
         if land is None:
             blocks = [None] * len(res)
         else:
             blocks = land.numpy() if reuse_buffers else land.numpy().copy()
         answers = [r + (b,) for r, b in zip(self._answers(res[:, 0], 0), blocks)]
-        return answers, self._answers(res, 0, topn_tuples)
+        return res, answers, self._answers(res, 0, topn_tuples)
 
     def query_dense_batch(self, emb, qstart, qlen, n=1, want_song_scores=False):
         """emb: torch cuda [sum(qlen), d] unit-norm rows, queries of 1..64 segments -> (answers, ranked), see query_dense_finish"""
         return self.query_dense_finish(self.query_dense_launch(emb, qstart, qlen, n, want_song_scores))
+
+    def query_dense_stats_finish(self, p, reuse_buffers=False):
+        """Second half of query_dense_launch(stats=True): -> (answers, ranked, log10_fa).  answers and ranked are exactly
+        query_dense_finish's, through the one read-back; log10_fa[j] is a float64 array aligned with ranked[j]: for every listed
+        song the log10 of the chance that the best of the query's candidates reaches that song's score when the query holds
+        nothing of the database, judged against the query's own background with the better-ranked entries and the entry itself
+        left out (significance.log10_false_alarms_ranked); 0 where that cannot be said.  Every query is one window of its own
+        rows, so the overlap histogram is that of its own length."""
+        from . import significance as sg
+        res, answers, ranked = self._dense_answers(p, reuse_buffers)
+        stats = self.index.stats_to_host(p["stats"])     # (complete behind the event the read-back waited for)
+        song_len = np.diff(self.song_pos)
+        if getattr(self, "_overlap_hists", None) is None or not np.array_equal(self._overlap_hists.song_len, song_len):
+            self._overlap_hists = sg.OverlapHistograms(song_len)
+        fa = []
+        for top, st, L, rows in zip(res, stats, p["rows_of"], ranked):
+            L = int(L)
+            v = sg.log10_false_alarms_ranked(top, L, (st["n_full"], st["sum_q"], st["sumsq_q"]), self._overlap_hists(L), song_len)
+            fa.append(v[:len(rows)])
+        return answers, ranked, fa
+
+    def query_dense_stats_batch(self, emb, qstart, qlen, n=1, want_song_scores=False):
+        """query_dense_batch with a significance for every ranked entry -> (answers, ranked, log10_fa), see query_dense_stats_finish"""
+        return self.query_dense_stats_finish(self.query_dense_launch(emb, qstart, qlen, n, want_song_scores, stats=True))
 
     # ---- rescored answers: the nominated matcher names n songs, the dense arithmetic scores every alignment of those ------
     def query_rescore_launch(self, emb, qstart, qlen, n):

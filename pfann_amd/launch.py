@@ -164,3 +164,38 @@ def matcher_rescore_flag(args):
         return n, ("matcher: --rescore is not supported by a song-sharded multi-GPU run: the nominated songs are rescored on one "
                    "GPU against the whole database (unset PFANN_GPUS)")
     return n, None
+
+
+def matcher_flag_error(args):
+    """the first refusal of matcher.py's optional arguments, in the one order both entry points report them (the script
+    matcher.py before it imports anything heavy, pfann_amd.matcher.main again): matcher_flags, matcher_dense_flag,
+    matcher_rescore_flag, matcher_max_fa_flag -> message or None"""
+    return matcher_flags(args)[2] or matcher_dense_flag(args)[1] or matcher_rescore_flag(args)[1] or matcher_max_fa_flag(args)[1]
+
+
+def matcher_max_fa_flag(args):
+    """matcher.py's --max-fa X among its optional arguments -> (X or None, error message or None).  Beside the three parsers
+    above (whose signatures stay) for the same reason: every refusal ends the command with status 2 and one line on stderr
+    before anything heavy is imported.  Refused: X not a number in 0 < X <= 1, --max-fa without --dense (the significance is
+    judged by the dense matcher's background), --max-fa with --rescore (the rescored songs have no background)."""
+    x, given, i = None, False, 0
+    while i < len(args):
+        a = args[i]
+        if a == "--max-fa" or a.startswith("--max-fa="):
+            val = a[9:] if a.startswith("--max-fa=") else (args[i + 1] if i + 1 < len(args) else "")
+            i += 0 if a.startswith("--max-fa=") else 1
+            given = True
+            try:
+                x = float(val)
+            except ValueError:
+                x = None
+            if x is None or not 0.0 < x <= 1.0:         # (a NaN fails the comparison too)
+                return None, "matcher: --max-fa is a false-alarm probability, 0 < X <= 1 (got %r)" % val
+        i += 1
+    if not given:
+        return None, None
+    if "--dense" not in args:
+        return x, "matcher: --max-fa judges an answer by the background of the dense matcher; it needs --dense"
+    if any(a == "--rescore" or a.startswith("--rescore=") for a in args):
+        return x, "matcher: --max-fa and --rescore exclude each other: the rescored songs have no background to be judged by"
+    return x, None

@@ -99,6 +99,8 @@ SYMBOLS = {
                                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "pfann_match_windows_dense_topn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
                                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pfann_match_windows_dense_topn_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
+                                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pfann_match_windows_dense_part": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
                                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "pfann_match_windows_dense_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64,

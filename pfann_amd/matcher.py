@@ -1,5 +1,5 @@
 """Matcher CLI, drop-in for the reference's matcher.py:
-    python matcher.py <query list> <database dir> <result file> [--top N] [--no-bin] [--dense] [--rescore N]
+    python matcher.py <query list> <database dir> <result file> [--top N] [--no-bin] [--dense] [--max-fa X] [--rescore N]
 
 Same argv and outputs (matcher.py:34-42,84,158-163): `<result>` TSV "query\\tanswer",
 `<result-stem>_detail.csv` with header query,answer,score,time,part_scores, and
@@ -17,6 +17,14 @@ Optional flags after the three positional arguments (without them every output i
              columns: the TSV and _detail.csv from the best song, `.bin` from the per-song block, _top.csv from the ranked
              list.  Defined for frame_shift_mul 1, score_alpha 0 and the python path (anything else: exit status 2); a query
              of more than 64 segments gets the error row and one line on stderr.
+  --max-fa X  (with --dense, 0 < X <= 1) also write `<result-stem>_fa.csv`, header query,rank,answer,score,time,log10_fa,detected:
+             up to max(N, 1) ranked songs per query (N from --top), best first, each with the log10 of the chance that the best of
+             the query's candidates reaches its score when the query holds nothing of the database -- judged by the query's own
+             background, the moments of all its other full alignments from the same pass (pfann_match_windows_dense_topn_stats),
+             with the better-ranked entries and the entry itself left out (pfann_amd/significance.py) -- and detected = 1 exactly
+             when log10_fa <= log10(X): the open-set answer, "this query is (not) in the database".  Every other file is byte for
+             byte what the command writes without the flag; an unreadable query, or one over 64 segments, gets
+             name,1,error,-inf,0,0.0,0.  Needs --dense, excludes --rescore (exit status 2).
   --rescore N  (1..64, with --no-bin) the nominated matcher names its N best songs per query (pfann_match_topn) and EVERY
              alignment of those N songs is then scored with the dense arithmetic (pfann_match_songs_dense, csrc/dense_songs.hip):
              a song's rescored entry is byte for byte --dense's entry for it, at the cost of a few thousand database rows per
@@ -28,6 +36,7 @@ None of them is supported by a song-sharded multi-GPU run (PFANN_GPUS / WORLD_SI
 import csv
 import ctypes
 import gc
+import math
 import os
 import sys
 import threading
@@ -39,7 +48,8 @@ import torch
 from .builder import embed_file_batches, gather_round
 from .database import Database
 from .dist import finish_ranks, init_ranks, self_launch_if_asked
-from .launch import DENSE_MAX_SEGMENTS, RESCORE_MAX_SEGMENTS, matcher_dense_flag, matcher_flags, matcher_rescore_flag
+from .launch import (DENSE_MAX_SEGMENTS, RESCORE_MAX_SEGMENTS, matcher_dense_flag, matcher_flag_error, matcher_flags, matcher_max_fa_flag,
+                     matcher_rescore_flag)
 from .engine import Engine
 from .musicdata import MusicDataset
 from .utils import StageTimer, StartupClock, get_logger, init_logger, read_config
@@ -53,10 +63,16 @@ class ResultWriter:
     query's block in place (pwrite) -- the shards' score blocks never travel to another rank, and the file ends up
     byte-identical to the one a single process appends (error rows stay the zeros the file was created with)."""
 
-    def __init__(self, result_file, n_songs, ranks=None, n_queries=0, song_range=None, top=False, no_bin=False):
+    def __init__(self, result_file, n_songs, ranks=None, n_queries=0, song_range=None, top=False, no_bin=False, max_fa=None):
         self.n_songs = n_songs
         self.no_bin = no_bin
         self.ftop = None
+        self.ffa = None
+        if max_fa is not None:                      # --dense --max-fa X: the calibrated ranked answers
+            self.log10_x = math.log10(max_fa)
+            self.ffa = open(os.path.splitext(result_file)[0] + "_fa.csv", "w", encoding="utf8", newline="\n")
+            self.fa = csv.writer(self.ffa)
+            self.fa.writerow(["query", "rank", "answer", "score", "time", "log10_fa", "detected"])
         self.sharded = ranks is not None and ranks.sharded
         self.text = ranks is None or ranks.rank == 0
         self._run = None            # [address, bytes, arrays kept alive] of the pending run of score blocks
@@ -117,9 +133,16 @@ class ResultWriter:
         for rank, (ans, sco, tim) in enumerate(rows, 1):
             self.top.writerow([name, rank, ans, sco, tim])
 
+    def write_fa(self, name, rows, log10_fa):
+        """rows: ranked (answer, score, time), best first; log10_fa aligned with them"""
+        for rank, ((ans, sco, tim), fa) in enumerate(zip(rows, log10_fa), 1):
+            self.fa.writerow([name, rank, ans, sco, tim, float(fa), int(fa <= self.log10_x)])
+
     def write_error(self, name, qi=None):
         if self.ftop is not None:
             self.write_top(name, [("error", -1e999, 0)])
+        if self.ffa is not None:
+            self.fa.writerow([name, 1, "error", -1e999, 0, 0.0, 0])
         if self.sharded or self.no_bin:             # (sharded: the block is already zero)
             if self.text:
                 self.fout.write("%s\t%s\n" % (name, "error"))
@@ -134,6 +157,8 @@ class ResultWriter:
             self.fout2.flush()
         if self.ftop is not None:
             self.ftop.flush()
+        if self.ffa is not None:
+            self.ffa.flush()
 
     def close(self):
         self._flush_run()
@@ -142,6 +167,8 @@ class ResultWriter:
             self.fout2.close()
         if self.ftop is not None:
             self.ftop.close()
+        if self.ffa is not None:
+            self.ffa.close()
         if self.no_bin:
             pass
         elif self.sharded:
@@ -155,12 +182,12 @@ def main(argv=None):
     if len(argv) < 4:
         print("Usage: python %s <query list> <database dir> <result file>" % argv[0])
         return 1
-    top_n, no_bin, err = matcher_flags(argv[4:])
-    dense, dense_err = matcher_dense_flag(argv[4:])
-    rescore, rescore_err = matcher_rescore_flag(argv[4:])
-    if err or dense_err or rescore_err:
-        print(err or dense_err or rescore_err, file=sys.stderr)
+    err = matcher_flag_error(argv[4:])
+    if err:
+        print(err, file=sys.stderr)
         return 2
+    top_n, no_bin, _ = matcher_flags(argv[4:])
+    dense, rescore, max_fa = matcher_dense_flag(argv[4:])[0], matcher_rescore_flag(argv[4:])[0], matcher_max_fa_flag(argv[4:])[0]
     rc = self_launch_if_asked(argv)         # PFANN_GPUS=N: N ranks of this command, one per GPU
     if rc is not None:
         return rc
@@ -222,7 +249,10 @@ def main(argv=None):
         if int(db.song_pos[-1]):
             wq = torch.zeros((19, db.d), device=db.index.device)
             wq[:, 0] = 1.0
-            db.query_dense_batch(wq, [0], [19], max(top_n, 1), want_song_scores=not no_bin)
+            if max_fa is not None:                  # (the call of the run: dense_ws is sized before the first timed group)
+                db.query_dense_stats_batch(wq, [0], [19], max(top_n, 1), want_song_scores=not no_bin)
+            else:
+                db.query_dense_batch(wq, [0], [19], max(top_n, 1), want_song_scores=not no_bin)
     elif rescore:
         try:
             db._dense_check("matcher --rescore")
@@ -244,7 +274,7 @@ def main(argv=None):
     db.timer = timer
     tm_0 = time.time()
     out = ResultWriter(result_file, len(db.songList), ranks=ranks, n_queries=len(dataset), song_range=db.song_range,
-                       top=top_n > 0, no_bin=no_bin)
+                       top=top_n > 0, no_bin=no_bin, max_fa=max_fa)
 
     too_long = lambda n: dense and n > DENSE_MAX_SEGMENTS
 
@@ -264,7 +294,8 @@ def main(argv=None):
             qlen = [n for _, n, _ in good]
             qstart = np.concatenate([[0], np.cumsum(qlen)[:-1]])
             if dense:
-                ps = db.query_dense_launch_chunks(emb, qstart, qlen, max(top_n, 1), want_song_scores=not no_bin)
+                ps = db.query_dense_launch_chunks(emb, qstart, qlen, max(top_n, 1), want_song_scores=not no_bin,
+                                                  stats=max_fa is not None)
             elif rescore:                          # search + top-N match + the listed songs' alignments: no per-song block
                 ps = [(0, len(good), db.query_rescore_launch(emb, qstart, qlen, rescore))]
             elif top_n and no_bin:                 # search + top-N match: no per-song block, so nothing to cut into chunks
@@ -278,7 +309,11 @@ def main(argv=None):
         it = iter(items)
         for j0, j1, p in ps:
             results = {}
-            if dense:
+            if dense and max_fa is not None:
+                answers, ranked, fas = db.query_dense_stats_finish(p, reuse_buffers=True)
+                for (i, _, _), r, rows, fa in zip(good[j0:j1], answers, ranked, fas):
+                    results[i] = r + (rows if top_n else None, (rows, fa))
+            elif dense:
                 answers, ranked = db.query_dense_finish(p, reuse_buffers=True)
                 for (i, _, _), r, rows in zip(good[j0:j1], answers, ranked):
                     results[i] = r + (rows if top_n else None,)
@@ -314,10 +349,13 @@ def main(argv=None):
         if n == 0 or too_long(n):                                         # matcher.py:94-107
             out.write_error(name, qi=i)
         else:
-            sco, (sid, tim), song_score, rows = results[i]
+            sco, (sid, tim), song_score, rows = results[i][:4]
             out.write(name, db.songList[sid], sco, tim, song_score, qi=i)   # sid == -1 -> last song (matcher.py:138)
             if rows is not None:
                 out.write_top(name, [(db.songList[s], sc, t) for sc, (s, t) in rows])
+            if max_fa is not None:
+                rows, fa = results[i][4]
+                out.write_fa(name, [(db.songList[s], sc, t) for sc, (s, t) in rows], fa)
 
     # matcher.py:120-126 asks the model for norm=False and L2-normalises on the CPU; the same formula runs inside the
     # projection kernel here.  One launch group = PFANN_MAX_BATCH windows (512 ten-second queries): enough 128x128

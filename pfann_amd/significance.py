@@ -13,6 +13,9 @@ match must not vouch for itself), a candidate that overlaps its song in only m o
 the candidates per overlap length (from the song lengths alone), and Q is the normal upper tail.  It is a union bound under a
 normal model of the totals, reported as log10 p (<= 0): a window is a detection at false-alarm level X when log10 p <= log10 X.
 
+A RANKED list (pfann_match_windows_dense_topn_stats: the n best songs of the window and the same moments from one pass) gets one
+such number per entry, log10_false_alarms_ranked: entry i is judged with entries 0..i left out of the background.
+
 numpy and math only; pure host code.
 """
 import math
@@ -92,6 +95,11 @@ def log10_false_alarm(score, n, song, offset, stats, hist, song_len):
     if 0 <= offset <= int(song_len[song]) - n:          # the best is a full candidate: its own integers are in the sums
         c, s1, s2 = quantised(T)
         N, S1, S2 = N - c, S1 - s1, S2 - s2
+    return _log10_tail(T, n, N, S1, S2, hist)
+
+
+def _log10_tail(T, n, N, S1, S2, hist):
+    """the module docstring's formula for a total T against the background (N, S1, S2) of a window of n rows"""
     if N < 2:
         return 0.0
     mu = S1 / float(1 << SUM_SHIFT) / N
@@ -116,3 +124,29 @@ def log10_false_alarms(results, stats, n, excl, hists, song_len):
     hist = hists(n, excl)
     return np.asarray([log10_false_alarm(r["score"], n, r["song"], r["offset"], (s["n_full"], s["sum_q"], s["sumsq_q"]), hist, song_len)
                        for r, s in zip(results, stats)], dtype=np.float64)
+
+
+def log10_false_alarms_ranked(entries, n, stats, hist, song_len):
+    """log10_false_alarm for every entry of one window's ranked list (pfann_match_windows_dense_topn_stats): entries (song,
+    offset, score fields, best first, padding song -1 last), n the window's rows, stats its (n_full, sum_q, sumsq_q), hist
+    overlap_histogram for (n, the recording's excluded song) -> float64 [len(entries)].
+    Entry i is judged against the window's full candidates with entries 0..i left out: every one of them that is itself a full
+    candidate (0 <= offset <= len_s - n) takes its three quantised integers out of the sums.  A true match must not vouch for
+    itself, nor may a better-ranked one: a second copy of a stretch would inflate the variance the third copy is judged by.
+    Only 0..i are taken out, so an entry's value does not depend on how long a list was asked for (the prefix rule), and
+    entry 0 is exactly log10_false_alarm.  Padding takes nothing out and gets 0."""
+    n = int(n)
+    out = np.zeros(len(entries), dtype=np.float64)
+    N, S1, S2 = (int(x) for x in stats)
+    if n < 1 or int(np.sum(hist)) == 0:
+        return out
+    for i, e in enumerate(entries):
+        song, offset = int(e["song"]), int(e["offset"])
+        if song < 0:
+            continue
+        T = best_total(e["score"], n)
+        if 0 <= offset <= int(song_len[song]) - n:
+            c, s1, s2 = quantised(T)
+            N, S1, S2 = N - c, S1 - s1, S2 - s2
+        out[i] = _log10_tail(T, n, N, S1, S2, hist)
+    return out
