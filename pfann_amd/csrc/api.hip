@@ -1170,6 +1170,21 @@ int pfann_topk_merge_lists(pfann_db *db, const float *D_lists_dev, const int64_t
 
 }  // extern "C"
 
+// The handle's grow-only scratch buffers (match_scratch, win_scratch, dense_ws): the larger buffer is allocated FIRST and the old
+// one freed only when that succeeded, so a failed allocation leaves the handle as it was (the error is reported as PF_HIP
+// reports it); for that moment the old and the new bytes are both held.  drain: earlier calls on `st` may still read the old
+// buffer -- wait for them first (not needed where the caller has drained the stream already).
+static int grow_scratch(void **buf, size_t *bytes, size_t need, hipStream_t st, bool drain) {
+    if (*bytes >= need) return 0;
+    if (drain) PF_HIP(hipStreamSynchronize(st));
+    void *grown = nullptr;
+    PF_HIP(hipMalloc(&grown, need));
+    if (*buf) (void)hipFree(*buf);
+    *buf = grown;
+    *bytes = need;
+    return 0;
+}
+
 // pfann_match and pfann_match_topn: one set-up, one launch plan (topn == 0: the single answer and the per-song block)
 static int match_call(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *qstart,
                       const int32_t *qlen, int64_t nQ, int max_qlen, int frame_shift_mul, float score_alpha, int mode,
@@ -1202,13 +1217,7 @@ static int match_call(pfann_db *db, const float *q, const int64_t *labels, int k
     if (P > 8192 || phased) {     // longer than the LDS candidate buffer, or phased: per-query slabs in HBM
         if ((int64_t)max_qlen * k > (1 << 22)) { set_error("match: query of %d rows x top_k %d is too long", max_qlen, k); return -1; }
         const size_t need = (size_t)nQ * P * 12 + (size_t)nQ * sizeof(int);
-        if (db->match_scratch_bytes < need) {
-            PF_HIP(hipStreamSynchronize((hipStream_t)stream));
-            if (db->match_scratch) (void)hipFree(db->match_scratch);
-            db->match_scratch = nullptr; db->match_scratch_bytes = 0;
-            PF_HIP(hipMalloc(&db->match_scratch, need));
-            db->match_scratch_bytes = need;
-        }
+        if (grow_scratch(&db->match_scratch, &db->match_scratch_bytes, need, (hipStream_t)stream, true)) return -1;
         a.gkeys = reinterpret_cast<unsigned long long *>(db->match_scratch);
         a.gscore = reinterpret_cast<float *>(a.gkeys + (size_t)nQ * P);
         if (phased) { a.ncand = reinterpret_cast<int *>(a.gscore + (size_t)nQ * P); a.phase = 1; }
@@ -1216,6 +1225,70 @@ static int match_call(pfann_db *db, const float *q, const int64_t *labels, int k
     a.results = results; a.song_scores = song_scores;
     a.topn = topn; a.top = top; a.n_found = n_found;
     return launch_match(a, (hipStream_t)stream);
+}
+
+// a recording is matched against ALL songs by one GPU: a shard of a song-sharded database cannot answer
+static bool db_is_whole(const pfann_db *db) {
+    return db->label_base == 0 && db->song_lo == 0 && db->song_hi == db->n_songs && !db->song_pos_h.empty() &&
+           db->song_pos_h.back() == db->n;
+}
+static int refuse_shard() {
+    set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
+    return -1;
+}
+
+// pfann_match_windows (n == 0: results) and pfann_match_windows_topn (n >= 1: top, n_found or null): one set of checks, ONE
+// routing -- so that entry 0 of a ranked window and the window's answer come from the same summation order -- and one general
+// path; `what` names the call
+static int windows_call(const char *what, pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart,
+                        const int32_t *rlen, int64_t nR, int window, int hop, int frame_shift_mul, float score_alpha, int mode,
+                        const int64_t *wfirst, pfann_match_result *results, int n, pfann_match_result *top, int32_t *n_found,
+                        void *stream) {
+    PF_HIP(hipSetDevice(db->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool ranked = n != 0;
+    if (db->d % 4 != 0) { set_error("%s: d %% 4 != 0 (d=%d)", what, db->d); return -1; }
+    if (window < 1 || hop < 1 || k < 1 || nR < 0) { set_error("%s: window=%d hop=%d k=%d nR=%lld", what, window, hop, k, (long long)nR); return -1; }
+    if (mode != 0 && mode != 1) { set_error("%s: unknown mode %d", what, mode); return -1; }
+    if (!db_is_whole(db)) return refuse_shard();
+    if (nR == 0) return 0;
+    const int C = match_windows_chunk(k, window, hop);
+    // PFANN_WINDOWS_GENERAL=1: every call takes the general path (A/B timing, tests); read per call, no process state
+    const char *env = getenv("PFANN_WINDOWS_GENERAL");
+    const bool forced = env != nullptr && env[0] != 0 && !(env[0] == '0' && env[1] == 0);
+    const bool fast = !forced && mode == 0 && frame_shift_mul == 1 && score_alpha == 0.0f && C >= 1 && n <= WIN_TOPN_FAST &&
+                      db->n_songs < (1 << 28) - 1 && db->max_song_rows < (1ll << 28) - 2 * WIN_SMAX;
+    if (fast) {
+        WindowsTopnArgs a;
+        a.db = db->emb; a.dbh = db->emb_h; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+        a.q = q; a.labels = labels; a.k = k; a.rstart = rstart; a.rlen = rlen; a.nR = nR;
+        a.window = window; a.hop = hop; a.C = C; a.wfirst = wfirst; a.results = results;
+        a.n = n; a.top = top; a.n_found = n_found;
+        return ranked ? launch_match_windows_topn(a, st) : launch_match_windows(a, st);
+    }
+    // ---- general path: the windows become (qstart, qlen) pairs on the device and go through match_call.  Its launches
+    // are sized on the host, so the number of windows is read back first: ONE synchronisation with the stream.
+    int64_t nW = 0;
+    PF_HIP(hipMemcpyAsync(&nW, wfirst + nR, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PF_HIP(hipStreamSynchronize(st));
+    if (nW <= 0) return 0;
+    const size_t o_ql = (size_t)nW * sizeof(int64_t), need = o_ql + (size_t)nW * sizeof(int32_t);
+    if (grow_scratch(&db->win_scratch, &db->win_scratch_bytes, need, st, false)) return -1;    // (the stream was drained above)
+    int64_t *qs = reinterpret_cast<int64_t *>(db->win_scratch);
+    int32_t *ql = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(db->win_scratch) + o_ql);
+    if (launch_expand_windows(rstart, rlen, nR, window, hop, wfirst, nW, qs, ql, st)) return -1;
+    // windows per match_call: its HBM slabs (lists longer than the LDS, or few queries) stay below 256 MB
+    int64_t P = 1;
+    while (P < (int64_t)window * k) P <<= 1;
+    const int64_t step = P > 8192 ? std::max<int64_t>(1, (256ll << 20) / (P * 12)) : 65536;
+    for (int64_t j0 = 0; j0 < nW; j0 += step) {
+        const int64_t m = std::min(step, nW - j0);
+        if (match_call(db, q, labels, k, qs + j0, ql + j0, m, window, frame_shift_mul, score_alpha, mode, 0,
+                       ranked ? nullptr : results + j0, nullptr, n, ranked ? top + j0 * n : nullptr,
+                       n_found != nullptr ? n_found + j0 : nullptr, stream))
+            return -1;
+    }
+    return 0;
 }
 
 extern "C" {
@@ -1238,67 +1311,11 @@ int pfann_match_topn(pfann_db *db, const float *q, const int64_t *labels, int k,
                       nullptr, n, top, n_found, stream);
 }
 
-// a recording is matched against ALL songs by one GPU: a shard of a song-sharded database cannot answer
-static bool db_is_whole(const pfann_db *db) {
-    return db->label_base == 0 && db->song_lo == 0 && db->song_hi == db->n_songs && !db->song_pos_h.empty() &&
-           db->song_pos_h.back() == db->n;
-}
-static int refuse_shard() {
-    set_error("match_windows: the handle holds a shard of the database (monitor mode is not song-sharded)");
-    return -1;
-}
-
 int pfann_match_windows(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart, const int32_t *rlen,
                         int64_t nR, int window, int hop, int frame_shift_mul, float score_alpha, int mode,
                         const int64_t *wfirst, pfann_match_result *results, void *stream) {
-    PF_HIP(hipSetDevice(db->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (db->d % 4 != 0) { set_error("match_windows: d %% 4 != 0 (d=%d)", db->d); return -1; }
-    if (window < 1 || hop < 1 || k < 1 || nR < 0) { set_error("match_windows: window=%d hop=%d k=%d nR=%lld", window, hop, k, (long long)nR); return -1; }
-    if (mode != 0 && mode != 1) { set_error("match_windows: unknown mode %d", mode); return -1; }
-    if (!db_is_whole(db)) return refuse_shard();
-    if (nR == 0) return 0;
-    const int C = match_windows_chunk(k, window, hop);
-    // PFANN_WINDOWS_GENERAL=1: every call takes the general path (A/B timing, tests); read per call, no process state
-    const char *env = getenv("PFANN_WINDOWS_GENERAL");
-    const bool forced = env != nullptr && env[0] != 0 && !(env[0] == '0' && env[1] == 0);
-    const bool fast = !forced && mode == 0 && frame_shift_mul == 1 && score_alpha == 0.0f && C >= 1 &&
-                      db->n_songs < (1 << 28) - 1 && db->max_song_rows < (1ll << 28) - 2 * WIN_SMAX;
-    if (fast) {
-        WindowsArgs a;
-        a.db = db->emb; a.dbh = db->emb_h; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
-        a.q = q; a.labels = labels; a.k = k; a.rstart = rstart; a.rlen = rlen; a.nR = nR;
-        a.window = window; a.hop = hop; a.C = C; a.wfirst = wfirst; a.results = results;
-        return launch_match_windows(a, st);
-    }
-    // ---- general path: the windows become (qstart, qlen) pairs on the device and go through pfann_match.  Its launches
-    // are sized on the host, so the number of windows is read back first: ONE synchronisation with the stream.
-    int64_t nW = 0;
-    PF_HIP(hipMemcpyAsync(&nW, wfirst + nR, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    PF_HIP(hipStreamSynchronize(st));
-    if (nW <= 0) return 0;
-    const size_t o_ql = (size_t)nW * sizeof(int64_t), need = o_ql + (size_t)nW * sizeof(int32_t);
-    if (db->win_scratch_bytes < need) {              // grow, then free: a failed allocation leaves the handle as it was
-        void *grown = nullptr;
-        PF_HIP(hipMalloc(&grown, need));
-        if (db->win_scratch) (void)hipFree(db->win_scratch);       // (the stream was drained above)
-        db->win_scratch = grown;
-        db->win_scratch_bytes = need;
-    }
-    int64_t *qs = reinterpret_cast<int64_t *>(db->win_scratch);
-    int32_t *ql = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(db->win_scratch) + o_ql);
-    if (launch_expand_windows(rstart, rlen, nR, window, hop, wfirst, nW, qs, ql, st)) return -1;
-    // windows per pfann_match call: its HBM slabs (lists longer than the LDS, or few queries) stay below 256 MB
-    int64_t P = 1;
-    while (P < (int64_t)window * k) P <<= 1;
-    const int64_t step = P > 8192 ? std::max<int64_t>(1, (256ll << 20) / (P * 12)) : 65536;
-    for (int64_t j0 = 0; j0 < nW; j0 += step) {
-        const int64_t n = std::min(step, nW - j0);
-        if (pfann_match(db, q, labels, k, qs + j0, ql + j0, n, window, frame_shift_mul, score_alpha, mode, 0, results + j0,
-                        nullptr, stream))
-            return -1;
-    }
-    return 0;
+    return windows_call("match_windows", db, q, labels, k, rstart, rlen, nR, window, hop, frame_shift_mul, score_alpha, mode, wfirst,
+                        results, 0, nullptr, nullptr, stream);
 }
 
 // ---- dense matcher: the three calls on one handle of the whole database, the parts on any fp32 handle, the merges on any handle
@@ -1424,14 +1441,8 @@ static int dense_ranked_call(const char *what, pfann_db *db, bool shard, const f
     if (env != nullptr && env[0] != 0 && atoll(env) > 0) cap = std::min<int64_t>(cap, atoll(env));
     const int64_t step = std::min(n_slots, std::max<int64_t>(1, cap / wps));
     const size_t need = (size_t)step * wps * songs * 8;
-    if (db->dense_ws_bytes < need) {                 // grow, then free: a failed allocation leaves the handle as it was
-        PF_HIP(hipStreamSynchronize(st));            // (the one exception to the asynchrony: earlier calls may still read it)
-        void *grown = nullptr;
-        PF_HIP(hipMalloc(&grown, need));
-        if (db->dense_ws) (void)hipFree(db->dense_ws);
-        db->dense_ws = grown;
-        db->dense_ws_bytes = need;
-    }
+    // (growing drains the stream, the one exception to the asynchrony: earlier calls may still read the workspace)
+    if (grow_scratch(&db->dense_ws, &db->dense_ws_bytes, need, st, true)) return -1;
     a.ws = reinterpret_cast<unsigned long long *>(db->dense_ws); a.wps = wps;
     a.n = n; a.top = top; a.n_found = n_found; a.song_scores = song_scores; a.stats = stats;
     if (stats != nullptr) PF_HIP(hipMemsetAsync(stats, 0, (size_t)n_windows * sizeof(pfann_dense_stats), st));
@@ -1530,55 +1541,10 @@ int pfann_match_windows_dense_topn_merge(pfann_db *db, const pfann_match_result 
 int pfann_match_windows_topn(pfann_db *db, const float *q, const int64_t *labels, int k, const int64_t *rstart, const int32_t *rlen,
                              int64_t nR, int window, int hop, int frame_shift_mul, float score_alpha, int mode,
                              const int64_t *wfirst, int n, pfann_match_result *top, int32_t *n_found, void *stream) {
-    PF_HIP(hipSetDevice(db->device));
-    hipStream_t st = (hipStream_t)stream;
     if (n < 1 || n > 64) { set_error("match_windows_topn: n=%d outside 1..64", n); return -1; }
     if (top == nullptr) { set_error("match_windows_topn: top_dev is null"); return -1; }
-    if (db->d % 4 != 0) { set_error("match_windows_topn: d %% 4 != 0 (d=%d)", db->d); return -1; }
-    if (window < 1 || hop < 1 || k < 1 || nR < 0) { set_error("match_windows_topn: window=%d hop=%d k=%d nR=%lld", window, hop, k, (long long)nR); return -1; }
-    if (mode != 0 && mode != 1) { set_error("match_windows_topn: unknown mode %d", mode); return -1; }
-    if (!db_is_whole(db)) return refuse_shard();
-    if (nR == 0) return 0;
-    // the routing of pfann_match_windows, so that entry 0 and its answer come from the same summation order
-    const int C = match_windows_chunk(k, window, hop);
-    const char *env = getenv("PFANN_WINDOWS_GENERAL");
-    const bool forced = env != nullptr && env[0] != 0 && !(env[0] == '0' && env[1] == 0);
-    const bool fast = !forced && mode == 0 && frame_shift_mul == 1 && score_alpha == 0.0f && C >= 1 && n <= WIN_TOPN_FAST &&
-                      db->n_songs < (1 << 28) - 1 && db->max_song_rows < (1ll << 28) - 2 * WIN_SMAX;
-    if (fast) {
-        WindowsTopnArgs a;
-        a.db = db->emb; a.dbh = db->emb_h; a.d = db->d; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
-        a.q = q; a.labels = labels; a.k = k; a.rstart = rstart; a.rlen = rlen; a.nR = nR;
-        a.window = window; a.hop = hop; a.C = C; a.wfirst = wfirst; a.results = nullptr;
-        a.n = n; a.top = top; a.n_found = n_found;
-        return launch_match_windows_topn(a, st);
-    }
-    // ---- general path: as pfann_match_windows', through pfann_match_topn (ONE synchronisation: the number of windows)
-    int64_t nW = 0;
-    PF_HIP(hipMemcpyAsync(&nW, wfirst + nR, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    PF_HIP(hipStreamSynchronize(st));
-    if (nW <= 0) return 0;
-    const size_t o_ql = (size_t)nW * sizeof(int64_t), need = o_ql + (size_t)nW * sizeof(int32_t);
-    if (db->win_scratch_bytes < need) {              // grow, then free: a failed allocation leaves the handle as it was
-        void *grown = nullptr;
-        PF_HIP(hipMalloc(&grown, need));
-        if (db->win_scratch) (void)hipFree(db->win_scratch);       // (the stream was drained above)
-        db->win_scratch = grown;
-        db->win_scratch_bytes = need;
-    }
-    int64_t *qs = reinterpret_cast<int64_t *>(db->win_scratch);
-    int32_t *ql = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(db->win_scratch) + o_ql);
-    if (launch_expand_windows(rstart, rlen, nR, window, hop, wfirst, nW, qs, ql, st)) return -1;
-    int64_t P = 1;
-    while (P < (int64_t)window * k) P <<= 1;
-    const int64_t step = P > 8192 ? std::max<int64_t>(1, (256ll << 20) / (P * 12)) : 65536;
-    for (int64_t j0 = 0; j0 < nW; j0 += step) {
-        const int64_t m = std::min(step, nW - j0);
-        if (pfann_match_topn(db, q, labels, k, qs + j0, ql + j0, m, window, frame_shift_mul, score_alpha, mode, 0, n, top + j0 * n,
-                             n_found != nullptr ? n_found + j0 : nullptr, stream))
-            return -1;
-    }
-    return 0;
+    return windows_call("match_windows_topn", db, q, labels, k, rstart, rlen, nR, window, hop, frame_shift_mul, score_alpha, mode,
+                        wfirst, nullptr, n, top, n_found, stream);
 }
 
 int pfann_song_scores_to_seconds(pfann_db *db, float *song_scores_dev, int64_t n_pairs, int frame_shift_mul, double hop_size,

@@ -150,8 +150,10 @@ struct WindowsArgs {
 };
 // window starts one workgroup can take (0: the lists do not fit the LDS, the caller expands the windows instead)
 int match_windows_chunk(int k, int window, int hop);
+// The fast path of api.hip's windows_call, which fills one WindowsTopnArgs for both forms.  The two launchers are one helper
+// (monitor.hip: launch_windows -- bounds, LDS opt-in and size, fp32 / fp16 instantiation) over their own kernel pair.
 int launch_match_windows(const WindowsArgs &a, hipStream_t s);
-// pfann_match_windows_topn, fast path: the n best songs of every window (results unused: top[windows][n], n_found or null)
+// the n best songs of every window (results unused: top[windows][n], n_found or null)
 static constexpr int WIN_TOPN_FAST = 64;    // longest ranked list the windowed kernel keeps (its per-window lists live in LDS)
 struct WindowsTopnArgs : WindowsArgs {
     int n; pfann_match_result *top; int *n_found;

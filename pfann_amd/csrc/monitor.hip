@@ -27,6 +27,7 @@
 #include "kernels.h"
 #include "match_common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace pfann {
 
@@ -563,40 +564,35 @@ int match_windows_chunk(int k, int window, int hop) {
     return (int)std::max<int64_t>(0, std::min<int64_t>(c, 64));     // one lane per window
 }
 
-int launch_match_windows(const WindowsArgs &a, hipStream_t s) {
+// what the two windowed launches share: the chunk and song bounds, the LDS opt-in and size, the fp32 / fp16 instantiation
+// (and the ranked launch's own argument check); `what` names the call in a refusal, `tag` is its ProfScope tag
+template <class Args>
+static int launch_windows(const char *what, const char *tag, void (*k32)(Args), void (*k16)(Args), const Args &a, hipStream_t s) {
     if (a.nR <= 0) return 0;
-    if (a.C < 1 || a.C > match_windows_chunk(a.k, a.window, a.hop)) { set_error("match_windows: chunk of %d windows does not fit", a.C); return -1; }
-    if (a.n_songs >= (1 << 28) - 1) { set_error("match_windows: too many songs"); return -1; }
+    if (a.C < 1 || a.C > match_windows_chunk(a.k, a.window, a.hop)) { set_error("%s: chunk of %d windows does not fit", what, a.C); return -1; }
+    if (a.n_songs >= (1 << 28) - 1) { set_error("%s: too many songs", what); return -1; }
+    if constexpr (std::is_same<Args, WindowsTopnArgs>::value)
+        if (a.n < 1 || a.n > WIN_TOPN_FAST || a.top == nullptr) { set_error("%s: top-N arguments (n=%d)", what, a.n); return -1; }
     const int lds_max = MAXC * 8 + (MAXC + 8) * 2;
-    const void *fn = a.db != nullptr ? (const void *)match_windows_kernel<false> : (const void *)match_windows_kernel<true>;
-    if (ensure_dyn_lds(fn, lds_max)) return -1;
+    void (*fn)(Args) = a.db != nullptr ? k32 : k16;
+    if (ensure_dyn_lds((const void *)fn, lds_max)) return -1;
     int P = 1;
     while (P < ((a.C - 1) * a.hop + a.window) * a.k) P <<= 1;
     const size_t lds = (size_t)P * 8 + (size_t)(P + 8) * 2;
-    ProfScope ps("seq_match_windows", s);
-    if (a.db != nullptr) PF_LAUNCH(match_windows_kernel<false>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
-    else PF_LAUNCH(match_windows_kernel<true>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
+    ProfScope ps(tag, s);
+    PF_LAUNCH(fn, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
     PF_HIP(hipGetLastError());
     return 0;
 }
 
+int launch_match_windows(const WindowsArgs &a, hipStream_t s) {
+    return launch_windows("match_windows", "seq_match_windows", match_windows_kernel<false>, match_windows_kernel<true>, a, s);
+}
+
 int launch_match_windows_topn(const WindowsTopnArgs &a, hipStream_t s) {
-    if (a.nR <= 0) return 0;
-    if (a.C < 1 || a.C > match_windows_chunk(a.k, a.window, a.hop)) { set_error("match_windows_topn: chunk of %d windows does not fit", a.C); return -1; }
-    if (a.n_songs >= (1 << 28) - 1) { set_error("match_windows_topn: too many songs"); return -1; }
-    if (a.n < 1 || a.n > WIN_TOPN_FAST || a.top == nullptr) { set_error("match_windows_topn: top-N arguments (n=%d)", a.n); return -1; }
     static_assert(MAXC <= (1 << WTOP_AL_BITS) && MAXC < (1 << WTOP_CNT_BITS), "a ranked word holds an alignment index and a count");
-    const int lds_max = MAXC * 8 + (MAXC + 8) * 2;
-    const void *fn = a.db != nullptr ? (const void *)match_windows_topn_kernel<false> : (const void *)match_windows_topn_kernel<true>;
-    if (ensure_dyn_lds(fn, lds_max)) return -1;
-    int P = 1;
-    while (P < ((a.C - 1) * a.hop + a.window) * a.k) P <<= 1;
-    const size_t lds = (size_t)P * 8 + (size_t)(P + 8) * 2;
-    ProfScope ps("seq_match_windows_topn", s);
-    if (a.db != nullptr) PF_LAUNCH(match_windows_topn_kernel<false>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
-    else PF_LAUNCH(match_windows_topn_kernel<true>, dim3(WIN_GRID), dim3(WIN_NT), lds, s, a);
-    PF_HIP(hipGetLastError());
-    return 0;
+    return launch_windows("match_windows_topn", "seq_match_windows_topn", match_windows_topn_kernel<false>,
+                          match_windows_topn_kernel<true>, a, s);
 }
 
 __global__ void noop_monitor_kernel() {}

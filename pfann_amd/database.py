@@ -366,9 +366,7 @@ class DeviceIndex:
         entries past the candidate songs are song -1 / score -inf; with to_host=False the two device tensors (uint8
         [nQ, n, 24], int32 [nQ]) that topn_to_host turns into the arrays later."""
         q, labels, qs_np, ql_np = self._match_args(q, labels, qstart, qlen)
-        nQ, n = int(ql_np.shape[0]), int(n)
-        if not 1 <= n <= 64:
-            raise _l.PfannError("match_topn: n=%d outside 1..64" % n)
+        nQ, n = int(ql_np.shape[0]), self._check_n("match_topn", n)
         qs, ql = self._upload_ranges(qs_np, ql_np)
         top = torch.empty((nQ, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
         n_found = torch.empty((nQ,), device=self.device, dtype=torch.int32)
@@ -381,26 +379,60 @@ class DeviceIndex:
             return top, n_found
         return self.topn_to_host(top, n_found)
 
-    def match_windows(self, q, labels, rstart, rlen, window, hop, fsm=1, alpha=0.0, mode=0, to_host=True):
-        """Sequence matcher over every window of nR recordings (pfann_match_windows): recording r owns rows
-        [rstart[r], rstart[r] + rlen[r]) of q / labels.  -> (results, wfirst): window i of recording r -- rows
-        [i * hop, i * hop + window) of it -- is results[wfirst[r] + i], field for field what `match` returns for that
-        slice; results is the structured array, or with to_host=False the device tensor."""
+    @staticmethod
+    def _check_n(what, n):
+        """-> n as an int, or the refusal of a ranked list that is not 1..64 long"""
+        n = int(n)
+        if not 1 <= n <= 64:
+            raise _l.PfannError("%s: n=%d outside 1..64" % (what, n))
+        return n
+
+    @staticmethod
+    def _window_hop(what, window, hop):
+        """-> (window, hop) as ints, or the ValueError every windowed call raises first"""
         window, hop = int(window), int(hop)
         if window < 1 or hop < 1:
-            raise ValueError("match_windows: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
+            raise ValueError("%s: window and hop are positive numbers of segments (got %r, %r)" % (what, window, hop))
+        return window, hop
+
+    def _alloc_outputs(self, nW, n, kinds):
+        """the outputs of a windowed call, by kind, in the order of the C arguments (None stays None: a null pointer)"""
+        rsz = ctypes.sizeof(_l.MatchResult)
+        form = {"res": ((nW, rsz), torch.uint8), "top": ((nW, n, rsz), torch.uint8), "n_found": ((nW,), torch.int32),
+                "stats": ((nW, 3), torch.int64), "ss": ((nW, self.n_songs, 2), torch.float32), "words": ((nW,), torch.int64)}
+        return tuple(None if kd is None else torch.empty(form[kd][0], device=self.device, dtype=form[kd][1]) for kd in kinds)
+
+    def _windows_lib_call(self, what, head, n, out):
+        """pfann_<what>(handle, *head, [n,] the outputs, stream)"""
+        _l.check(getattr(self.lib, "pfann_" + what)(self.handle, *head, *(() if n is None else (n,)),
+                                                    *(None if t is None else t.data_ptr() for t in out), self._stream()),
+                 "pfann_" + what)
+
+    def _match_windows(self, what, q, labels, rstart, rlen, window, hop, fsm, alpha, mode, n=None):
+        """match_windows (n None) and match_windows_topn: the outputs on the device -> ((res,) or (top, n_found), wfirst).
+        Order of refusals: window / hop, n, the assertion."""
+        window, hop = self._window_hop(what, window, hop)
+        if n is not None:
+            n = self._check_n(what, n)
         q, labels, rs_np, rl_np = self._match_args(q, labels, rstart, rlen)
         nR = int(rl_np.shape[0])
         assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
         wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
         nW = int(wfirst[-1])
-        res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        out = self._alloc_outputs(nW, n, ("res",) if n is None else ("top", "n_found"))
         if nW:
             rs, rl = self._upload_ranges(rs_np, rl_np)
             wf = _l.upload_async(wfirst, self.device, np.int64)
-            _l.check(self.lib.pfann_match_windows(self.handle, q.data_ptr(), labels.data_ptr(), labels.shape[1], rs.data_ptr(),
-                                                  rl.data_ptr(), nR, window, hop, int(fsm), float(alpha), int(mode),
-                                                  wf.data_ptr(), res.data_ptr(), self._stream()), "pfann_match_windows")
+            self._windows_lib_call(what, (q.data_ptr(), labels.data_ptr(), labels.shape[1], rs.data_ptr(), rl.data_ptr(), nR, window,
+                                          hop, int(fsm), float(alpha), int(mode), wf.data_ptr()), n, out)
+        return out, wfirst
+
+    def match_windows(self, q, labels, rstart, rlen, window, hop, fsm=1, alpha=0.0, mode=0, to_host=True):
+        """Sequence matcher over every window of nR recordings (pfann_match_windows): recording r owns rows
+        [rstart[r], rstart[r] + rlen[r]) of q / labels.  -> (results, wfirst): window i of recording r -- rows
+        [i * hop, i * hop + window) of it -- is results[wfirst[r] + i], field for field what `match` returns for that
+        slice; results is the structured array, or with to_host=False the device tensor."""
+        (res,), wfirst = self._match_windows("match_windows", q, labels, rstart, rlen, window, hop, fsm, alpha, mode)
         return (self.results_to_host(res) if to_host else res), wfirst
 
     def match_windows_topn(self, q, labels, rstart, rlen, window, hop, n, fsm=1, alpha=0.0, mode=0, to_host=True):
@@ -408,41 +440,15 @@ class DeviceIndex:
         -> ((top [nW, n] of RESULT_DTYPE, n_found int32 [nW]), wfirst): row wfirst[r] + i is, field for field, what
         `match_topn` returns for window i of recording r, and its entry 0 is match_windows' answer; with to_host=False
         the two device tensors (uint8 [nW, n, 24], int32 [nW]) that topn_to_host turns into the arrays later."""
-        window, hop, n = int(window), int(hop), int(n)
-        if window < 1 or hop < 1:
-            raise ValueError("match_windows_topn: window and hop are positive numbers of segments (got %r, %r)" % (window, hop))
-        if not 1 <= n <= 64:
-            raise _l.PfannError("match_windows_topn: n=%d outside 1..64" % n)
-        q, labels, rs_np, rl_np = self._match_args(q, labels, rstart, rlen)
-        nR = int(rl_np.shape[0])
-        assert rs_np.shape[0] == nR and (nR == 0 or int((rs_np + rl_np).max()) <= q.shape[0]), "recordings exceed the rows given"
-        wfirst = np.pad(np.cumsum(window_counts(rl_np, window, hop)), (1, 0)).astype(np.int64)
-        nW = int(wfirst[-1])
-        top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
-        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
-        if nW:
-            rs, rl = self._upload_ranges(rs_np, rl_np)
-            wf = _l.upload_async(wfirst, self.device, np.int64)
-            _l.check(self.lib.pfann_match_windows_topn(self.handle, q.data_ptr(), labels.data_ptr(), labels.shape[1], rs.data_ptr(),
-                                                       rl.data_ptr(), nR, window, hop, int(fsm), float(alpha), int(mode),
-                                                       wf.data_ptr(), n, top.data_ptr(), n_found.data_ptr(), self._stream()),
-                     "pfann_match_windows_topn")
-        return ((top, n_found) if not to_host else self.topn_to_host(top, n_found)), wfirst
-
-    @staticmethod
-    def _dense_window_hop(what, window, hop):
-        """-> (window, hop) as ints, or the ValueError every dense call raises first"""
-        window, hop = int(window), int(hop)
-        if window < 1 or hop < 1:
-            raise ValueError("%s: window and hop are positive numbers of segments (got %r, %r)" % (what, window, hop))
-        return window, hop
+        out, wfirst = self._match_windows("match_windows_topn", q, labels, rstart, rlen, window, hop, fsm, alpha, mode, n)
+        return (self.topn_to_host(*out) if to_host else out), wfirst
 
     def _dense_args(self, what, rstart, rlen, window, hop, exclude_song, q_rows=None):
         """the windowed arguments every dense call shares -> (window, hop, nR, nW, wfirst, device rstart, rlen, wfirst,
         exclude_song or None).  q_rows: the rows of q that the recordings must lie in (None for dense_merge, which reads no q).
         Order of refusals: window / hop, the two assertions, exclude_song's shape; the three arrays are uploaded even when
         there is no window (the caller then makes no library call)."""
-        window, hop = self._dense_window_hop(what, window, hop)
+        window, hop = self._window_hop(what, window, hop)
         rs_np, rl_np = np.ascontiguousarray(rstart, dtype=np.int64), np.ascontiguousarray(rlen, dtype=np.int32)
         nR = int(rl_np.shape[0])
         assert rs_np.shape[0] == nR, "one start per recording"
@@ -457,19 +463,27 @@ class DeviceIndex:
         rs, rl = self._upload_ranges(rs_np, rl_np)
         return window, hop, nR, int(wfirst[-1]), wfirst, rs, rl, _l.upload_async(wfirst, self.device, np.int64), ex
 
+    def _dense_call(self, what, q, rstart, rlen, window, hop, exclude_song, kinds, n=None):
+        """The six dense calls over q (pfann_<what>): kinds names the form's outputs in the order of its C arguments (_alloc_outputs),
+        n is the list length of a ranked form -> (the outputs on the device, wfirst); no library call without a window.
+        Order of refusals: window / hop, n, then _dense_args'."""
+        if n is not None:
+            self._window_hop(what, window, hop)
+            n = self._check_n(what, n)
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args(what, rstart, rlen, window, hop, exclude_song, q.shape[0])
+        q = q.to(self.device, torch.float32).contiguous()
+        out = self._alloc_outputs(nW, n, kinds)
+        if nW:
+            self._windows_lib_call(what, (q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop, wf.data_ptr(), nW,
+                                          ex.data_ptr() if ex is not None else None), n, out)
+        return out, wfirst
+
     def match_windows_dense(self, q, rstart, rlen, window, hop, exclude_song=None, to_host=True):
         """Dense matcher over every window of nR recordings (pfann_match_windows_dense): no labels -- every alignment of
         every song is a candidate of every window, so the answer is what `match` gives for the slice when each row's label
         list is the whole database.  Recordings, windows and the return value (results, wfirst) are match_windows'.
         exclude_song: one song id per recording (-1: none) whose alignments are no candidates.  window <= 64, fp32 rows."""
-        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense", rstart, rlen, window, hop, exclude_song,
-                                                                       q.shape[0])
-        q = q.to(self.device, torch.float32).contiguous()
-        res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
-        if nW:
-            _l.check(self.lib.pfann_match_windows_dense(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
-                                                        wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
-                                                        res.data_ptr(), self._stream()), "pfann_match_windows_dense")
+        (res,), wfirst = self._dense_call("match_windows_dense", q, rstart, rlen, window, hop, exclude_song, ("res",))
         return (self.results_to_host(res) if to_host else res), wfirst
 
     def match_windows_dense_stats(self, q, rstart, rlen, window, hop, exclude_song=None, to_host=True):
@@ -477,16 +491,7 @@ class DeviceIndex:
         the two fixed-point sums of the totals of its full candidates, significance.STATS_DTYPE, from the same pass.
         -> ((results, stats), wfirst): results byte for byte match_windows_dense's; with to_host=False the device tensors
         (uint8 [nW, 24], int64 [nW, 3])."""
-        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_stats", rstart, rlen, window, hop,
-                                                                       exclude_song, q.shape[0])
-        q = q.to(self.device, torch.float32).contiguous()
-        res = torch.empty((nW, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
-        stats = torch.empty((nW, 3), device=self.device, dtype=torch.int64)
-        if nW:
-            _l.check(self.lib.pfann_match_windows_dense_stats(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
-                                                              wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
-                                                              res.data_ptr(), stats.data_ptr(), self._stream()),
-                     "pfann_match_windows_dense_stats")
+        (res, stats), wfirst = self._dense_call("match_windows_dense_stats", q, rstart, rlen, window, hop, exclude_song, ("res", "stats"))
         if not to_host:
             return (res, stats), wfirst
         return (self.results_to_host(res), self.stats_to_host(stats)), wfirst
@@ -497,58 +502,27 @@ class DeviceIndex:
         from .significance import STATS_DTYPE
         return np.ascontiguousarray(stats_dev.cpu().numpy()).view(STATS_DTYPE).reshape(-1)
 
+    def _dense_ranked_to_host(self, top, n_found, ss, *stats):
+        return self.topn_to_host(top, n_found) + (ss.cpu().numpy() if ss is not None else None,) + tuple(map(self.stats_to_host, stats))
+
     def match_windows_dense_topn(self, q, rstart, rlen, window, hop, n, exclude_song=None, want_song_scores=False, to_host=True):
         """Ranked dense answers (pfann_match_windows_dense_topn): the n best songs of every window over EVERY alignment, and
         with want_song_scores the per-song block [nW, n_songs, 2] of (float32 score, best offset in frames; zeros where the
         score is not > 0).  Recordings, windows and exclude_song as in match_windows_dense.
         -> ((top [nW, n] of RESULT_DTYPE, n_found int32 [nW], block or None), wfirst): entry 0 of a window is
         match_windows_dense's answer; with to_host=False the device tensors (uint8 [nW, n, 24], int32 [nW], float32 block)."""
-        window, hop = self._dense_window_hop("match_windows_dense_topn", window, hop)
-        n = int(n)
-        if not 1 <= n <= 64:
-            raise _l.PfannError("match_windows_dense_topn: n=%d outside 1..64" % n)
-        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_topn", rstart, rlen, window, hop,
-                                                                       exclude_song, q.shape[0])
-        q = q.to(self.device, torch.float32).contiguous()
-        top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
-        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
-        ss = torch.empty((nW, self.n_songs, 2), device=self.device, dtype=torch.float32) if want_song_scores else None
-        if nW:
-            _l.check(self.lib.pfann_match_windows_dense_topn(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
-                                                             wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None, n,
-                                                             top.data_ptr(), n_found.data_ptr(),
-                                                             ss.data_ptr() if ss is not None else None, self._stream()),
-                     "pfann_match_windows_dense_topn")
-        if not to_host:
-            return (top, n_found, ss), wfirst
-        return self.topn_to_host(top, n_found) + (ss.cpu().numpy() if ss is not None else None,), wfirst
+        out, wfirst = self._dense_call("match_windows_dense_topn", q, rstart, rlen, window, hop, exclude_song,
+                                       ("top", "n_found", "ss" if want_song_scores else None), n)
+        return (self._dense_ranked_to_host(*out) if to_host else out), wfirst
 
     def match_windows_dense_topn_stats(self, q, rstart, rlen, window, hop, n, exclude_song=None, want_song_scores=False, to_host=True):
         """match_windows_dense_topn with the background statistics of every window from the same pass
         (pfann_match_windows_dense_topn_stats): the ranked outputs byte for byte match_windows_dense_topn's, the statistics byte
         for byte match_windows_dense_stats'.  Whole handles only.
         -> ((top, n_found, block or None, stats), wfirst); with to_host=False the device tensors (.., int64 [nW, 3])."""
-        window, hop = self._dense_window_hop("match_windows_dense_topn_stats", window, hop)
-        n = int(n)
-        if not 1 <= n <= 64:
-            raise _l.PfannError("match_windows_dense_topn_stats: n=%d outside 1..64" % n)
-        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_topn_stats", rstart, rlen, window, hop,
-                                                                       exclude_song, q.shape[0])
-        q = q.to(self.device, torch.float32).contiguous()
-        top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
-        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
-        ss = torch.empty((nW, self.n_songs, 2), device=self.device, dtype=torch.float32) if want_song_scores else None
-        stats = torch.empty((nW, 3), device=self.device, dtype=torch.int64)
-        if nW:
-            _l.check(self.lib.pfann_match_windows_dense_topn_stats(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window,
-                                                                   hop, wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None, n,
-                                                                   top.data_ptr(), n_found.data_ptr(),
-                                                                   ss.data_ptr() if ss is not None else None, stats.data_ptr(),
-                                                                   self._stream()),
-                     "pfann_match_windows_dense_topn_stats")
-        if not to_host:
-            return (top, n_found, ss, stats), wfirst
-        return self.topn_to_host(top, n_found) + (ss.cpu().numpy() if ss is not None else None, self.stats_to_host(stats)), wfirst
+        out, wfirst = self._dense_call("match_windows_dense_topn_stats", q, rstart, rlen, window, hop, exclude_song,
+                                       ("top", "n_found", "ss" if want_song_scores else None, "stats"), n)
+        return (self._dense_ranked_to_host(*out) if to_host else out), wfirst
 
     def match_songs_dense(self, q, qstart, qlen, cand, to_host=True):
         """Rescoring stage (pfann_match_songs_dense): every alignment of the songs `cand` lists for each of nQ queries, scored
@@ -588,17 +562,8 @@ class DeviceIndex:
         """This handle's part of match_windows_dense / _stats (pfann_match_windows_dense_part): the handle may hold a shard.
         -> ((words int64 [nW]: the bit patterns of the windows' raw running-best words, 0 where this handle has no candidate;
         the statistics int64 [nW, 3] over this handle's full candidates, or None), wfirst); device tensors for dense_merge."""
-        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_part", rstart, rlen, window, hop,
-                                                                       exclude_song, q.shape[0])
-        q = q.to(self.device, torch.float32).contiguous()
-        words = torch.empty((nW,), device=self.device, dtype=torch.int64)
-        st = torch.empty((nW, 3), device=self.device, dtype=torch.int64) if stats else None
-        if nW:
-            _l.check(self.lib.pfann_match_windows_dense_part(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop,
-                                                             wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
-                                                             words.data_ptr(), st.data_ptr() if st is not None else None,
-                                                             self._stream()), "pfann_match_windows_dense_part")
-        return (words, st), wfirst
+        return self._dense_call("match_windows_dense_part", q, rstart, rlen, window, hop, exclude_song,
+                                ("words", "stats" if stats else None))
 
     def dense_merge(self, words, part_stats, rlen, window, hop, exclude_song=None):
         """words int64 [parts, nW] (and part_stats int64 [parts, nW, 3] or None) of match_windows_dense_part over handles that cut
@@ -627,20 +592,8 @@ class DeviceIndex:
     def match_windows_dense_topn_part(self, q, rstart, rlen, window, hop, n, exclude_song=None):
         """This handle's part of match_windows_dense_topn (pfann_match_windows_dense_topn_part): the n best of its owned songs for
         every window, no per-song block.  -> ((top uint8 [nW, n, 24], n_found int32 [nW]), wfirst); device tensors."""
-        n = int(n)
-        if not 1 <= n <= 64:
-            raise _l.PfannError("match_windows_dense_topn_part: n=%d outside 1..64" % n)
-        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args("match_windows_dense_topn_part", rstart, rlen, window, hop,
-                                                                       exclude_song, q.shape[0])
-        q = q.to(self.device, torch.float32).contiguous()
-        top = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
-        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
-        if nW:
-            _l.check(self.lib.pfann_match_windows_dense_topn_part(self.handle, q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window,
-                                                                  hop, wf.data_ptr(), nW, ex.data_ptr() if ex is not None else None,
-                                                                  n, top.data_ptr(), n_found.data_ptr(), self._stream()),
-                     "pfann_match_windows_dense_topn_part")
-        return (top, n_found), wfirst
+        n = self._check_n("match_windows_dense_topn_part", n)       # (this form refuses n before window and hop)
+        return self._dense_call("match_windows_dense_topn_part", q, rstart, rlen, window, hop, exclude_song, ("top", "n_found"), n)
 
     def dense_topn_merge(self, tops, n_found_parts):
         """tops uint8 [parts, nW, n, 24] and n_found_parts int32 [parts, nW] of match_windows_dense_topn_part, parts in any order
@@ -954,17 +907,23 @@ class Database:
         three score blocks of max_score_pairs pairs therefore exist at any time -- the one being read back, its
         successor, and the first one of the next launch group -- whatever the number of sub-launches (all of them at
         once until round 5: the budget then bounded only the pinned landing buffer)."""
+        return self._launch_chunks(lambda e, qs, ql: self.query_launch(e, qs, ql, want_song_scores, mode),
+                                   getattr(self, "_widest_shard", self.song_range[1] - self.song_range[0]), emb, qstart, qlen,
+                                   want_song_scores)
+
+    def _launch_chunks(self, launch, width, emb, qstart, qlen, want_song_scores):
+        """The one cutter of a launch group: launch(rows, qstart, qlen) over runs of queries whose per-song blocks, `width`
+        songs wide, stay within max_score_pairs (one run without blocks) -> LazyLaunches, see query_launch_chunks"""
         nq = len(qlen)
-        width = max(getattr(self, "_widest_shard", self.song_range[1] - self.song_range[0]), 1)
-        step = max(1, nq) if not want_song_scores else max(1, min(nq, self.max_score_pairs // width))
+        step = max(1, nq) if not want_song_scores else max(1, min(nq, self.max_score_pairs // max(width, 1)))
         qstart = np.asarray(qstart, dtype=np.int64)
 
-        def launch(j0, j1):
+        def cut(j0, j1):
             r0 = int(qstart[j0])
             r1 = int(qstart[j1 - 1]) + int(qlen[j1 - 1])
             sub = emb if (j0 == 0 and j1 == nq) else emb[r0:r1]
-            return self.query_launch(sub, qstart[j0:j1] - r0, qlen[j0:j1], want_song_scores, mode)
-        return LazyLaunches([(j0, min(j0 + step, nq)) for j0 in range(0, nq, step)], launch)
+            return launch(sub, qstart[j0:j1] - r0, qlen[j0:j1])
+        return LazyLaunches([(j0, min(j0 + step, nq)) for j0 in range(0, nq, step)], cut)
 
     def _pinned(self, shape, dtype):
         """one reusable pinned landing buffer per result kind (a pinned allocation costs milliseconds)"""
@@ -976,15 +935,16 @@ class Database:
             self._pin[key] = buf
         return buf[:n].view(shape)
 
-    def _launch(self, emb, match, mode=None, k=None, exclude=None):
+    def _launch(self, emb, match, mode=None, k=None, exclude=None, search=True):
         """The single-GPU launch skeleton: timed event, search, timed event, match(labels, mode) -> dict of what it left on
-        the device, timed event; nothing is read back.  -> that dict + the keys every finish half reads."""
+        the device, timed event; nothing is read back.  -> that dict + the keys every finish half reads.
+        search=False (the dense forms, which pass mode 0): no search -- an empty search stage -- and match() takes no argument."""
         mode = default_mode(mode)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
-        D, I = self.index.search(emb, self.top_k if k is None else int(k), exclude=exclude)
+        I = self.index.search(emb, self.top_k if k is None else int(k), exclude=exclude)[1] if search else None
         ev[1].record()
-        out = match(I, mode)
+        out = match(I, mode) if search else match()
         ev[2].record()
         return dict(out, ev=ev, keep=(emb, I), mode=mode)
 
@@ -1020,11 +980,15 @@ class Database:
         reuse_buffers: the song_score blocks are views of a pinned buffer that the NEXT query_finish overwrites (the CLIs
         write them out at once)."""
         res, land = self._read_back(p)
+        return [r + (b,) for r, b in zip(self._answers(res, p["mode"]), self._blocks(land, len(res), reuse_buffers))]
+
+    @staticmethod
+    def _blocks(land, nq, reuse_buffers):
+        """the per-song block of each of nq queries: None without a landing buffer, else its rows -- views of the pinned
+        buffer with reuse_buffers, a copy otherwise"""
         if land is None:
-            blocks = [None] * len(res)
-        else:
-            blocks = land.numpy() if reuse_buffers else land.numpy().copy()
-        return [r + (b,) for r, b in zip(self._answers(res, p["mode"]), blocks)]
+            return [None] * nq
+        return land.numpy() if reuse_buffers else land.numpy().copy()
 
     def query_batch(self, emb, qstart, qlen, want_song_scores=False, mode=None):
         """emb: torch cuda [sum(qlen), d] unit-norm rows; -> list of (score, (song, time), song_score|None)."""
@@ -1069,16 +1033,24 @@ class Database:
         [rstart[r], rstart[r] + rlen[r]); window, hop in segments.  edge_window > 0: the same labels are matched a second
         time in short windows of that many segments at hop 1 (monitor_finish leaves them in p["edge_rows"]): they place
         the edges of a detection far better than the long windows' scores do (monitor.merge_windows)."""
-        if self.sharded is not None:
-            raise _l.PfannError("monitor mode is not song-sharded: a recording is matched on one GPU against the whole "
-                                "database (run without PFANN_GPUS / ranks)")
+        self._whole_only("monitor mode is", "a recording is matched on one GPU against the whole database")
+        return self._launch(emb, lambda I, mode: self._windows_launched(
+            lambda w, h: self.index.match_windows(emb, I, rstart, rlen, w, h, self.frame_shift_mul, self.score_alpha, mode,
+                                                  to_host=False), window, hop, edge_window))
 
-        def match(I, mode):
-            windows = lambda w, h: self.index.match_windows(emb, I, rstart, rlen, w, h, self.frame_shift_mul, self.score_alpha,
-                                                            mode, to_host=False)
-            res, wfirst = windows(window, hop)
-            return {"res": res, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None, "hop": int(hop)}
-        return self._launch(emb, match)
+    def _whole_only(self, what, why):
+        """the refusal of a form that wants the whole database on one handle, under ranks"""
+        if self.sharded is not None:
+            raise _l.PfannError("%s not song-sharded: %s (run without PFANN_GPUS / ranks)" % (what, why))
+
+    @staticmethod
+    def _windows_launched(windows, window, hop, edge_window=0, long=None):
+        """What a windowed launch leaves for its finish half, from windows(w, h) -> (res or (top, n_found), wfirst) on the device:
+        the long windows -- `long` where the caller has made that call itself --, then, with edge_window > 0, the short windows
+        of the edge pass at hop 1 as "fine" (else None)."""
+        res, wfirst = windows(window, hop) if long is None else long
+        out = {"res": res} if not isinstance(res, tuple) else {"res": res[0], "n_found": res[1]}
+        return dict(out, wfirst=wfirst, fine=windows(edge_window, 1) if edge_window > 0 else None, hop=int(hop))
 
     def _dense_check(self, what):
         """the dense matcher is defined for the default family only: mode 0, frame_shift_mul 1, score_alpha 0.  Under ranks its
@@ -1106,15 +1078,6 @@ class Database:
             return (top, n_found, None), wfirst
         return self.index.match_windows_dense_topn(emb, rstart, rlen, window, hop, n, want_song_scores=want_song_scores, to_host=False)
 
-    def _launch_dense(self, emb, match):
-        """_launch without a search: the three timed events with an empty search stage, mode 0"""
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
-        ev[1].record()
-        out = match()
-        ev[2].record()
-        return dict(out, ev=ev, keep=(emb, None), mode=0)
-
     def monitor_dense_launch(self, emb, rstart, rlen, window, hop, edge_window=0, stats=False):
         """monitor_launch on the dense matcher (pfann_match_windows_dense): no search, every alignment of every song is a
         candidate of every window (and of every short window of the edge pass).  -> what monitor_finish reads.
@@ -1122,18 +1085,17 @@ class Database:
         statistics for monitor_dense_stats_finish; the edge pass stays as it is (its rows only place edges)."""
         self._dense_check("monitor_dense_launch")
 
+        def windows(w, h):
+            (res, _), wfirst = self._dense_windows(emb, rstart, rlen, w, h)
+            return res, wfirst
+
         def match():
-            def windows(w, h):
-                (res, _), wfirst = self._dense_windows(emb, rstart, rlen, w, h)
-                return res, wfirst
-            out = {}
-            if stats:
-                (res, out["stats"]), wfirst = self._dense_windows(emb, rstart, rlen, window, hop, stats=True)
-                out["rows_of"] = (int(window), np.asarray(rlen, dtype=np.int64))
-            else:
-                res, wfirst = windows(window, hop)
-            return dict(out, res=res, wfirst=wfirst, fine=windows(edge_window, 1) if edge_window > 0 else None, hop=int(hop))
-        return self._launch_dense(emb, match)
+            if not stats:
+                return self._windows_launched(windows, window, hop, edge_window)
+            (res, st), wfirst = self._dense_windows(emb, rstart, rlen, window, hop, stats=True)
+            return dict(self._windows_launched(windows, window, hop, edge_window, long=(res, wfirst)), stats=st,
+                        rows_of=(int(window), np.asarray(rlen, dtype=np.int64)))
+        return self._launch(emb, match, mode=0, search=False)
 
     def monitor_dense_stats_finish(self, p):
         """Second half of monitor_dense_launch(stats=True): -> (what monitor_finish returns, per recording a float64 array
@@ -1147,26 +1109,28 @@ class Database:
         wfirst, fsm = p["wfirst"], self.frame_shift_mul
         rows = monitor_rows(raw, wfirst, p["hop"], p["mode"], fsm, self.hop_size)
         self._edge_finish(p, fsm)
+        hists, song_len = self._hists()
+        fa = [sg.log10_false_alarms(raw[a:b], stats[a:b], min(window, int(L)), -1, hists, song_len)
+              for a, b, L in zip(wfirst[:-1], wfirst[1:], rlen)]
+        return rows, fa
+
+    def _hists(self):
+        """-> (the significance.OverlapHistograms of the songs' lengths, kept until they change; the lengths)"""
+        from . import significance as sg
         song_len = np.diff(self.song_pos)
         if getattr(self, "_overlap_hists", None) is None or not np.array_equal(self._overlap_hists.song_len, song_len):
             self._overlap_hists = sg.OverlapHistograms(song_len)
-        fa = [sg.log10_false_alarms(raw[a:b], stats[a:b], min(window, int(L)), -1, self._overlap_hists, song_len)
-              for a, b, L in zip(wfirst[:-1], wfirst[1:], rlen)]
-        return rows, fa
+        return self._overlap_hists, song_len
 
     def monitor_dense_topn_launch(self, emb, rstart, rlen, window, hop, n, edge_window=0):
         """monitor_topn_launch on the ranked dense matcher (pfann_match_windows_dense_topn): no search, the n best songs of every
         window -- and of every short window of the edge pass -- over every alignment.  -> what monitor_dense_topn_finish reads."""
         self._dense_check("monitor_dense_topn_launch")
 
-        def match():
-            def windows(w, h):
-                (top, n_found, _), wfirst = self._dense_windows_topn(emb, rstart, rlen, w, h, n)
-                return (top, n_found), wfirst
-            (top, n_found), wfirst = windows(window, hop)
-            return {"res": top, "n_found": n_found, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None,
-                    "hop": int(hop)}
-        return self._launch_dense(emb, match)
+        def windows(w, h):
+            (top, n_found, _), wfirst = self._dense_windows_topn(emb, rstart, rlen, w, h, n)
+            return (top, n_found), wfirst
+        return self._launch(emb, lambda: self._windows_launched(windows, window, hop, edge_window), mode=0, search=False)
 
     def monitor_dense_topn_finish(self, p):
         """Second half of monitor_dense_topn_launch: what monitor_topn_finish returns, votes = len_s + window rows - 1 (every
@@ -1204,20 +1168,12 @@ class Database:
             assert int(wfirst[-1]) == ql.shape[0]
             self.index.song_scores_to_seconds(ss, 1, self.hop_size)
             return dict(out, res=top, n_found=n_found, ss=ss)
-        return self._launch_dense(emb, match)
+        return self._launch(emb, match, mode=0, search=False)
 
     def query_dense_launch_chunks(self, emb, qstart, qlen, n=1, want_song_scores=False, stats=False):
         """query_dense_launch cut by the score-block budget, lazily, exactly as query_launch_chunks cuts query_launch"""
-        nq = len(qlen)
-        step = max(1, nq) if not want_song_scores else max(1, min(nq, self.max_score_pairs // max(len(self.songList), 1)))
-        qstart = np.asarray(qstart, dtype=np.int64)
-
-        def launch(j0, j1):
-            r0 = int(qstart[j0])
-            r1 = int(qstart[j1 - 1]) + int(qlen[j1 - 1])
-            sub = emb if (j0 == 0 and j1 == nq) else emb[r0:r1]
-            return self.query_dense_launch(sub, qstart[j0:j1] - r0, qlen[j0:j1], n, want_song_scores, stats)
-        return LazyLaunches([(j0, min(j0 + step, nq)) for j0 in range(0, nq, step)], launch)
+        return self._launch_chunks(lambda e, qs, ql: self.query_dense_launch(e, qs, ql, n, want_song_scores, stats),
+                                   len(self.songList), emb, qstart, qlen, want_song_scores)
 
     def query_dense_finish(self, p, reuse_buffers=False):
         """Second half: -> (answers, ranked): answers as query_finish gives them, [(score, (song, time_s), song_score|None)]
@@ -1228,11 +1184,7 @@ class Database:
     def _dense_answers(self, p, reuse_buffers):
         """the read-back of a query_dense_launch -> (raw ranked lists RESULT_DTYPE [nQ, n], answers, ranked)"""
         res, land = self._read_back(p)
-        if land is None:
-            blocks = [None] * len(res)
-        else:
-            blocks = land.numpy() if reuse_buffers else land.numpy().copy()
-        answers = [r + (b,) for r, b in zip(self._answers(res[:, 0], 0), blocks)]
+        answers = [r + (b,) for r, b in zip(self._answers(res[:, 0], 0), self._blocks(land, len(res), reuse_buffers))]
         return res, answers, self._answers(res, 0, topn_tuples)
 
     def query_dense_batch(self, emb, qstart, qlen, n=1, want_song_scores=False):
@@ -1249,13 +1201,11 @@ class Database:
         from . import significance as sg
         res, answers, ranked = self._dense_answers(p, reuse_buffers)
         stats = self.index.stats_to_host(p["stats"])     # (complete behind the event the read-back waited for)
-        song_len = np.diff(self.song_pos)
-        if getattr(self, "_overlap_hists", None) is None or not np.array_equal(self._overlap_hists.song_len, song_len):
-            self._overlap_hists = sg.OverlapHistograms(song_len)
+        hists, song_len = self._hists()
         fa = []
         for top, st, L, rows in zip(res, stats, p["rows_of"], ranked):
             L = int(L)
-            v = sg.log10_false_alarms_ranked(top, L, (st["n_full"], st["sum_q"], st["sumsq_q"]), self._overlap_hists(L), song_len)
+            v = sg.log10_false_alarms_ranked(top, L, (st["n_full"], st["sum_q"], st["sumsq_q"]), hists(L), song_len)
             fa.append(v[:len(rows)])
         return answers, ranked, fa
 
@@ -1269,13 +1219,9 @@ class Database:
         every alignment of those songs (pfann_match_songs_dense), on the one stream; nothing is read back.  A song's rescored
         entry is byte for byte the ranked dense matcher's entry for it, so the answer is query_dense_batch's wherever the dense
         answer's song is among the n nominated ones.  A query of more than 64 segments keeps its nominated list."""
-        if self.ranks is not None:
-            raise _l.PfannError("query_rescore_launch: rescoring is not song-sharded: the nominated songs are scored on one GPU "
-                                "against the whole database (run without PFANN_GPUS / ranks)")
+        self._whole_only("query_rescore_launch: rescoring is", "the nominated songs are scored on one GPU against the whole database")
         self._dense_check("query_rescore_launch")
-        n = int(n)
-        if not 1 <= n <= 64:
-            raise _l.PfannError("query_rescore_launch: n=%d outside 1..64" % n)
+        n = DeviceIndex._check_n("query_rescore_launch", n)
 
         def match(I, mode):
             out = self._match_topn(emb, I, qstart, qlen, n, mode)
@@ -1299,31 +1245,26 @@ class Database:
         row, and score / song / time exactly as query_finish reports them for that slice (no candidate: -inf, -1, 0)."""
         return self._windows_finish(p, self.frame_shift_mul)
 
-    def _windows_finish(self, p, fsm):
-        out = monitor_rows(self._read_back(p)[0], p["wfirst"], p["hop"], p["mode"], fsm, self.hop_size)
-        self._edge_finish(p, fsm)
+    def _windows_finish(self, p, fsm, rows=monitor_rows):
+        out = rows(self._read_back(p)[0], p["wfirst"], p["hop"], p["mode"], fsm, self.hop_size)
+        self._edge_finish(p, fsm, rows)
         return out
 
-    def _edge_finish(self, p, fsm):
+    def _edge_finish(self, p, fsm, rows=monitor_rows):
+        """the edge pass of a windowed launch, read back and formatted by `rows` (monitor_rows, or monitor_topn_rows for a
+        ranked launch) into p["edge_rows"]"""
         if p.get("fine") is not None:                    # (complete behind the same event; the timer has its split already)
             edge, efirst = p["fine"]
-            edge = self._read_back({"res": edge, "ev": p["ev"][-1:]})[0]
-            p["edge_rows"] = monitor_rows(edge, efirst, 1, p["mode"], fsm, self.hop_size)
+            edge = self._read_back({"res": edge[0] if isinstance(edge, tuple) else edge, "ev": p["ev"][-1:]})[0]
+            p["edge_rows"] = rows(edge, efirst, 1, p["mode"], fsm, self.hop_size)
 
     def monitor_topn_launch(self, emb, rstart, rlen, window, hop, n, edge_window=0):
         """monitor_launch with ranked answers (pfann_match_windows_topn): the n best songs of every window, and of every
         short window of the edge pass, from the same single search."""
-        if self.sharded is not None:
-            raise _l.PfannError("monitor mode is not song-sharded: a recording is matched on one GPU against the whole "
-                                "database (run without PFANN_GPUS / ranks)")
-
-        def match(I, mode):
-            windows = lambda w, h: self.index.match_windows_topn(emb, I, rstart, rlen, w, h, n, self.frame_shift_mul,
-                                                                 self.score_alpha, mode, to_host=False)
-            (top, n_found), wfirst = windows(window, hop)
-            return {"res": top, "n_found": n_found, "wfirst": wfirst, "fine": windows(edge_window, 1) if edge_window > 0 else None,
-                    "hop": int(hop)}
-        return self._launch(emb, match)
+        self._whole_only("monitor mode is", "a recording is matched on one GPU against the whole database")
+        return self._launch(emb, lambda I, mode: self._windows_launched(
+            lambda w, h: self.index.match_windows_topn(emb, I, rstart, rlen, w, h, n, self.frame_shift_mul, self.score_alpha, mode,
+                                                       to_host=False), window, hop, edge_window))
 
     def monitor_topn_finish(self, p):
         """Second half: -> (per recording a structured array [windows, n] of (w0, score, song, time_s, votes), best song
@@ -1333,13 +1274,8 @@ class Database:
         return self._windows_topn_finish(p, self.frame_shift_mul)
 
     def _windows_topn_finish(self, p, fsm):
-        wfirst = p["wfirst"]
-        out = monitor_topn_rows(self._read_back(p)[0], wfirst, p["hop"], p["mode"], fsm, self.hop_size)
-        n_found = p["n_found"].cpu().numpy()
-        if p.get("fine") is not None:
-            (edge, _), efirst = p["fine"]
-            edge = self._read_back({"res": edge, "ev": p["ev"][-1:]})[0]
-            p["edge_rows"] = monitor_topn_rows(edge, efirst, 1, p["mode"], fsm, self.hop_size)
+        out = self._windows_finish(p, fsm, monitor_topn_rows)
+        n_found, wfirst = p["n_found"].cpu().numpy(), p["wfirst"]
         return out, [n_found[a:b] for a, b in zip(wfirst[:-1], wfirst[1:])]
 
     # ---- updates: songs added and removed without a rebuild (include/pfann_amd.h: "Database updates") ---------------
@@ -1424,12 +1360,7 @@ class Database:
             raise _l.PfannError("self_match: top=%d outside 1..64" % top)
         if dense:
             self._dense_check("self_match")
-        if dense and self.sharded is not None:
-            raise _l.PfannError("self_match: the dense self-match is not song-sharded: the whole database sits on one handle (run "
-                                "without PFANN_GPUS / ranks)")
-        if self.sharded is not None:
-            raise _l.PfannError("self-match is not song-sharded: the whole database sits on one handle (run without "
-                                "PFANN_GPUS / ranks)")
+        self._whole_only("self_match: the dense self-match is" if dense else "self-match is", "the whole database sits on one handle")
         song_lo, song_hi = int(song_lo), int(song_hi)
         if not 0 <= song_lo <= song_hi <= len(self.songList):
             raise ValueError("self_match: songs [%d, %d) outside 0..%d" % (song_lo, song_hi, len(self.songList)))
@@ -1443,18 +1374,18 @@ class Database:
                 if top > 1:
                     (res, n_found, _), wfirst = self.index.match_windows_dense_topn(q, rstart, rlen, window, hop, top,
                                                                                     exclude_song=own, to_host=False)
-                    return {"res": res, "n_found": n_found, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
-                res, wfirst = self.index.match_windows_dense(q, rstart, rlen, window, hop, exclude_song=own, to_host=False)
-                return {"res": res, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
-            return self._launch_dense(q, match_dense)
+                    long = (res, n_found), wfirst
+                else:
+                    long = self.index.match_windows_dense(q, rstart, rlen, window, hop, exclude_song=own, to_host=False)
+                return dict(self._windows_launched(None, window, hop, long=long), songs=(song_lo, song_hi))
+            return self._launch(q, match_dense, mode=0, search=False)
 
         def match(I, mode):
             if top > 1:
-                (res, n_found), wfirst = self.index.match_windows_topn(q, I, rstart, rlen, window, hop, top, 1, self.score_alpha,
-                                                                       mode, to_host=False)
-                return {"res": res, "n_found": n_found, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
-            res, wfirst = self.index.match_windows(q, I, rstart, rlen, window, hop, 1, self.score_alpha, mode, to_host=False)
-            return {"res": res, "wfirst": wfirst, "hop": int(hop), "songs": (song_lo, song_hi)}
+                long = self.index.match_windows_topn(q, I, rstart, rlen, window, hop, top, 1, self.score_alpha, mode, to_host=False)
+            else:
+                long = self.index.match_windows(q, I, rstart, rlen, window, hop, 1, self.score_alpha, mode, to_host=False)
+            return dict(self._windows_launched(None, window, hop, long=long), songs=(song_lo, song_hi))
         return self._launch(q, match, k=k, exclude=(lo, hi))
 
     def self_match_finish(self, p):
