@@ -167,8 +167,19 @@ int pfann_resample_to_mono(pfann_ctx *ctx, const int16_t *pcm_dev, int n_ch, con
 /* Debug/verification taps: copy the activation after sub-layer `idx` (0..15) of the LAST
  * pfann_encode call's first `B` samples to host as NCHW floats.  Returns numel or <0. */
 int64_t pfann_debug_activation(pfann_ctx *ctx, int idx, int64_t B, float *host, int64_t cap);
-/* Enable keeping those taps (costs one D2D copy per sub-layer; off by default). */
+/* Enable keeping those taps (costs one D2D copy per sub-layer; off by default): pfann_debug_keep_at(ctx, on, 0). */
 void pfann_debug_keep(pfann_ctx *ctx, int on);
+/* Taps mode and position.  mode 0: off.  mode 1: all 16 taps; the fused path then materialises the first conv instead
+ * of folding it into sub-layer 1's loader, i.e. it runs ANOTHER plan than production for sub-layers 0 and 1.  mode 2: the
+ * taps are taken beside the production plan, which is left exactly as it is (first conv folded, same kernels, same
+ * embeddings bit for bit): taps 1..15 are kept and tap 0, where that plan folds the first conv and never materialises it,
+ * is reported absent by pfann_debug_activation with an error that says so (a plan that does not fold it -- the unfused
+ * path, PFANN_NO_FOLD_FIRST, a first conv of more than 256 channels -- has all 16 in either mode).  first_sample: the taps
+ * are those of the 8 consecutive samples of the chunk that start there, clamped to the chunk (a chunk of B samples keeps
+ * [min(first_sample, B - 8), ...), all of a chunk of 8 or fewer); pfann_debug_activation's sample 0 is the first kept
+ * one.  Taps are defined for single-stream calls (pfann_set_streams 1) of at most max_batch samples.  Returns mode, <0 on
+ * bad arguments. */
+int pfann_debug_keep_at(pfann_ctx *ctx, int mode, int64_t first_sample);
 
 /* Selects the LayerNorm-fused encoder path (default: on whenever the model supports it, i.e.
  * every conv2 is a full conv; off = separate LayerNorm kernels).  Returns the state now in
@@ -199,8 +210,28 @@ int64_t pfann_set_plan_batch(pfann_ctx *ctx, int64_t n);
 
 /* Number of internal HIP streams (1..8) a batch is split over inside pfann_encode /
  * pfann_segment_embed*: the MFMA-bound GEMMs of one sub-batch overlap the HBM-bound passes
- * of another.  Work is forked from and joined back into the caller's stream.  Returns n. */
+ * of another.  Work is forked from and joined back into the caller's stream.  Returns n.
+ * A call of B samples (at most max_batch) runs on min(n, B / 128) streams, in chunks of B / streams samples (the first
+ * B % streams one larger).  The stream count changes no kernel choice: every chunk runs the kernel variants the whole call
+ * would run on one stream -- the fingerprints are bit-identical for every n, pinned plan or not -- and owns a slice of the
+ * split-K scratch.  A layer whose partials for one chunk would pass 256 MiB is not split (a rule of the layer and the chunk
+ * alone, whatever earlier calls allocated), so n streams hold at most n x 256 MiB of it; if the scratch cannot be allocated
+ * the call fails instead of running other kernels. */
 int pfann_set_streams(pfann_ctx *ctx, int n);
+
+/* The launches of one pfann_encode chunk as text, from the functions the launchers themselves execute
+ * (csrc/encoder_plan.h); needs no device and no context.  cfg: the model (max_batch <= 0: 512); B: samples of the call
+ * (above max_batch: the first chunk); plan_batch: as pfann_set_plan_batch; precision: as pfann_set_encoder_precision;
+ * fused: 1 / 0 as pfann_set_fused_layernorm, -1 the context's default; taps: the mode of pfann_debug_keep_at; n_streams: as
+ * pfann_set_streams.  Per stream chunk one line `chunk K b0= B= splitk_offset= splitk_bytes=`, then one line per launch:
+ * `NAME grid= block= lds= layer= tile= n_splits= first= out_P=` -- the kernel with its template arguments as a kernel
+ * trace prints it, workgroups, workgroup size, dynamic LDS bytes, the sub-layer (-1: the head) and, for the fused conv
+ * layers, tile, split-K chunks (0: not split), whether the first conv is folded in and the LayerNorm partial slots per
+ * sample of the output.  Last line: `flags fused= precision= plan_batch= fold_first= chunks= splitk_bytes= part_slots=`
+ * (the call's split-K scratch and the partial slots pfann_create allocates).  Returns the text's length, -2 when buf is
+ * too small, -1 on bad arguments. */
+int pfann_encode_plan(const pfann_config *cfg, int64_t B, int64_t plan_batch, int precision, int fused, int taps, int n_streams,
+                      char *buf, int len);
 
 /* ---- database: device-resident fingerprints, exact search, sequence match ------------ */
 typedef struct pfann_db pfann_db;

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libpfann_amd.so")
 SOURCES = ["api.hip", "mel.hip", "encoder.hip", "encoder_fused.hip", "search.hip", "search_f16.hip", "rerank.hip", "monitor.hip", "dense.hip", "dense_songs.hip", "dbstore.hip", "wavio.hip"]
-HEADERS = [os.path.abspath(__file__), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "search_common.h"), os.path.join(CSRC, "search_plan.h"), os.path.join(CSRC, "match_common.h"),
+HEADERS = [os.path.abspath(__file__), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "search_common.h"), os.path.join(CSRC, "search_plan.h"), os.path.join(CSRC, "encoder_plan.h"), os.path.join(CSRC, "match_common.h"),
            os.path.join(HERE, "..", "include", "pfann_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"] + os.environ.get("PFANN_HIPCC_FLAGS", "").split()
 # mel.hip without the SLP vectoriser, i.e. without packed-fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32:

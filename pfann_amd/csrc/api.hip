@@ -91,9 +91,12 @@ struct pfann_ctx {
     size_t splitk_bytes = 0;
     float *stats = nullptr;         // [max_batch][2] (mean, rstd) of the current GEMM input
     int64_t part_slots = 0;         // per sample
-    bool keep = false;
+    int keep = 0;                   // verification taps (pfann_debug_keep_at): 0 off, 1 every sub-layer with the first conv
+                                    // materialised, 2 sub-layers 1..15 beside the production plan
+    int64_t keep_first = 0;         // first of the (up to) 8 consecutive samples of a chunk whose taps are kept
     int64_t keep_B = 0;
     float *dbg[16] = {};
+    bool dbg_has[16] = {};          // tap written by the last call
     float *dbg_tmp = nullptr;
     int64_t dbg_cap = 0;
 };
@@ -101,26 +104,8 @@ struct pfann_ctx {
 extern "C" int pfann_set_streams(pfann_ctx *c, int n);
 
 static int build_plan(pfann_ctx *c) {
-    const pfann_config &g = c->cfg;
-    const int ch[9] = {1, g.d, g.d, 2 * g.d, 2 * g.d, 4 * g.d, 4 * g.d, g.h, g.h};
-    int F = c->F, T = c->T;
-    for (int i = 0; i < 8; ++i) {
-        const int st = g.stride_t[i] > 0 ? g.stride_t[i] : 2;
-        const int sf = g.stride_f[i] > 0 ? g.stride_f[i] : 2;
-        const int p1 = (T - 1) / st * st + 3 - T, p2 = (F - 1) / sf * sf + 3 - F;
-        const int T1 = (T - 1) / st + 1, F2 = (F - 1) / sf + 1;
-        SubLayer &a = c->sub[2 * i], &b = c->sub[2 * i + 1];
-        a = SubLayer{};
-        b = SubLayer{};
-        a.ci = ch[i]; a.co = ch[i + 1]; a.F = F; a.T = T; a.Fo = F; a.To = T1;
-        a.axis = 0; a.stride = st; a.pad_lo = p1 / 2; a.depthwise = 0;
-        b.ci = ch[i + 1]; b.co = ch[i + 1]; b.F = F; b.T = T1; b.Fo = F2; b.To = T1;
-        b.axis = 1; b.stride = sf; b.pad_lo = p2 / 2; b.depthwise = g.fuller ? 0 : 1;
-        F = F2; T = T1;
-    }
-    if (F != 1 || T != 1) { set_error("encoder output must be 1x1, got %dx%d", F, T); return -1; }
-    if (g.h % g.d != 0) { set_error("h must be divisible by d"); return -1; }
-    if (g.d % 4 != 0) { set_error("d must be a multiple of 4"); return -1; }
+    const char *why = plan_sublayers(c->cfg, c->F, c->T, c->sub);       // csrc/encoder_plan.h
+    if (why) { set_error("%s", why); return -1; }
     return 0;
 }
 
@@ -183,12 +168,7 @@ pfann_ctx *pfann_create(const pfann_config *cfg, int device) {
         fprintf(stderr, "pfann_amd: this model's layer shapes (an Fo*To that is not a power of two, or channel counts not "
                         "multiples of 4) are outside the LayerNorm-fused GEMM path; using the separate-LayerNorm kernels\n");
     if (getenv("PFANN_STREAMS")) pfann_set_streams(c, atoi(getenv("PFANN_STREAMS")));
-    for (int i = 0; i < 16; ++i) {
-        const SubLayer &L = c->sub[i];
-        const int rps = L.Fo * L.To;
-        const int64_t slots = (int64_t)(rps >= 64 ? rps / 64 : 1) * cdiv(L.co, 64);
-        c->part_slots = std::max(c->part_slots, slots);
-    }
+    c->part_slots = plan_part_slots(c->sub);         // csrc/encoder_plan.h
     if (hipMalloc(&c->scratch, 16 * sizeof(double)) != hipSuccess) {
         set_error("hipMalloc failed");
         delete c;
@@ -360,13 +340,22 @@ int pfann_melspec_plan(pfann_ctx *c, int64_t B, int out[4]) {
     return 0;
 }
 
+// the kept samples of a chunk of B: up to 8 from keep_first, clamped to the chunk
+static int64_t keep_window(const pfann_ctx *c, int64_t B, int64_t *first) {
+    const int64_t nb = std::min<int64_t>(B, 8);
+    *first = std::max<int64_t>(0, std::min<int64_t>(c->keep_first, B - nb));
+    return nb;
+}
+
 static int keep_tap(pfann_ctx *c, int idx, const float *act, int64_t B, hipStream_t s) {
     const SubLayer &L = c->sub[idx];
     const int64_t e = (int64_t)L.co * L.Fo * L.To;
-    const int64_t nb = std::min<int64_t>(B, 8);
+    int64_t b0;
+    const int64_t nb = keep_window(c, B, &b0);
     if (!c->dbg[idx]) PF_HIP(hipMalloc(&c->dbg[idx], 8 * e * sizeof(float)));
-    PF_HIP(hipMemcpyAsync(c->dbg[idx], act, nb * e * sizeof(float), hipMemcpyDeviceToDevice, s));
+    PF_HIP(hipMemcpyAsync(c->dbg[idx], act + b0 * e, nb * e * sizeof(float), hipMemcpyDeviceToDevice, s));
     c->keep_B = nb;
+    c->dbg_has[idx] = true;
     return 0;
 }
 
@@ -396,10 +385,12 @@ static int ensure_workspace(pfann_ctx *c, bool need_mel) {
 static int keep_tap_fused(pfann_ctx *c, int idx, const float *z, const float *part, int P, int64_t B, hipStream_t s) {
     const SubLayer &L = c->sub[idx];
     const int64_t e = (int64_t)L.co * L.Fo * L.To;
-    const int64_t nb = std::min<int64_t>(B, 8);
+    int64_t b0;
+    const int64_t nb = keep_window(c, B, &b0);
     if (!c->dbg[idx]) PF_HIP(hipMalloc(&c->dbg[idx], 8 * e * sizeof(float)));
     c->keep_B = nb;
-    return launch_ln_apply(L, z, part, P, c->dbg[idx], nb, c->cfg.activation, c->cfg.relu_after_bn, s);
+    c->dbg_has[idx] = true;
+    return launch_ln_apply(L, z + b0 * e, part + b0 * P * 2, P, c->dbg[idx], nb, c->cfg.activation, c->cfg.relu_after_bn, s);
 }
 
 // Gram form of the first conv's LayerNorm statistics (see conv_first_gram_stats_kernel), in fp64
@@ -421,31 +412,18 @@ static void build_gram(pfann_ctx *c) {
     c->gram_ready = true;
 }
 
+// sk / sk_bytes: this chunk's slice of the split-K scratch, plan_chunk_scratch bytes of it (encode_chunk)
 static int encode_chunk_fused(pfann_ctx *c, const float *mel, int64_t B, float *emb, int normalize, hipStream_t s,
-                              int64_t slot0) {
+                              int64_t slot0, float *sk, size_t sk_bytes, int64_t Bcall) {
     const pfann_config &g = c->cfg;
     float *buf[2] = {c->buf[0] + slot0 * c->buf_elems[0], c->buf[1] + slot0 * c->buf_elems[1]};
     float *part[2] = {c->part[0] + slot0 * c->part_slots * 2, c->part[1] + slot0 * c->part_slots * 2};
     // Sub-layer 0 (C_in = 1 conv): normally only its LayerNorm statistics are computed here and the
     // conv itself is folded into sub-layer 1's A-loader; the 2 MiB/segment tensor is materialised
     // only when verification taps are requested.
-    const bool fold_first = !c->keep && c->sub[1].axis == 1 && c->sub[0].co <= 256 &&
-                            getenv("PFANN_NO_FOLD_FIRST") == nullptr;
-    const int64_t Bp = c->plan_batch > 0 ? c->plan_batch : B;
-    {   // split-K scratch: the largest [n_splits][B rows][N] partial tensor among the layers the plan splits at this batch
-        // (grow-only; one query: ~5 MB, 304 windows: ~30 MB; layers whose partials would pass 256 MB are not split)
-        size_t need = 0;
-        for (int i = 1; i < 16; ++i) {
-            const size_t n_i = splitk_scratch_need(c->sub[i], B, Bp);
-            if (n_i <= ((size_t)256 << 20)) need = std::max(need, n_i);
-        }
-        if (need > c->splitk_bytes) {
-            if (c->splitk) { PF_HIP(hipStreamSynchronize(s)); (void)hipFree(c->splitk); }
-            c->splitk = nullptr; c->splitk_bytes = 0;
-            if (hipMalloc(&c->splitk, need) == hipSuccess) c->splitk_bytes = need;
-            else { c->splitk = nullptr; (void)hipGetLastError(); }
-        }
-    }
+    const bool fold_first = plan_fold_first(c->sub, c->keep);         // csrc/encoder_plan.h
+    const int64_t Bp = c->plan_batch > 0 ? c->plan_batch : Bcall;     // the variants are those of the whole call
+    for (int i = 0; i < 16; ++i) c->dbg_has[i] = false;
     if (fold_first && g.relu_after_bn && (int)c->w1_host.size() == 3 * c->sub[0].co && (int)c->b1_host.size() == c->sub[0].co) {
         if (!c->gram_ready) build_gram(c);
         if (launch_conv_first_gram_stats(c->sub[0], mel, part[0], B, c->gram, s)) return -1;
@@ -453,7 +431,7 @@ static int encode_chunk_fused(pfann_ctx *c, const float *mel, int64_t B, float *
         return -1;
     }
     int P = fused_out_slots(c->sub[0], Bp);
-    if (c->keep && keep_tap_fused(c, 0, buf[0], part[0], P, B, s)) return -1;
+    if ((c->keep == 1 || (c->keep == 2 && !fold_first)) && keep_tap_fused(c, 0, buf[0], part[0], P, B, s)) return -1;
     int stats_final = 0;             // c->stats already holds (mean, rstd) of the next layer's input (split-K reduction)
     for (int i = 1; i < 16; ++i) {
         const bool first = fold_first && i == 1;
@@ -463,7 +441,7 @@ static int encode_chunk_fused(pfann_ctx *c, const float *mel, int64_t B, float *
                                   buf[i & 1], part[i & 1], B, g.activation, g.relu_after_bn, first ? &c->sub[0] : nullptr, s)) return -1;
         } else if (launch_conv_gemm_ln(c->sub[i], c->sub[i - 1], first ? mel : buf[(i - 1) & 1], part[(i - 1) & 1], P, c->stats + slot0 * 2, buf[i & 1],
                                 part[i & 1], B, g.activation, g.relu_after_bn, first ? &c->sub[0] : nullptr, c->precision, s,
-                                c->n_streams == 1 || B < 128 ? c->splitk : nullptr, c->splitk_bytes, &stats_final, Bp)) return -1;
+                                sk, sk_bytes, &stats_final, Bp, Bcall)) return -1;
         P = fused_out_slots(c->sub[i], Bp);
         if (c->keep && keep_tap_fused(c, i, buf[i & 1], part[i & 1], P, B, s)) return -1;
     }
@@ -472,8 +450,9 @@ static int encode_chunk_fused(pfann_ctx *c, const float *mel, int64_t B, float *
 }
 
 static int encode_chunk1(pfann_ctx *c, const float *mel, int64_t B, float *emb, int normalize, hipStream_t s,
-                         int64_t slot0) {
-    if (c->fused) return encode_chunk_fused(c, mel, B, emb, normalize, s, slot0);
+                         int64_t slot0, float *sk, size_t sk_bytes, int64_t Bcall) {
+    if (c->fused) return encode_chunk_fused(c, mel, B, emb, normalize, s, slot0, sk, sk_bytes, Bcall);
+    for (int i = 0; i < 16; ++i) c->dbg_has[i] = false;
     const float *x = mel;
     for (int i = 0; i < 16; ++i) {
         const SubLayer &L = c->sub[i];
@@ -481,7 +460,7 @@ static int encode_chunk1(pfann_ctx *c, const float *mel, int64_t B, float *emb, 
         int rc;
         if (L.ci == 1 && !L.depthwise) rc = launch_conv_first(L, x, y, B, s);
         else if (L.depthwise) rc = launch_conv_depthwise(L, x, y, B, s);
-        else rc = launch_conv_gemm(L, x, y, B, s);
+        else rc = launch_conv_gemm(L, x, y, B, s, Bcall);
         if (rc) return rc;
         if (launch_ln_act(L, y, B, c->cfg.activation, c->cfg.relu_after_bn, s)) return -1;
         if (c->keep && keep_tap(c, i, y, B, s)) return -1;
@@ -493,8 +472,24 @@ static int encode_chunk1(pfann_ctx *c, const float *mel, int64_t B, float *emb, 
 
 // Splits a chunk over the internal streams: fork after the caller's stream, join back into it.
 static int encode_chunk(pfann_ctx *c, const float *mel, int64_t B, float *emb, int normalize, hipStream_t s) {
-    const int ns = (int)std::min<int64_t>(c->n_streams, B / 128);
-    if (ns <= 1) return encode_chunk1(c, mel, B, emb, normalize, s, 0);
+    // The stream count never changes a kernel choice: every stream's chunk runs the kernel variants the whole call would run
+    // on one stream (split-K layers included) on its own slice of the scratch -- [n_splits][rows][N] partials of the chunk's
+    // largest split layer (one query: ~5 MB, 304 windows: ~30 MB; a layer whose partials would pass 256 MB is not split).
+    const std::vector<int64_t> chunks = plan_stream_chunks(B, c->n_streams);        // csrc/encoder_plan.h
+    const int ns = (int)chunks.size();
+    size_t sk_off[9] = {0};
+    for (int k = 0; k < ns; ++k) {
+        const size_t need = c->fused ? plan_chunk_scratch(c->sub, chunks[k], c->plan_batch > 0 ? c->plan_batch : B, c->keep, B) : 0;
+        sk_off[k + 1] = sk_off[k] + (need + 255) / 256 * 256;
+    }
+    if (sk_off[ns] > c->splitk_bytes) {          // grow-only
+        if (c->splitk) { PF_HIP(hipStreamSynchronize(s)); (void)hipFree(c->splitk); }
+        c->splitk = nullptr; c->splitk_bytes = 0;
+        PF_HIP(hipMalloc(&c->splitk, sk_off[ns]));
+        c->splitk_bytes = sk_off[ns];
+    }
+    auto slice = [&](int k) { return c->splitk ? c->splitk + sk_off[k] / sizeof(float) : nullptr; };
+    if (ns <= 1) return encode_chunk1(c, mel, B, emb, normalize, s, 0, slice(0), sk_off[1] - sk_off[0], B);
     if (!c->ev_fork) {
         PF_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         for (int k = 0; k < 8; ++k) {
@@ -506,9 +501,9 @@ static int encode_chunk(pfann_ctx *c, const float *mel, int64_t B, float *emb, i
     const int64_t per = (int64_t)c->F * c->T;
     int64_t b0 = 0;
     for (int k = 0; k < ns; ++k) {
-        const int64_t nb = B / ns + (k < B % ns ? 1 : 0);
+        const int64_t nb = chunks[k];
         PF_HIP(hipStreamWaitEvent(c->side[k], c->ev_fork, 0));
-        if (encode_chunk1(c, mel + b0 * per, nb, emb + b0 * c->cfg.d, normalize, c->side[k], b0)) return -1;
+        if (encode_chunk1(c, mel + b0 * per, nb, emb + b0 * c->cfg.d, normalize, c->side[k], b0, slice(k), sk_off[k + 1] - sk_off[k], B)) return -1;
         PF_HIP(hipEventRecord(c->ev_join[k], c->side[k]));
         PF_HIP(hipStreamWaitEvent(s, c->ev_join[k], 0));
         b0 += nb;
@@ -581,7 +576,14 @@ int pfann_pcm16_files_to_mono(pfann_ctx *c, const void *const *host_pcm, const i
     return launch_pcm16_to_mono(pcm_dev, total, 1, wav_dev, reinterpret_cast<float *>(c->scratch), (hipStream_t)stream);
 }
 
-void pfann_debug_keep(pfann_ctx *c, int on) { c->keep = on != 0; }
+void pfann_debug_keep(pfann_ctx *c, int on) { (void)pfann_debug_keep_at(c, on != 0 ? 1 : 0, 0); }
+
+int pfann_debug_keep_at(pfann_ctx *c, int mode, int64_t first_sample) {
+    if (mode < 0 || mode > 2 || first_sample < 0) { set_error("pfann_debug_keep_at: mode %d, first_sample %lld", mode, (long long)first_sample); return -1; }
+    c->keep = mode;
+    c->keep_first = first_sample;
+    return mode;
+}
 
 int pfann_prewarm(int device) {
     if (hipSetDevice(device) != hipSuccess) { set_error("pfann_prewarm: no HIP device %d", device); return -1; }
@@ -613,7 +615,13 @@ int pfann_set_fused_layernorm(pfann_ctx *c, int on) {
 }
 
 int64_t pfann_debug_activation(pfann_ctx *c, int idx, int64_t B, float *host, int64_t cap) {
-    if (idx < 0 || idx > 15 || !c->dbg[idx]) { set_error("no tap %d (call pfann_debug_keep(ctx,1) before encoding)", idx); return -1; }
+    if (idx < 0 || idx > 15 || !c->dbg[idx] || !c->dbg_has[idx]) {
+        if (idx == 0 && c->keep == 2 && c->fused)
+            set_error("tap 0 is absent in taps mode 2: this model's plan folds the first conv into sub-layer 1's loader and never "
+                      "materialises it (taps 1..15 are kept; mode 1 keeps tap 0)");
+        else set_error("no tap %d (call pfann_debug_keep(ctx,1) before encoding)", idx);
+        return -1;
+    }
     if (hipSetDevice(c->device) != hipSuccess) return -1;
     const SubLayer &L = c->sub[idx];
     const int64_t e = (int64_t)L.co * L.Fo * L.To;
@@ -1139,6 +1147,54 @@ int pfann_search_plan(int64_t n, int d, int64_t nq, int k, int storage, int phas
     sh.resume = phase == 2 && resume_with_lb != 0;
     sh.has_lb = phase == 2;
     return print_search_plan(plan_search(sh, search_tuning()), buf, len);
+}
+
+int pfann_encode_plan(const pfann_config *cfg, int64_t B, int64_t plan_batch, int precision, int fused, int taps, int n_streams,
+                      char *buf, int len) {
+    if (cfg == nullptr || B < 1 || precision < 0 || precision > 1 || taps < 0 || taps > 2 || n_streams < 1 || n_streams > 8 ||
+        (buf == nullptr && len > 0) || cfg->stft_hop <= 0) {
+        set_error("pfann_encode_plan: B=%lld precision=%d taps=%d streams=%d", (long long)B, precision, taps, n_streams);
+        return -1;
+    }
+    SubLayer sub[16];
+    const char *why = plan_sublayers(*cfg, cfg->n_mels, 1 + cfg->segment_len / cfg->stft_hop, sub);
+    if (why) { set_error("pfann_encode_plan: %s", why); return -1; }
+    // what pfann_create, pfann_set_fused_layernorm, pfann_set_encoder_precision and pfann_set_plan_batch make of the request
+    const bool can_fuse = plan_fused_supported(sub, 16) && getenv("PFANN_NO_FUSE") == nullptr;
+    const bool use_fused = fused < 0 ? can_fuse : (fused != 0 && plan_fused_supported(sub, 16));
+    if (!use_fused) precision = 0;
+    const int64_t pinned = plan_batch <= 0 ? 0 : (plan_batch < 65 ? 65 : plan_batch);
+    const int64_t max_batch = cfg->max_batch > 0 ? cfg->max_batch : 512;
+    if (B > max_batch) B = max_batch;           // the first chunk of a longer call
+    const int64_t part_slots = plan_part_slots(sub);
+    std::string out;
+    char line[320];
+    const std::vector<int64_t> chunks = plan_stream_chunks(B, n_streams);
+    size_t total = 0;
+    int64_t b0 = 0;
+    for (size_t k = 0; k < chunks.size(); ++k) {
+        const int64_t nb = chunks[k], Bp = pinned > 0 ? pinned : B;        // the variants are those of the whole call
+        const size_t need = use_fused ? plan_chunk_scratch(sub, nb, Bp, taps, B) : 0;
+        snprintf(line, sizeof line, "chunk %d b0=%lld B=%lld splitk_offset=%zu splitk_bytes=%zu\n", (int)k, (long long)b0, (long long)nb,
+                 total, need);
+        out += line;
+        std::vector<PlannedLaunch> ls;
+        plan_chunk_launches(*cfg, sub, nb, Bp, precision, use_fused, taps, ls, B);
+        for (const PlannedLaunch &l : ls) {
+            snprintf(line, sizeof line, "%s grid=%lld block=%d lds=%zu layer=%d tile=%d n_splits=%d first=%d out_P=%d\n", l.name.c_str(),
+                     (long long)l.grid, l.block, l.lds, l.layer, l.tile, l.n_splits, l.first, l.out_P);
+            out += line;
+        }
+        total += (need + 255) / 256 * 256;
+        b0 += nb;
+    }
+    snprintf(line, sizeof line, "flags fused=%d precision=%d plan_batch=%lld fold_first=%d chunks=%d splitk_bytes=%zu part_slots=%lld\n",
+             use_fused ? 1 : 0, precision, (long long)pinned, use_fused && plan_fold_first(sub, taps) ? 1 : 0, (int)chunks.size(), total,
+             (long long)part_slots);
+    out += line;
+    if ((int)out.size() + 1 > len) { set_error("pfann_encode_plan: the text needs %d bytes", (int)out.size() + 1); return -2; }
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return (int)out.size();
 }
 
 int pfann_search_plan_excl(int64_t n, int d, int64_t nq, int k, int storage, char *buf, int len) {

@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(GemmConvParams p) {
     }
 }
 
-int launch_conv_gemm(const SubLayer &L, const float *x, float *y, int64_t B, hipStream_t s) {
+int launch_conv_gemm(const SubLayer &L, const float *x, float *y, int64_t B, hipStream_t s, int64_t Bcall) {
     GemmConvParams p;
     p.x = x; p.w = L.w; p.bias = L.bias; p.y = y;
     p.rows_per_sample = L.Fo * L.To;
@@ -197,7 +197,7 @@ int launch_conv_gemm(const SubLayer &L, const float *x, float *y, int64_t B, hip
     const double flops = 2.0 * (double)p.M * p.N * (p.k_end - p.k_begin);
     // tile choice: big tiles when the grid still fills 256 CUs a few times over
     const int64_t blocks128 = (int64_t)cdiv(p.M, 128) * cdiv(p.N, 128);
-    if (p.N >= 128 && blocks128 >= 512) {
+    if (plain_gemm_tile(L, Bcall > 0 ? Bcall : B) == 128) {          // csrc/encoder_plan.h
         p.n_tiles_n = cdiv(p.N, 128);
         ProfScope ps("conv_gemm_128", s, flops);
         PF_LAUNCH((conv_gemm_kernel<128, 128, 64, 64>), dim3((unsigned)blocks128), dim3(256),
@@ -351,7 +351,7 @@ int launch_ln_act(const SubLayer &L, float *xy, int64_t B, int activation, int r
                   hipStream_t s) {
     const int n = L.co * L.Fo * L.To;
     ProfScope ps("ln_act", s, 4.0 * (double)B * n * 3.0);
-    if (n >= 65536)
+    if (ln_act_threads(L) == 1024)               // csrc/encoder_plan.h
         PF_LAUNCH((ln_act_kernel<1024>), dim3((unsigned)B), dim3(1024), 0, s, xy, L.ln_w, L.ln_b, n,
                            activation, relu_after_bn);
     else

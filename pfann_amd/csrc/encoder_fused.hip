@@ -1081,75 +1081,9 @@ __global__ __launch_bounds__(1024) void splitk_reduce_ln_kernel(const float *__r
     }
 }
 
-static void live_taps(const SubLayer &L, int in_len, int &k_begin, int &k_end) {
-    const int out_len = L.axis == 0 ? L.To : L.Fo;
-    int lo = 3, hi = -1;
-    for (int tap = 0; tap < 3; ++tap)
-        for (int o = 0; o < out_len; ++o) {
-            const int pos = o * L.stride - L.pad_lo + tap;
-            if (pos >= 0 && pos < in_len) { lo = tap < lo ? tap : lo; hi = tap > hi ? tap : hi; break; }
-        }
-    k_begin = lo * L.ci;
-    k_end = (hi + 1) * L.ci;
-}
+int fused_out_slots(const SubLayer &L, int64_t B) { return plan_out_slots(L, B); }
 
-// tile size used for sub-layer L at batch B (shared by the launcher and the partial-slot planner)
-static int gemm_tile(const SubLayer &L, int64_t B) {
-    const int64_t M = B * L.Fo * L.To;
-    const int64_t blocks128 = (int64_t)cdiv(M, 128) * cdiv(L.co, 128);
-    static const int64_t min128 = getenv("PFANN_TILE128_MIN") ? atoll(getenv("PFANN_TILE128_MIN")) : 512;
-    return (L.co >= 128 && blocks128 >= min128 && L.ci % 32 == 0) ? 128 : 64;
-}
-
-int fused_out_slots(const SubLayer &L, int64_t B) {
-    const int rps = L.Fo * L.To;
-    if (L.ci == 1 || L.depthwise) return rps / 64 > 0 ? rps / 64 : 1;       // conv_first_stats / conv_dw_ln: 64 rows per block
-    const int bt = gemm_tile(L, B);
-    return (rps >= bt ? rps / bt : 1) * cdiv(L.co, bt);
-}
-
-bool fused_supported(const SubLayer *sub, int n) {
-    for (int i = 0; i < n; ++i) {
-        const SubLayer &L = sub[i];
-        const int rps = L.Fo * L.To;
-        if (rps & (rps - 1)) return false;                  // power of two: tiles never straddle samples unevenly
-        if (L.depthwise) { if (L.co % 4 || L.axis != 1) return false; continue; }     // conv_dw_ln_kernel
-        if (L.ci == 1) { if (i != 0 || rps % 64 || L.co % 4) return false; }
-        else if (L.ci % 4 || L.co % 4) return false;
-    }
-    return true;
-}
-
-// Split-K plan of sub-layer L (64x64 tiles only): number of K chunks, 0 = not split.  The cut is chunks of 8 K-tiles whatever
-// the batch -- it depends on the layer only -- so a window's bits do not depend on how many windows share the launch;
-// WHETHER a layer is split depends on the batch the plan is made for:
-//   * plans of at most 64 windows (the one-query regime; pfann_set_plan_batch never pins one): launches of < 192 tiles;
-//   * larger plans (round 6: the middle of the batch curve, 65 .. ~1000 windows): the layers whose launch at the PLAN's
-//     batch is < 512 tiles of a chip that holds ~1000 -- the deep layers, M = B * (1 .. 8) rows with K loops of 48-96
-//     K-tiles: at 76 windows `rows=2 K=3072` was 48 workgroups x 96 K-tiles, 71 us on a sixth of the chip.
-// The same predicate sizes the scratch (splitk_scratch_need) and picks the kernel (launch_conv_gemm_ln).
-static int splitk_plan(const SubLayer &L, int64_t B, int64_t Bp, bool first, int k_live) {
-    static const int chunk_kt = getenv("PFANN_SPLITK_CHUNK") ? atoi(getenv("PFANN_SPLITK_CHUNK")) : 8;
-    static const bool no_splitk = getenv("PFANN_NO_SPLITK") != nullptr;
-    static const int64_t mid_max = getenv("PFANN_SPLITK_MID_BLOCKS") ? atoll(getenv("PFANN_SPLITK_MID_BLOCKS")) : 512;
-    if (no_splitk || first || chunk_kt <= 0 || L.ci % 32 != 0 || k_live % 32 != 0) return 0;
-    const int nk = k_live / 32;
-    const int n_splits = (nk + chunk_kt - 1) / chunk_kt;
-    if (nk < 16 || n_splits <= 1) return 0;
-    const int64_t rps = (int64_t)L.Fo * L.To, ntn = cdiv(L.co, 64);
-    const int64_t blocks = (int64_t)cdiv(B * rps, 64) * ntn, blocks_p = (int64_t)cdiv(Bp * rps, 64) * ntn;
-    const bool small = B <= 64 && Bp <= 64;
-    if (small ? blocks >= 192 : (B > Bp || blocks_p >= mid_max)) return 0;
-    return n_splits;
-}
-
-size_t splitk_scratch_need(const SubLayer &L, int64_t B, int64_t Bp) {
-    if (L.depthwise || L.ci == 1 || gemm_tile(L, Bp) != 64) return 0;
-    int kb, ke;
-    live_taps(L, L.axis == 0 ? L.T : L.F, kb, ke);
-    const int n_splits = splitk_plan(L, B, Bp, false, ke - kb);
-    return (size_t)n_splits * (size_t)B * L.Fo * L.To * L.co * sizeof(float);
-}
+bool fused_supported(const SubLayer *sub, int n) { return plan_fused_supported(sub, n); }
 
 // Lfirst != nullptr: x is the log-mel batch and Lfirst (= Lin, the C_in = 1 conv) is folded into the A-loader
 static int ilog2(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
@@ -1157,7 +1091,7 @@ static int ilog2(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
 int launch_conv_gemm_ln(const SubLayer &L, const SubLayer &Lin, const float *x, const float *in_part, int in_P,
                         float *in_stats, float *y, float *out_part, int64_t B, int act, int after_bn,
                         const SubLayer *Lfirst, int precision, hipStream_t s, float *splitk_scratch, size_t splitk_bytes,
-                        int *stats_final, int64_t Bplan) {
+                        int *stats_final, int64_t Bplan, int64_t Bcall) {
     const int64_t Bp = Bplan > 0 ? Bplan : B;      // the batch the kernel variant is chosen for (kernels.h)
     // stats_final (in/out, may be null): in: in_stats already holds (mean, rstd) of the input (written by the previous
     // layer's split-K reduction) -> no ln_finalize launch; out: whether this layer left its OUTPUT statistics there.
@@ -1176,11 +1110,13 @@ int launch_conv_gemm_ln(const SubLayer &L, const SubLayer &Lin, const float *x, 
     p.axis = L.axis; p.stride = L.stride; p.pad_lo = L.pad_lo;
     p.in_len = L.axis == 0 ? L.T : L.F;
     p.tap_stride = L.axis == 0 ? (int64_t)L.ci : (int64_t)L.T * L.ci;
-    live_taps(L, p.in_len, p.k_begin, p.k_end);
+    // every variant decision: csrc/encoder_plan.h (the same function pfann_encode_plan prints)
+    const ConvGemmPlan q = plan_conv_gemm_ln(L, B, Bp, Lfirst != nullptr, precision, act, after_bn, in_final, Bcall);
+    p.k_begin = q.k_begin; p.k_end = q.k_end;
     p.in_stats = in_stats;
     p.ln_w = Lin.ln_w; p.ln_b = Lin.ln_b;
     p.in_elems = (int64_t)L.F * L.T * L.ci;
-    p.out_part = out_part; p.out_P = fused_out_slots(L, Bp);
+    p.out_part = out_part; p.out_P = q.out_P;
     p.act = act; p.after_bn = after_bn;
     p.n_samples = (int)B;
     p.w1 = nullptr; p.b1 = nullptr; p.T0 = 0; p.s1 = 1; p.pad1 = 0;
@@ -1188,13 +1124,13 @@ int launch_conv_gemm_ln(const SubLayer &L, const SubLayer &Lin, const float *x, 
         p.w1 = Lfirst->w; p.b1 = Lfirst->bias;
         p.T0 = Lfirst->T; p.s1 = Lfirst->stride; p.pad1 = Lfirst->pad_lo;
     }
-    if (!in_final && !(PFANN_ABL & 8)) {        // (PFANN_ABL & 8: timing-only build without the ln_finalize launches)
+    if (q.finalize && !(PFANN_ABL & 8)) {       // (PFANN_ABL & 8: timing-only build without the ln_finalize launches)
         ProfScope ps("ln_finalize", s);
         PF_LAUNCH(ln_finalize_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, s, in_part, in_P, 1.0 / (double)p.in_elems,
                   in_stats, (int)B);
     }
     const double flops = 2.0 * (double)p.M * p.N * (p.k_end - p.k_begin);
-    const bool first = Lfirst != nullptr, relu_bn = act == 0 && after_bn, uni = L.ci % 32 == 0;
+    const bool first = q.first, relu_bn = q.relu_bn, uni = q.uni;
     // PFANN_PROF_LAYERS=1: one profiling tag per layer shape (tuning aid; bench.py's roofline wants the plain tags)
     static const bool per_layer = getenv("PFANN_PROF_LAYERS") != nullptr;
     auto layer_tag = [&](const char *base) -> const char * {
@@ -1212,18 +1148,14 @@ int launch_conv_gemm_ln(const SubLayer &L, const SubLayer &Lin, const float *x, 
         else if (relu_bn) PF_LAUNCH((conv_gemm_ln_kernel<BM, BN, WM, WN, true, false, UNI_>), g, t, 0, s, p);      \
         else PF_LAUNCH((conv_gemm_ln_kernel<BM, BN, WM, WN, false, false, UNI_>), g, t, 0, s, p);                  \
     } while (0)
-    if (gemm_tile(L, Bp) == 128) {
-        p.n_tiles_n = cdiv(p.N, 128);
+    const int64_t blocks = q.blocks;
+    if (q.tile == 128) {
+        p.n_tiles_n = q.n_tiles_n;
         p.dv_n = make_fastdiv(p.n_tiles_n); p.dv_tile = make_fastdiv(64 * p.n_tiles_n);
         p.dv_group = make_fastdiv(64 * (p.rows_per_sample >= 128 ? p.rows_per_sample / 128 : 1) * p.n_tiles_n);
-        const int64_t blocks = (int64_t)cdiv(p.M, 128) * p.n_tiles_n;
         // five channel blocks per output pair instead of six (conv_gemm_ln_w22_kernel) where the layer allows it
-        static const bool no_w22 = getenv("PFANN_NO_W22") != nullptr;
-        const int out_len = L.axis == 0 ? L.To : L.Fo;
-        if (!no_w22 && (!first || (L.axis == 1 && L.ci <= 256 && getenv("PFANN_NO_W22_FIRST") == nullptr)) && precision == 0 && L.w22 != nullptr && L.stride == 2 && L.pad_lo == 0 && p.k_begin == 0 &&
-            p.k_end == 3 * L.ci && out_len % 2 == 0 && p.in_len >= 2 * out_len && p.M % 2 == 0 &&
-            p.N % 128 == 0 && (L.axis == 0 || (L.To <= 64 && 128 % (2 * L.To) == 0)) &&
-            (int64_t)p.N * 4 * p.Ci * 4 < 0x7FFF0000ll) {
+        if (q.w22) {
+            if (L.w22 == nullptr) { set_error("conv_gemm_ln: the five-block weights of this layer are not loaded"); return -1; }
             p.w = L.w22;
             ProfScope ps(layer_tag(per_layer ? "conv_gemm_ln_128 w22" : "conv_gemm_ln_128"), s, flops);
             const dim3 g((unsigned)blocks), t(512);
@@ -1238,24 +1170,28 @@ int launch_conv_gemm_ln(const SubLayer &L, const SubLayer &Lin, const float *x, 
         // 8 waves (512 threads), each a 64x32 tile: half the prefetch registers per thread and four
         // waves per SIMD with two resident blocks
         constexpr bool UNI_ = true;
-        if (precision == 1 && relu_bn && L.w_hi != nullptr) {
+        if (q.split16) {
+            if (L.w_hi == nullptr) { set_error("conv_gemm_ln: the fp16 split weights of this layer are not loaded"); return -1; }
             const dim3 g((unsigned)blocks), t(512);
             if (first) PF_LAUNCH((conv_gemm_ln_kernel<128, 128, 64, 32, true, true, true, 32, true>), g, t, 0, s, p);
             else PF_LAUNCH((conv_gemm_ln_kernel<128, 128, 64, 32, true, false, true, 32, true>), g, t, 0, s, p);
         } else
         PF_GEMM_LN(128, 128, 64, 32, 512);
     } else {
-        p.n_tiles_n = cdiv(p.N, 64);
+        p.n_tiles_n = q.n_tiles_n;
         p.dv_n = make_fastdiv(p.n_tiles_n); p.dv_tile = make_fastdiv(64 * p.n_tiles_n);
         p.dv_group = make_fastdiv(64 * (p.rows_per_sample >= 64 ? p.rows_per_sample / 64 : 1) * p.n_tiles_n);
-        const int64_t blocks = (int64_t)cdiv(p.M, 64) * p.n_tiles_n;
-        // split-K for launches that cannot fill the chip and have a long K loop (splitk_plan above): chunks of 8 K-tiles
-        // (measured on one 19-segment query: 12 -> 344 us, 8 -> 323, 6 -> 323, 4 -> 331 for the whole embed)
-        static const int chunk_kt = getenv("PFANN_SPLITK_CHUNK") ? atoi(getenv("PFANN_SPLITK_CHUNK")) : 8;
-        const int n_splits = uni ? splitk_plan(L, B, Bp, first, p.k_end - p.k_begin) : 0;
-        if (n_splits > 1 && splitk_scratch != nullptr && (size_t)n_splits * p.M * p.N * sizeof(float) <= splitk_bytes) {
+        // split-K for launches that cannot fill the chip and have a long K loop (splitk_plan, encoder_plan.h)
+        const int n_splits = q.n_splits;
+        if (n_splits > 1) {
+            // the plan is the contract: running the unsplit kernel here instead would change the summation order, and with
+            // it the bits a pinned plan promises
+            if (splitk_scratch == nullptr || q.scratch > splitk_bytes) {
+                set_error("conv_gemm_ln: split-K scratch of %zu bytes needed, %zu given", q.scratch, splitk_scratch ? splitk_bytes : (size_t)0);
+                return -1;
+            }
             p.blocks_mn = (int)blocks;
-            p.k_chunk = chunk_kt * 32;
+            p.k_chunk = q.k_chunk;
             p.y = splitk_scratch;
             {
                 ProfScope ps(layer_tag("conv_gemm_ln_64"), s, flops);
@@ -1740,21 +1676,18 @@ int launch_myg_ln(const SubLayer &Llast, const float *z, const float *part, int 
     const int nt = ((d + 63) / 64) * 64;
     if (nt > 1024) { set_error("MyG: d = %d > 1024 unsupported", d); return -1; }
     ProfScope ps("myg_ln", s);
-    static const bool no_small = getenv("PFANN_NO_SMALL_HEAD") != nullptr;
-    const size_t small_lds = ((size_t)d * v + (size_t)d * u) * sizeof(float);
-    if (B <= 64 && (Bplan <= 0 || Bplan <= 64) && !no_small && small_lds <= 60 * 1024) {
-        int thr = d * u < 1024 ? ((d * u + 63) / 64) * 64 : 1024;
-        if (thr < nt) thr = nt;
-        PF_LAUNCH(myg_ln_small_kernel, dim3((unsigned)B), dim3(thr), small_lds, s, z, part, P, Llast.ln_w, Llast.ln_b, act, after_bn,
+    const HeadPlan h = plan_myg_ln(d, u, v, B, Bplan);       // csrc/encoder_plan.h
+    if (h.small) {
+        PF_LAUNCH(myg_ln_small_kernel, dim3((unsigned)h.grid), dim3(h.threads), h.lds, s, z, part, P, Llast.ln_w, Llast.ln_b, act, after_bn,
                   w1, b1, w2, b2, d, u, v, emb, normalize);
         PF_HIP(hipGetLastError());
         return 0;
     }
-    if (v <= 8)
-        PF_LAUNCH((myg_ln_kernel<4, 8>), dim3((unsigned)cdiv(B, 4)), dim3(nt), 0, s, z, part, P, Llast.ln_w, Llast.ln_b, act,
+    if (h.seg == 4)
+        PF_LAUNCH((myg_ln_kernel<4, 8>), dim3((unsigned)h.grid), dim3(nt), 0, s, z, part, P, Llast.ln_w, Llast.ln_b, act,
                   after_bn, w1, b1, w2, b2, d, u, v, emb, normalize, B);
     else
-        PF_LAUNCH((myg_ln_kernel<1, 32>), dim3((unsigned)B), dim3(nt), 0, s, z, part, P, Llast.ln_w, Llast.ln_b, act,
+        PF_LAUNCH((myg_ln_kernel<1, 32>), dim3((unsigned)h.grid), dim3(nt), 0, s, z, part, P, Llast.ln_w, Llast.ln_b, act,
                   after_bn, w1, b1, w2, b2, d, u, v, emb, normalize, B);
     PF_HIP(hipGetLastError());
     return 0;

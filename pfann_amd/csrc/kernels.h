@@ -1,6 +1,7 @@
 // Host-side launchers of the HIP kernels (one translation unit per stage).
 #pragma once
 #include "common.h"
+#include "encoder_plan.h"
 
 namespace pfann {
 
@@ -32,7 +33,7 @@ int launch_pcm16_to_mono(const int16_t *pcm, int64_t n_frames, int n_ch, float *
 
 // ---- encoder.hip ---------------------------------------------------------------------
 int launch_conv_first(const SubLayer &L, const float *x, float *y, int64_t B, hipStream_t s);
-int launch_conv_gemm(const SubLayer &L, const float *x, float *y, int64_t B, hipStream_t s);
+int launch_conv_gemm(const SubLayer &L, const float *x, float *y, int64_t B, hipStream_t s, int64_t Bcall = 0);
 int launch_conv_depthwise(const SubLayer &L, const float *x, float *y, int64_t B, hipStream_t s);
 int launch_ln_act(const SubLayer &L, float *xy, int64_t B, int activation, int relu_after_bn,
                   hipStream_t s);
@@ -43,8 +44,6 @@ int launch_cl_to_nchw(const float *x, float *y, int64_t B, int C, int HW, hipStr
 // ---- encoder_fused.hip (LayerNorm fused into the GEMM; "fuller" models) -------------------
 bool fused_supported(const SubLayer *sub, int n);
 int fused_out_slots(const SubLayer &L, int64_t B);
-// bytes of split-K scratch sub-layer L needs at batch B under the plan for batch Bp (0: the layer is not split)
-size_t splitk_scratch_need(const SubLayer &L, int64_t B, int64_t Bp);
 int launch_conv_first_stats(const SubLayer &L, const float *x, float *y, float *part, int64_t B, int act,
                             int after_bn, hipStream_t s);
 int launch_conv_first_gram_stats(const SubLayer &L, const float *x, float *part, int64_t B, const float *gram14,
@@ -53,7 +52,11 @@ int launch_conv_first_gram_stats(const SubLayer &L, const float *x, float *part,
 int launch_conv_gemm_ln(const SubLayer &L, const SubLayer &Lin, const float *x, const float *in_part, int in_P,
                         float *in_stats, float *y, float *out_part, int64_t B, int act, int after_bn,
                         const SubLayer *Lfirst, int precision, hipStream_t s, float *splitk_scratch = nullptr,
-                        size_t splitk_bytes = 0, int *stats_final = nullptr, int64_t Bplan = 0);
+                        size_t splitk_bytes = 0, int *stats_final = nullptr, int64_t Bplan = 0, int64_t Bcall = 0);
+// Bcall: the samples of the whole call when this launch is one internal stream's share of it (0: B); the variant is chosen for
+// the call, so the stream count never changes a kernel choice.
+// Every variant decision of the launchers above and below is made by csrc/encoder_plan.h (plan_conv_gemm_ln, plan_myg_ln,
+// plan_out_slots); splitk_scratch must hold what plan_chunk_scratch states for the chunk.
 int launch_conv_dw_ln(const SubLayer &L, const SubLayer &Lin, const float *x, const float *in_part, int in_P, float *in_stats,
                       float *y, float *out_part, int64_t B, int act, int after_bn, const SubLayer *Lfirst, hipStream_t s);
 int launch_ln_apply(const SubLayer &L, const float *z, const float *part, int P, float *out, int64_t B, int act,

@@ -47,6 +47,35 @@ def mel_filterbank(sample_rate, n_fft, n_mels, f_min, f_max, naf_mode=False):
     return fb.to(torch.float32).contiguous()
 
 
+def encode_plan(cfg, B, plan_batch=0, precision=0, fused=-1, taps=0, streams=1):
+    """pfann_encode_plan parsed (no GPU needed).  cfg: a lib.Config (config_from_params).  -> (launches, flags): launches is
+    a list of dicts {chunk, name, grid, block, lds, layer, tile, n_splits, first, out_P}, one per kernel launch in launch
+    order; flags holds the last line's fields as ints plus "chunk_info": [{b0, B, splitk_offset, splitk_bytes}, ...]."""
+    lib = _l.load()
+    size = 1 << 16
+    while True:
+        buf = ctypes.create_string_buffer(size)
+        rc = lib.pfann_encode_plan(ctypes.byref(cfg), int(B), int(plan_batch), int(precision), int(fused), int(taps), int(streams),
+                                   buf, len(buf))
+        if rc != -2 or size >= 1 << 24:          # -2: the text did not fit (8 streams with taps pass 64 KiB)
+            break
+        size *= 4
+    _l.check(rc, "pfann_encode_plan")
+    lines = buf.value.decode().splitlines()
+    assert lines[-1].startswith("flags "), lines[-1]
+    launches, chunk_info = [], []
+    for ln in lines[:-1]:
+        if ln.startswith("chunk "):
+            chunk_info.append({k: int(v) for k, v in (kv.split("=") for kv in ln.split(" ")[2:])})
+            continue
+        name, rest = ln.rsplit(" grid=", 1)
+        d = {k: int(v) for k, v in (kv.split("=") for kv in ("grid=" + rest).split(" "))}
+        launches.append(dict(d, name=name, chunk=len(chunk_info) - 1))
+    flags = {k: int(v) for k, v in (kv.split("=") for kv in lines[-1].split(" ")[1:])}
+    flags["chunk_info"] = chunk_info
+    return launches, flags
+
+
 class Engine:
     def __init__(self, params, device=0, max_batch=512, encoder_only=False):
         """encoder_only: the context serves `encode` alone (FpNetwork built without a full config, model.py:132-146
@@ -244,6 +273,19 @@ class Engine:
     # ---- verification taps -----------------------------------------------------------
     def debug_keep(self, on=True):
         self.lib.pfann_debug_keep(self.handle, 1 if on else 0)
+
+    def debug_keep_at(self, mode, first_sample=0):
+        """Taps mode 0 (off), 1 (all 16 taps, first conv materialised) or 2 (taps 1..15 beside the production plan), for the
+        8 consecutive samples of a chunk from first_sample, clamped to the chunk (include/pfann_amd.h)."""
+        return int(_l.check(self.lib.pfann_debug_keep_at(self.handle, int(mode), int(first_sample)), "pfann_debug_keep_at"))
+
+    def set_streams(self, n=1):
+        """Internal streams (1..8) a call is split over; changes no kernel choice (include/pfann_amd.h).  -> n in effect."""
+        return int(self.lib.pfann_set_streams(self.handle, int(n)))
+
+    def encode_plan(self, B, plan_batch=0, precision=0, fused=-1, taps=0, streams=1):
+        """The launches of a pfann_encode call of B samples on this model: encode_plan() below with this engine's config."""
+        return encode_plan(self.cfg, B, plan_batch, precision, fused, taps, streams)
 
     def debug_activation(self, idx, B):
         from .synth import layer_plan

@@ -57,6 +57,8 @@ SYMBOLS = {
                                        c_void_p, c_void_p, c_void_p]),
     "pfann_debug_activation": (c_int64, [c_void_p, c_int, c_int64, c_void_p, c_int64]),
     "pfann_debug_keep": (None, [c_void_p, c_int]),
+    "pfann_debug_keep_at": (c_int, [c_void_p, c_int, c_int64]),
+    "pfann_encode_plan": (c_int, [POINTER(Config), c_int64, c_int64, c_int, c_int, c_int, c_int, c_char_p, c_int]),
     "pfann_set_fused_layernorm": (c_int, [c_void_p, c_int]),
     "pfann_set_encoder_precision": (c_int, [c_void_p, c_int]),
     "pfann_prewarm": (c_int, [c_int]),

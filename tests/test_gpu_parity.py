@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import make_golden as mg
+from encoder_tap_cases import signature as plan_signature
 from pfann_amd import synth
 from score_bits import assert_canonical_topk, rescoring_path
 
@@ -165,6 +166,10 @@ def test_encoder_vs_reference_golden(torch_cuda, name, fused):
         pytest.skip("fused LayerNorm path not available for this model (reported by pfann_set_fused_layernorm)")
     eng.debug_keep(True)
     x = mg.encoder_inputs(F, T)
+    # the path the docstring names is the path that runs; with taps (mode 1) the fused path materialises the first conv
+    launches, flags = eng.encode_plan(x.shape[0], fused=fused, taps=1)
+    assert flags["fused"] == fused and flags["fold_first"] == 0
+    assert ("ln_act_kernel<256>" in [l["name"] for l in launches]) == (not fused)
     xt = torch_cuda.as_tensor(x).cuda()
     emb = eng.encode(xt, norm=True).cpu().numpy()
     taps_ref = []
@@ -184,6 +189,7 @@ def test_encoder_vs_reference_golden(torch_cuda, name, fused):
     # without verification taps the fused path folds the first conv into the second one's loader
     # (the 2 MiB/segment tensor is never written; LayerNorm statistics from the Gram form)
     eng.debug_keep(False)
+    assert eng.encode_plan(x.shape[0], fused=fused)[1]["fold_first"] == fused
     emb2 = eng.encode(xt, norm=True).cpu().numpy()
     assert np.abs(emb2 - emb).max() < 2e-6
     assert np.abs(emb2 - z["emb"]).max() < 1e-4
@@ -227,8 +233,10 @@ def test_encoder_large_mean_activations(torch_cuda, fused):
 
 
 def test_encoder_large_batch_128_tiles_vs_oracle(torch_cuda):
-    """A batch large enough for the 128x128 GEMM tiles (the golden tests run 3 segments, i.e. the 64x64 tiles):
-    embeddings against the CPU oracle for a batch that is not a multiple of anything convenient."""
+    """A batch that is not a multiple of anything convenient, against the CPU oracle.  What runs at 37 segments
+    (pfann_encode_plan): sub-layer 1, with the first conv folded in, on the 128-tile five-block kernel -- the ONLY 128-row
+    tiles of this batch -- sub-layers 2..5 on 64x64 tiles, 6..15 split along K, and the small-batch head.  The plain
+    128x128 kernel and the other 128-tile layers are covered by tests/test_gpu_encoder_taps.py."""
     from oracle import encoder as oe
     from pfann_amd.engine import Engine
     params = cfg("default")
@@ -239,6 +247,7 @@ def test_encoder_large_batch_128_tiles_vs_oracle(torch_cuda):
     ref = oe.encode(x, sd, params, norm=True)
     eng = Engine(params, 0, max_batch=64)
     eng.load_state_dict(sd)
+    assert plan_signature(eng.encode_plan(B)[0]) == "gW*sssskkkkkkkkkkS"
     e1 = eng.encode(torch_cuda.as_tensor(x).cuda(), norm=True).cpu().numpy()
     print("128-tile kernels vs oracle %.3e" % np.abs(e1 - ref).max())
     assert np.abs(e1 - ref).max() < 1e-4
@@ -246,7 +255,8 @@ def test_encoder_large_batch_128_tiles_vs_oracle(torch_cuda):
 
 @pytest.mark.parametrize("variant", ["default", "elu_pre_ln"])
 def test_encoder_five_block_kernel_vs_oracle(torch_cuda, variant):
-    """A batch large enough (130 segments) for the stride-2 layers with 1024 / 512 / 256 rows per sample to run on
+    """A batch large enough (130 segments) for the stride-2 layers with 2048 / 1024 / 512 / 256 rows per sample
+    (sub-layers 1..4; asserted from pfann_encode_plan) to run on
     conv_gemm_ln_w22_kernel (five channel blocks per output pair instead of six: conv along T and along F, N = 128 and
     256, a last tile with rows >= M): every sub-layer activation and the embeddings against the CPU oracle.  "elu_pre_ln":
     the same model with ELU applied BEFORE LayerNorm (model.py:58-72 with relu_after_bn=False), i.e. the kernel's generic
@@ -267,6 +277,11 @@ def test_encoder_five_block_kernel_vs_oracle(torch_cuda, variant):
     eng = Engine(params, 0, max_batch=160)
     eng.load_state_dict(sd)
     eng.debug_keep(True)
+    # with taps (mode 1) the first conv is materialised; without, it is folded into sub-layer 1's five-block kernel
+    assert plan_signature(eng.encode_plan(B, taps=1)[0]) == "cWWWWsskkkkkkkkk4"
+    assert plan_signature(eng.encode_plan(B)[0]) == ("gW*WWWsskkkkkkkkk4" if variant == "default" else "cW*WWWsskkkkkkkkk4")
+    names = [l["name"] for l in eng.encode_plan(B)[0]]
+    assert ("conv_gemm_ln_w22_kernel<false, true>" in names and "conv_gemm_ln_w22_kernel<false, false>" in names) == (variant == "elu_pre_ln")
     e1 = eng.encode(torch_cuda.as_tensor(x).cuda(), norm=True).cpu().numpy()
     worst = 0.0
     for i, tr in enumerate(taps_ref):
@@ -300,6 +315,10 @@ def test_encoder_mid_batch_plan_vs_oracle(torch_cuda):
     ref = np.concatenate([oe.encode(x[i:i + 76], sd, params, norm=True) for i in range(0, B, 76)])
     eng = Engine(params, 0, max_batch=B)
     eng.load_state_dict(sd)
+    # five-block 128-tile kernel on sub-layers 1..5, 64x64 tiles on 6..8, split-K on 9..15 -- alone and pinned, at 304 and 76
+    for b, pb in ((B, 0), (B, B), (76, B)):
+        assert plan_signature(eng.encode_plan(b, pb)[0]) == "gW*WWWWssskkkkkkk4"
+    assert plan_signature(eng.encode_plan(76)[0]) == "gW*Wssskkkkkkkkkk4"
     xt = torch_cuda.as_tensor(x).cuda()
     e1 = eng.encode(xt, norm=True).cpu().numpy()
     print("mid-batch plan (304 windows) vs oracle %.3e" % np.abs(e1 - ref).max())
@@ -311,7 +330,7 @@ def test_encoder_mid_batch_plan_vs_oracle(torch_cuda):
     assert np.array_equal(e_all, e1)
     assert np.array_equal(e_head, e_all[:76]), "a window's bits depend on the batch under a pinned plan"
     eng.set_plan_batch(0)
-    e76 = eng.encode(xt[:76].contiguous(), norm=True).cpu().numpy()          # its own plan (64x64 tiles everywhere)
+    e76 = eng.encode(xt[:76].contiguous(), norm=True).cpu().numpy()          # its own plan (128 tiles on sub-layers 1, 2 only)
     assert np.abs(e76 - ref[:76]).max() < 1e-4
 
 
@@ -329,6 +348,9 @@ def test_encoder_split_precision_matches_fp32(torch_cuda):
     eng = Engine(params, 0, max_batch=512)
     eng.load_state_dict(sd)
     B = 512
+    # the split instantiation on the 128-tile layers (1..6), where precision 0 runs the five-block kernel
+    assert plan_signature(eng.encode_plan(B, precision=1)[0]) == "gH*HHHHHsssskskkk4"
+    assert plan_signature(eng.encode_plan(B)[0]) == "gW*WWWWWsssskskkk4"
     x = (synth.normal(77, "t/split", B * F * T).reshape(B, F, T) * 3.0 - 6.0).astype(np.float32)
     xt = torch_cuda.as_tensor(x).cuda()
     assert eng.set_encoder_precision(0) == 0
