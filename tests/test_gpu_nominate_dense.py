@@ -12,6 +12,7 @@ import pytest
 import dense_cases as dc
 import dense_topn_cases as dt
 import match_exact as mx
+from fp16_margin_cases import margin_ref as _margin      # E_j as the select kernel forms it: fp32 eps_t and norms, the rest in double
 
 pytestmark = pytest.mark.gpu
 D = 128
@@ -143,15 +144,6 @@ def noisy_world(tmp_path_factory):
         rows.append(x / np.linalg.norm(x, axis=1, keepdims=True))
         qlen.append(n)
     return d, emb, pos, np.concatenate(rows).astype(np.float32), _starts(qlen), qlen, 9
-
-
-def _margin(q_rows, d, xmax):
-    """E_j as the select kernel forms it: the fp32 eps_t and norms, the rest in double"""
-    x = np.float32(xmax)
-    nrm = np.sqrt((q_rows.astype(np.float32) ** 2).sum(1, dtype=np.float32)).astype(np.float32)
-    eps = np.float32(1.05e-3) * nrm * x + np.float32(3.1e-8) * np.sqrt(np.float32(d)) * (nrm + x)
-    n = q_rows.shape[0]
-    return float(eps.astype(np.float64).sum() + 2.0 ** -22 * (d + n) * float(x) * float(nrm.astype(np.float64).sum()))
 
 
 def test_bound_and_certificate(torch_cuda, noisy_world):
