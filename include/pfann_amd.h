@@ -705,6 +705,41 @@ int pfann_nominate_songs_dense(pfann_db *db, const float *q_dev,
                                int32_t *n_found_dev /* [nQ] or NULL */, int32_t *n_close_dev /* [nQ] or NULL */,
                                void *stream);
 
+/* Windowed dense nomination (csrc/nominate_windows.hip): pfann_nominate_songs_dense for every window of long recordings -- monitor
+ * mode's form of it.  Recordings, windows, wfirst_dev, n_windows, short recordings (one window of rlen rows) and empty recordings
+ * follow pfann_match_windows_dense.  Window w of recording r is the query of rows [rstart[r] + w * hop, .. + wl),
+ * wl = min(window, rlen[r]); its outputs are row wfirst[r] + w of cand_dev[n_windows][n], n_found_dev and n_close_dev.
+ *   excl_song_dev NULL   a window's cand row, n_found and n_close are byte for byte what pfann_nominate_songs_dense writes for that
+ *                 query: tot16, A, eps_t, E (summed in ascending t, in double) and the ranking keep their definitions and their
+ *                 summation order;
+ *   excl_song_dev[r] = s   the candidates of song s are no candidates of the windows of recording r (-1: none): s is not ranked
+ *                 and not counted in n_found or n_close.  n_close <= n then proves that the best song of
+ *                 pfann_match_windows_dense_topn called WITH THE SAME EXCLUSION is listed;
+ *   a row with norm >= 6e4 or a NaN   every window that contains it is all padding, n_found = -1, n_close = -1; the windows that do
+ *                 not contain it are unaffected;
+ *   prefix        the entries for n = a are the first a entries for n = b > a.
+ * Disjoint queries packed into tiles compute every row dot once per window; here a tile is 128 consecutive recording rows
+ * against 128 database rows with a halo of window-1 rows both ways, as in csrc/dense.hip, and the 128 - (window-1) window starts
+ * it owns share its row dots: at window 19, hop 2 that is 55 windows per tile product instead of 6.  A prep kernel writes ONE
+ * fp16 image of the call's rows with their eps_t, norms and flags; the tile kernel leaves each song's best total per (window,
+ * tile) with one 32-bit atomicMax in a workspace [windows of a chunk][n_songs] (4 bytes per pair, zeroed per chunk, at most
+ * 256 MB unless one row-tile slot of windows needs more); a select kernel, one workgroup per window, ranks, counts n_close and
+ * writes.  Longer calls walk chunks of whole row-tile slots; PFANN_NOMINATE_WINDOWS=<windows> in the environment (read at every
+ * call) lowers the windows per chunk, rounded up to whole slots.
+ * BYTE CONTRACT: a window's cand row, n_found and n_close are a function of its rows, the database and its recording's excluded
+ * song alone: not of hop, the window's position, its neighbours, the other recordings, the chunking, the launch shape or the run.
+ * Asynchronous on `stream`, no read-back; the only wait is growing the handle's scratch on demand (which drains the stream once).
+ * Returns -1 with a message, launches nothing and writes nothing -- the first that applies is reported --: first
+ * pfann_nominate_songs_dense's refusals in its order (a shard, fp16-only storage, no fp16 copy of the rows, n outside 1..64),
+ * then window outside 1..64, hop < 1, nR < 0 or n_windows < 0, a null cand_dev. */
+int pfann_nominate_windows_dense(pfann_db *db, const float *q_dev,
+                                 const int64_t *rstart_dev, const int32_t *rlen_dev, int64_t nR,
+                                 int window, int hop, const int64_t *wfirst_dev, int64_t n_windows,
+                                 const int32_t *excl_song_dev /* [nR] or NULL */, int n,
+                                 pfann_match_result *cand_dev /* [n_windows][n] */,
+                                 int32_t *n_found_dev /* [n_windows] or NULL */,
+                                 int32_t *n_close_dev /* [n_windows] or NULL */, void *stream);
+
 /* Song-sharded dense matcher (csrc/dense.hip): the three calls above refuse a handle that holds a shard; these four split them
  * into a PART per handle and a MERGE, so that N handles that cut the song list into contiguous ranges -- N GPUs, each with 1/N
  * of the rows -- give, byte for byte, what one handle of the whole database gives.

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libpfann_amd.so")
-SOURCES = ["api.hip", "mel.hip", "encoder.hip", "encoder_fused.hip", "search.hip", "search_f16.hip", "rerank.hip", "monitor.hip", "dense.hip", "dense_songs.hip", "nominate.hip", "dbstore.hip", "wavio.hip"]
+SOURCES = ["api.hip", "mel.hip", "encoder.hip", "encoder_fused.hip", "search.hip", "search_f16.hip", "rerank.hip", "monitor.hip", "dense.hip", "dense_songs.hip", "nominate.hip", "nominate_windows.hip", "dbstore.hip", "wavio.hip"]
 HEADERS = [os.path.abspath(__file__), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "search_common.h"), os.path.join(CSRC, "search_plan.h"), os.path.join(CSRC, "encoder_plan.h"), os.path.join(CSRC, "match_common.h"),
            os.path.join(HERE, "..", "include", "pfann_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"] + os.environ.get("PFANN_HIPCC_FLAGS", "").split()

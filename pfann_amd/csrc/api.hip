@@ -1600,6 +1600,57 @@ int pfann_nominate_songs_dense(pfann_db *db, const float *q, const int64_t *qsta
     return 0;
 }
 
+// the nomination for every window of long recordings (nominate_windows.hip).  The scratch is the handle's dense_ws: the call's
+// fp16 row image with its bounds, norms and flags, then the ws of one chunk.  Chunks of whole row-tile slots as in
+// dense_ranked_call: 4 bytes per (window the chunk's slots can hold, song), at most 256 MB unless one slot alone needs more;
+// PFANN_NOMINATE_WINDOWS (read per call) lowers the windows per chunk
+int pfann_nominate_windows_dense(pfann_db *db, const float *q, const int64_t *rstart, const int32_t *rlen, int64_t nR, int window,
+                                 int hop, const int64_t *wfirst, int64_t n_windows, const int32_t *excl_song, int n,
+                                 pfann_match_result *cand, int32_t *n_found, int32_t *n_close, void *stream) {
+    const char *what = "nominate_windows_dense";
+    PF_HIP(hipSetDevice(db->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!db_is_whole(db)) return refuse_shard();
+    if (db->storage != PFANN_DB_F32 || (db->n > 0 && db->emb == nullptr)) {
+        set_error("%s: fp16-only storage (the dense matcher scores fp32 rows)", what);
+        return -1;
+    }
+    if (db->n > 0 && db->emb_h == nullptr) {
+        set_error("%s: the handle keeps no fp16 copy of its rows (d %% 8 != 0, PFANN_NO_F16_PREFILTER at load, or row norms >= 1e4; d=%d)",
+                  what, db->d);
+        return -1;
+    }
+    if (n < 1 || n > 64) { set_error("%s: n=%d outside 1..64", what, n); return -1; }
+    if (window < 1 || window > 64) { set_error("%s: window=%d outside 1..64", what, window); return -1; }
+    if (hop < 1) { set_error("%s: hop=%d", what, hop); return -1; }
+    if (nR < 0 || n_windows < 0) { set_error("%s: nR=%lld n_windows=%lld", what, (long long)nR, (long long)n_windows); return -1; }
+    if (cand == nullptr) { set_error("%s: cand_dev is null", what); return -1; }
+    if (nR == 0 || n_windows == 0) return 0;
+    NominateWindowsArgs a = {};
+    a.dbh = db->emb_h; a.ntotal = db->n; a.d = db->d; a.xnorm_max = db->xnorm_max; a.song_pos = db->song_pos; a.n_songs = db->n_songs;
+    a.q = q; a.rstart = rstart; a.rlen = rlen; a.nR = nR; a.window = window; a.hop = hop; a.wfirst = wfirst; a.nW = n_windows;
+    a.excl = excl_song;
+    a.n = n; a.cand = cand; a.n_found = n_found; a.n_close = n_close;
+    a.n_rows = nominate_windows_rows(n_windows, nR, window, hop);
+    a.wps = dense_topn_wps(window, hop);
+    const int64_t n_slots = dense_topn_slots(n_windows, nR, window, hop);
+    const int64_t songs = std::max(a.n_songs, 1);
+    int64_t cap = (256ll << 20) / (4 * songs);
+    const char *env = getenv("PFANN_NOMINATE_WINDOWS");
+    if (env != nullptr && env[0] != 0 && atoll(env) > 0) cap = std::min<int64_t>(cap, atoll(env));
+    const int64_t step = std::min(n_slots, std::max<int64_t>(1, cap / a.wps));
+    const size_t need = nominate_windows_image_bytes(a.n_rows, a.d) + (size_t)step * a.wps * songs * 4;
+    // (growing drains the stream, the one exception to the asynchrony: earlier calls may still read the scratch)
+    if (grow_scratch(&db->dense_ws, &db->dense_ws_bytes, need, st, true)) return -1;
+    nominate_windows_scratch_layout(a, db->dense_ws);
+    if (launch_nominate_windows_prep(a, st)) return -1;
+    for (int64_t s0 = 0; s0 < n_slots; s0 += step) {
+        a.slot_lo = s0; a.slot_n = std::min(step, n_slots - s0);
+        if (launch_nominate_windows_dense(a, st)) return -1;
+    }
+    return 0;
+}
+
 int pfann_match_windows_dense_merge(pfann_db *db, const uint64_t *words, const pfann_dense_stats *part_stats, int n_parts,
                                     const int32_t *rlen, int64_t nR, int window, const int64_t *wfirst, int64_t n_windows,
                                     const int32_t *excl_song, pfann_match_result *results, pfann_dense_stats *stats, void *stream) {

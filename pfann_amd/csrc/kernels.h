@@ -259,6 +259,40 @@ size_t nominate_scratch_bytes(int64_t q_n, int n_songs, int max_qlen, int d);
 void nominate_scratch_layout(NominateArgs &a, void *base);  // needs q_n, n_songs, max_qlen, d
 int launch_nominate_songs_dense(const NominateArgs &a, hipStream_t s);
 
+// ---- nominate_windows.hip: the nomination for every window of long recordings, over tiles the windows share
+// (pfann_nominate_windows_dense) ----------------
+// Its own argument type, like NominateArgs.
+struct NominateWindowsArgs {
+    const void *dbh; int64_t ntotal; int d;     // fp16 copy of the rows of the WHOLE database
+    float xnorm_max;
+    const int64_t *song_pos; int n_songs;
+    const float *q;
+    const int64_t *rstart; const int32_t *rlen; int64_t nR;
+    int window, hop;                            // window 1..64
+    const int64_t *wfirst;                      // [nR + 1]
+    int64_t nW;                                 // wfirst[nR], from the caller
+    const int32_t *excl;                        // [nR] song whose alignments are no candidates (-1: none), or null
+    // ---- once per call (nominate_windows_scratch_layout): row i of recording r is row
+    // (wfirst[r] * hop / SI + r) * SI + r * (window-1) + i, SI = 128 - (window-1).  Recording r owns
+    // wfirst[r+1] * hop / SI - wfirst[r] * hop / SI + 1 slots, more than nw * hop / SI, so its SI rows per slot and its halo
+    // hold the (nw-1) * hop + min(window, rlen[r]) rows that its nw windows read
+    int64_t n_rows;                             // nominate_windows_rows(nW, nR, window, hop)
+    void *qh;                                   // [n_rows][d] fp16 rows
+    float *eps, *norm;                          // [n_rows] the bound and the norm of each row
+    int *bad;                                   // [n_rows] the row is outside fp16's range (its image is zeros)
+    // ---- one chunk of row-tile slots [slot_lo, slot_lo + slot_n) of the call
+    unsigned *ws;                               // [slot_n][wps][n_songs] ordered bits of every song's best approximate total, 0: none
+    int64_t slot_lo, slot_n;
+    int wps;                                    // window starts one slot can hold: dense_topn_wps(window, hop)
+    int n; pfann_match_result *cand;            // cand[nW][n]
+    int32_t *n_found, *n_close;                 // [nW] or null
+};
+int64_t nominate_windows_rows(int64_t nW, int64_t nR, int window, int hop);
+size_t nominate_windows_image_bytes(int64_t n_rows, int d);         // the rows' share of the scratch; the chunk's ws lies behind it
+void nominate_windows_scratch_layout(NominateWindowsArgs &a, void *base);   // needs n_rows, d; base 256-byte aligned
+int launch_nominate_windows_prep(const NominateWindowsArgs &a, hipStream_t s);   // once per call, before its first chunk
+int launch_nominate_windows_dense(const NominateWindowsArgs &a, hipStream_t s);  // one chunk: zeroes ws, tiles, select
+
 // ---- dbstore.hip: what an update of a loaded handle needs (pfann_db_append / pfann_db_remove_songs) ----------------
 struct DbRun { int64_t src, dst, len; };    // kept rows [src, src + len) go to [dst, dst + len), dst <= src
 // atomic maximum of the row norms (the per-row arithmetic of rows_to_half_kernel) into song_max[song - song_base]; row r of x

@@ -581,6 +581,27 @@ class DeviceIndex:
             return cand, n_found, n_close
         return self.topn_to_host(cand, n_found) + (n_close.cpu().numpy(),)
 
+    def nominate_windows_dense(self, q, rstart, rlen, window, hop, n, exclude_song=None, to_host=True):
+        """Windowed dense nomination (pfann_nominate_windows_dense): nominate_songs_dense for every window of nR recordings, over
+        tiles that neighbouring windows share.  Recordings, windows and exclude_song as in match_windows_dense.
+        -> ((cand [nW, n] of RESULT_DTYPE, n_found int32 [nW], n_close int32 [nW]), wfirst): row wfirst[r] + i is byte for byte
+        what nominate_songs_dense gives the query window_queries names for window i of recording r (without that recording's
+        excluded song); with to_host=False the three device tensors (uint8 [nW, n, 24], int32 [nW], int32 [nW])."""
+        what = "nominate_windows_dense"
+        self._window_hop(what, window, hop)
+        n = self._check_n(what, n)
+        window, hop, nR, nW, wfirst, rs, rl, wf, ex = self._dense_args(what, rstart, rlen, window, hop, exclude_song, q.shape[0])
+        q = q.to(self.device, torch.float32).contiguous()
+        cand = torch.empty((nW, n, ctypes.sizeof(_l.MatchResult)), device=self.device, dtype=torch.uint8)
+        n_found = torch.empty((nW,), device=self.device, dtype=torch.int32)
+        n_close = torch.empty((nW,), device=self.device, dtype=torch.int32)
+        if nW:
+            self._windows_lib_call(what, (q.data_ptr(), rs.data_ptr(), rl.data_ptr(), nR, window, hop, wf.data_ptr(), nW,
+                                          ex.data_ptr() if ex is not None else None), n, (cand, n_found, n_close))
+        if not to_host:
+            return (cand, n_found, n_close), wfirst
+        return self.topn_to_host(cand, n_found) + (n_close.cpu().numpy(),), wfirst
+
     # ---- the dense matcher over song-sharded handles: a part per handle, one merge (include/pfann_amd.h) ----------------
     def match_windows_dense_part(self, q, rstart, rlen, window, hop, exclude_song=None, stats=False):
         """This handle's part of match_windows_dense / _stats (pfann_match_windows_dense_part): the handle may hold a shard.
@@ -641,6 +662,17 @@ def window_counts(rlen, window, hop):
     one window over all rows when 0 < L < window; none when L == 0"""
     L = np.asarray(rlen, dtype=np.int64)
     return np.where(L <= 0, 0, np.where(L < window, 1, (L - window) // hop + 1)).astype(np.int64)
+
+
+def window_queries(rstart, rlen, window, hop):
+    """the windows of window_counts as queries -> (qstart int64 [nW], qlen int32 [nW], wfirst int64 [nR + 1]): window i of
+    recording r is query wfirst[r] + i, rows [rstart[r] + i * hop, .. + min(window, rlen[r])) of the rows the recordings lie in"""
+    rs, L = np.asarray(rstart, dtype=np.int64).reshape(-1), np.asarray(rlen, dtype=np.int64).reshape(-1)
+    counts = window_counts(L, window, hop)
+    wfirst = np.pad(np.cumsum(counts), (1, 0)).astype(np.int64)
+    rec = np.repeat(np.arange(L.shape[0], dtype=np.int64), counts)
+    qstart = rs[rec] + (np.arange(int(wfirst[-1]), dtype=np.int64) - wfirst[rec]) * int(hop)
+    return qstart.astype(np.int64), np.minimum(L[rec], int(window)).astype(np.int32), wfirst
 
 
 def self_match_ranges(song_pos, song_lo, song_hi):
@@ -1289,6 +1321,53 @@ class Database:
     def query_nominate_rescore_batch(self, emb, qstart, qlen, n):
         """emb: torch cuda [sum(qlen), d] rows -> (answers, ranked, certified), see query_nominate_rescore_finish"""
         return self.query_nominate_rescore_finish(self.query_nominate_rescore_launch(emb, qstart, qlen, n))
+
+    # ---- monitor mode through the nomination: dense-grade windows without the fp32 dense pass, a certificate per window ------
+    def monitor_nominate_launch(self, emb, rstart, rlen, window, hop, n, edge_window=0):
+        """monitor_dense_launch without the fp32 dense pass: the n songs of every window with the best approximate dense score on
+        the fp16 MFMA (pfann_nominate_windows_dense: the windows of a recording share their row dots), then every alignment of
+        those songs for the windows as queries (pfann_match_songs_dense on window_queries), then entry 0 of every window, on the
+        one stream; no search, nothing is read back.  edge_window > 0: the short windows at hop 1 take the same route.
+        PFANN_NOMINATE_WINDOWS_GENERAL=1 (read per launch) routes the nomination through pfann_nominate_songs_dense on the
+        expanded windows instead: the same bytes, for A/B timing.  Refuses where query_nominate_rescore_launch refuses.
+        -> what monitor_nominate_finish reads."""
+        self._whole_only("monitor_nominate_launch: rescoring is", "the nominated songs are scored on one GPU against the whole database")
+        self._dense_check("monitor_nominate_launch")
+        n = DeviceIndex._check_n("monitor_nominate_launch", n)
+        general = os.environ.get("PFANN_NOMINATE_WINDOWS_GENERAL", "") == "1"
+
+        def windows(w, h):
+            qstart, qlen, wfirst = window_queries(rstart, rlen, w, h)
+            if general:
+                cand, _, n_close = self.index.nominate_songs_dense(emb, qstart, qlen, n, to_host=False, max_qlen=min(int(w), 64))
+            else:
+                (cand, _, n_close), _ = self.index.nominate_windows_dense(emb, rstart, rlen, w, h, n, to_host=False)
+            top, _ = self.index.match_songs_dense(emb, qstart, qlen, cand, to_host=False)
+            return top[:, 0].contiguous(), wfirst, n_close
+
+        def match():
+            DeviceIndex._window_hop("monitor_nominate_launch", window, hop)
+            res, wfirst, n_close = windows(int(window), int(hop))
+            out = {"res": res, "wfirst": wfirst, "hop": int(hop), "n_close": n_close, "n": n, "fine": None}
+            if edge_window > 0:
+                edge, efirst, out["edge_n_close"] = windows(int(edge_window), 1)
+                out["fine"] = (edge, efirst)
+            return out
+        return self._launch(emb, match, mode=0, search=False)
+
+    def monitor_nominate_finish(self, p):
+        """Second half: -> (rows as monitor_finish gives them, per recording n_close int32 [windows], per recording certified bool
+        [windows]): certified = 0 <= n_close <= n, the proof that the window's row IS monitor_dense_launch's row.  The edge
+        pass is left in p["edge_rows"], p["edge_n_close"] and p["edge_certified"] in the same form."""
+        rows = self.monitor_finish(p)
+
+        def per_recording(n_close, wfirst):
+            n_close = n_close.cpu().numpy()
+            close = [n_close[a:b] for a, b in zip(wfirst[:-1], wfirst[1:])]
+            return close, [(c >= 0) & (c <= p["n"]) for c in close]
+        if p.get("fine") is not None:
+            p["edge_n_close"], p["edge_certified"] = per_recording(p["edge_n_close"], p["fine"][1])
+        return (rows,) + tuple(per_recording(p["n_close"], p["wfirst"]))
 
     def monitor_finish(self, p):
         """Second half: -> per recording a structured array (w0, score, song, time_s), one entry per window: its first

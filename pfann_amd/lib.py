@@ -114,6 +114,8 @@ SYMBOLS = {
     "pfann_match_songs_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "pfann_nominate_songs_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
+    "pfann_nominate_windows_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
+                                             c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pfann_db_owned_songs": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     "pfann_db_set_owned_songs": (c_int, [c_void_p, c_int, c_int]),
     "pfann_song_scores_to_seconds": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_int, c_void_p]),

@@ -1,5 +1,5 @@
 """Monitor mode: go through long recordings and say what played when.
-    python monitor.py <recording list> <database dir> <result file> [--window N] [--hop N] [--min-score X] [--max-gap N] [--min-windows N] [--edge-window N] [--top N] [--dense] [--max-fa X]
+    python monitor.py <recording list> <database dir> <result file> [--window N] [--hop N] [--min-score X] [--max-gap N] [--min-windows N] [--edge-window N] [--top N] [--dense] [--max-fa X] [--nominate N]
 
 Every recording is embedded once, all its rows are searched once, and the windowed sequence matcher
 (pfann_match_windows, csrc/monitor.hip) answers every window of `--window` segments, `--hop` segments apart, exactly as
@@ -36,6 +36,14 @@ pfann_amd/significance.py turns the best score into log10_fa, log10 of the chanc
 scores as high.  A window then counts when it names a song and log10_fa <= log10(X); `--min-score` is not consulted.  The
 windows file gets a seventh column, log10_fa, and the detections file a ninth, min_log10_fa: the most significant member
 window.  What score chance reaches depends on the window length, the size of the database and the model; X does not.
+
+`--dense --nominate N` (1 <= N <= 64) gives `--dense`'s answers without the fp32 dense pass: the fp16 MFMA names N songs per
+window over every alignment (pfann_nominate_windows_dense, csrc/nominate_windows.hip: the windows of a recording share their
+row dots), pfann_match_songs_dense scores those songs exactly, and the window's n_close <= N proves that its row is `--dense`'s
+row byte for byte (Database.monitor_nominate_launch / monitor_nominate_finish).  Both files keep `--dense`'s columns;
+`<result-stem>_nominate.csv` gets one row per long window, recording,w0,n_close,certified (an unreadable recording:
+recording,error,-1,0).  Not together with `--max-fa` (the background statistics come from the fp32 dense pass), `--top N` > 1 or
+several ranks.
 """
 import argparse
 import csv
@@ -219,6 +227,33 @@ def ranked_window_csv(name, ranked_rows, seg_step_s, song_names):
     return out
 
 
+NOMINATE_HEADER = ["recording", "w0", "n_close", "certified"]
+
+
+def nominate_csv(name, rows, n_close, certified):
+    """rows of `<stem>_nominate.csv` for one recording: NOMINATE_HEADER, one row per long window in the order of the windows
+    file; rows: the recording's (w0, ..) rows, n_close / certified: one value per row (Database.monitor_nominate_finish)"""
+    assert len(rows) == len(n_close) == len(certified), "one n_close and one certificate per window"
+    return [[name, int(row[0]), int(c), 1 if ok else 0] for row, c, ok in zip(rows, n_close, certified)]
+
+
+def check_nominate(args, several=False):
+    """-> the message that refuses this use of --nominate, or None"""
+    if args.nominate is None:
+        return None
+    if not args.dense:
+        return "--nominate names the songs that the dense arithmetic then scores; it needs --dense"
+    if args.max_fa is not None:
+        return "--nominate cannot be combined with --max-fa: the background statistics come from the fp32 dense pass"
+    if args.top > 1:
+        return "--nominate gives one answer per window; it cannot be combined with --top %d" % args.top
+    if not 1 <= args.nominate <= 64:
+        return "--nominate lists 1..64 songs per window"
+    if several:
+        return "--nominate rescoring runs on ONE GPU against the whole database; song-sharded multi-GPU is not supported (unset PFANN_GPUS)"
+    return None
+
+
 def parse_args(argv):
     ap = argparse.ArgumentParser(prog=os.path.basename(argv[0]), description="what played when in long recordings")
     ap.add_argument("recordings", help="text file with one recording (16-bit PCM WAV) per line")
@@ -241,6 +276,9 @@ def parse_args(argv):
     ap.add_argument("--max-fa", type=float, default=None,
                     help="with --dense: a window counts when the chance that its best score is a chance alignment is at most X "
                          "(0 < X <= 1), judged from the window's own background; replaces --min-score")
+    ap.add_argument("--nominate", type=int, default=None, metavar="N",
+                    help="with --dense: the fp16 MFMA names N songs per window (1..64), only those are scored exactly; "
+                         "<result-stem>_nominate.csv says which windows are certified to be --dense's")
     return ap.parse_args(argv[1:])
 
 
@@ -251,6 +289,10 @@ def main(argv=None):
     if several and not args.dense:                       # (only the dense matcher merges song shards: pfann_amd/dist.py)
         print("monitor: a recording is matched on ONE GPU against the whole database; song-sharded multi-GPU monitor mode "
               "is not supported (unset PFANN_GPUS)", file=sys.stderr)
+        return 2
+    refused = check_nominate(args, several)
+    if refused is not None:
+        print("monitor: " + refused, file=sys.stderr)
         return 2
     if args.hop < 1 or (args.window is not None and args.window < 1):
         print("monitor: --window and --hop are positive numbers of segments", file=sys.stderr)
@@ -308,8 +350,10 @@ def main(argv=None):
     stem = os.path.splitext(args.result)[0]
     n_windows = n_det = 0
     with open(args.result if rank0 else os.devnull, "w", encoding="utf8", newline="\n") as fout, \
-            open(stem + "_windows.csv" if rank0 else os.devnull, "w", encoding="utf8", newline="\n") as fwin:
-        wcsv = csv.writer(fwin)
+            open(stem + "_windows.csv" if rank0 else os.devnull, "w", encoding="utf8", newline="\n") as fwin, \
+            open(stem + "_nominate.csv" if rank0 and args.nominate is not None else os.devnull, "w", encoding="utf8", newline="\n") as fnom:
+        wcsv, ncsv = csv.writer(fwin), csv.writer(fnom)
+        ncsv.writerow(NOMINATE_HEADER)
         wcsv.writerow(WINDOWS_HEADER + (["rank", "votes"] if args.top > 1 else []) + (["log10_fa"] if args.max_fa is not None else []))
 
         def launch(items):
@@ -319,7 +363,9 @@ def main(argv=None):
                 emb = torch.cat([e for _, _, e in good])
                 rlen = [n for _, n, _ in good]
                 rstart = np.concatenate([[0], np.cumsum(rlen)[:-1]])
-                if args.dense:
+                if args.nominate is not None:
+                    p = db.monitor_nominate_launch(emb, rstart, rlen, window, args.hop, args.nominate, edge_window=edge_window)
+                elif args.dense:
                     p = db.monitor_dense_launch(emb, rstart, rlen, window, args.hop, edge_window=edge_window,
                                                 stats=args.max_fa is not None)
                 elif args.top > 1:
@@ -331,8 +377,11 @@ def main(argv=None):
         def finish(launched):
             nonlocal n_windows, n_det
             items, good, p = launched
-            fa = {}
-            if p is not None and args.max_fa is not None:
+            fa, cert = {}, {}
+            if p is not None and args.nominate is not None:
+                rows, close, sure = db.monitor_nominate_finish(p)
+                per, cert = dict(zip([i for i, _, _ in good], rows)), dict(zip([i for i, _, _ in good], zip(close, sure)))
+            elif p is not None and args.max_fa is not None:
                 rows, log10_fa = db.monitor_dense_stats_finish(p)
                 per, fa = dict(zip([i for i, _, _ in good], rows)), dict(zip([i for i, _, _ in good], log10_fa))
             elif p is not None and args.top > 1:
@@ -345,8 +394,11 @@ def main(argv=None):
                 if n == 0:
                     fout.write("%s\terror\n" % name)
                     wcsv.writerow([name, "error", "", "", -1e999, 0] + ([0.0] if args.max_fa is not None else []))
+                    ncsv.writerow([name, "error", -1, 0])
                     continue
                 rows = per[i]
+                if args.nominate is not None:
+                    ncsv.writerows(nominate_csv(name, rows, *cert[i]))
                 if args.top > 1:
                     wcsv.writerows(ranked_window_csv(name, rows, seg_step_s, db.songList))
                     n_windows += len(rows)
