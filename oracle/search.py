@@ -56,8 +56,21 @@ def flat_ip_topk_f16(query, db, k):
     I = np.full((nq, k), -1, dtype=np.int64)
     if n == 0:
         return D, I
-    s = q16 @ x16.T
     kk = min(k, n)
+    if nq * n > (1 << 24) and kk < n:
+        # big cases: the same list by selection (a stable argsort of 513 x 262,200 scores took 20 s).  Everything above the
+        # k-th score, then the LOWEST rows that tie with it -- what the stable sort keeps --, in blocks of query rows
+        for m0 in range(0, nq, 64):
+            s = q16[m0:m0 + 64] @ x16.T
+            kth = -np.partition(-s, kk - 1, axis=1)[:, kk - 1]
+            for r in range(s.shape[0]):
+                above = np.flatnonzero(s[r] > kth[r])
+                rows = np.concatenate([above, np.flatnonzero(s[r] == kth[r])[:kk - above.size]])
+                rows = rows[np.lexsort((rows, -s[r, rows]))]
+                D[m0 + r, :kk] = s[r, rows]
+                I[m0 + r, :kk] = rows
+        return D, I
+    s = q16 @ x16.T
     order = np.argsort(-s, axis=1, kind="stable")[:, :kk]
     D[:, :kk] = np.take_along_axis(s, order, axis=1)
     I[:, :kk] = order

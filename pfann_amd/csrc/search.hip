@@ -82,9 +82,13 @@ __global__ __launch_bounds__(256, 2) void scan_emit_kernel(ScanParams p) {
     unsigned aoff[AR];
 #pragma unroll
     for (int i = 0; i < AR; ++i) aoff[i] = (unsigned)(rowq + 32 * i) * (unsigned)p.d * 4u;
-    int lkap = col4 * 4, lrow = rowq;        // lrow: row (inside the run) of this thread's first A row
+    // lk0: first k of the cursor's K tile.  The cursor moves to the next query tile when the K TILE passes d -- for every
+    // thread at once: a thread whose own k (lk0 + 4 col4) passes d sooner, in the last K tile of a d % 32 != 0, loads
+    // zeros there and must not run ahead into the next query tile of the run (QT > 1)
+    int lk0 = 0, lrow = rowq;                // lrow: row (inside the run) of this thread's first A row
     unsigned lbase = 0;                      // byte offset of the cursor's query tile
     auto load_tile = [&]() {
+        const int lkap = lk0 + col4 * 4;
         const bool kok = lkap < p.d;
 #pragma unroll
         for (int i = 0; i < AR; ++i)
@@ -92,9 +96,9 @@ __global__ __launch_bounds__(256, 2) void scan_emit_kernel(ScanParams p) {
 #pragma unroll
         for (int j = 0; j < BR; ++j)
             rb[j] = buf_load4(srd_db[j], (kok && doff[j] != BUF_OOB) ? doff[j] + (unsigned)lkap * 4u : BUF_OOB);
-        lkap += BK;
-        const bool wrap = lkap >= p.d;
-        lkap = wrap ? col4 * 4 : lkap;
+        lk0 += BK;
+        const bool wrap = lk0 >= p.d;
+        lk0 = wrap ? 0 : lk0;
         lrow += wrap ? BM : 0;
         lbase += wrap ? tile_bytes : 0u;
     };

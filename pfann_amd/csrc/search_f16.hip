@@ -135,19 +135,22 @@ __global__ __launch_bounds__(256, 2) void scan_f16_kernel(ScanParams p) {
     unsigned aoff[AR];
 #pragma unroll
     for (int i = 0; i < AR; ++i) aoff[i] = (unsigned)(rowq + 32 * i) * row_bytes;
-    unsigned lkb = (unsigned)col4 * 16u;     // byte offset of this thread's 16-byte piece inside the row
+    // lk0: byte offset of the cursor's K tile inside the row; the cursor moves to the next query tile when the K TILE passes
+    // the row's end, for every thread at once (see scan_emit_kernel: row_bytes % 128 != 0 with QT > 1)
+    unsigned lk0 = 0;
     int lrow = rowq;
     unsigned lbase = 0;
     auto load_tile = [&]() {
+        const unsigned lkb = lk0 + (unsigned)col4 * 16u;     // this thread's 16-byte piece inside the row
         const bool kok = lkb < row_bytes;
 #pragma unroll
         for (int i = 0; i < AR; ++i)
             ra[i] = buf_load4(srd_q, (kok && lrow + 32 * i < q_rows_left) ? lbase + aoff[i] + lkb : BUF_OOB);
 #pragma unroll
         for (int j = 0; j < BR; ++j) rb[j] = buf_load4(srd_db[j], (kok && doff[j] != BUF_OOB) ? doff[j] + lkb : BUF_OOB);
-        lkb += 128u;
-        const bool wrap = lkb >= row_bytes;
-        lkb = wrap ? (unsigned)col4 * 16u : lkb;
+        lk0 += 128u;
+        const bool wrap = lk0 >= row_bytes;
+        lk0 = wrap ? 0u : lk0;
         lrow += wrap ? BM : 0;
         lbase += wrap ? tile_bytes : 0u;
     };

@@ -65,7 +65,9 @@ def masked_topk(q, db, k, lo, hi, kind, label_base=0):
     for a, b in sorted(set(zip(lo.tolist(), hi.tolist()))):
         rows = np.flatnonzero((lo == a) & (hi == b))
         rest = np.concatenate([db[:a], db[b:]])
-        Dg, Ig = fn(q[rows], rest, k)
+        # (big groups: the argpartition form of the same definition, as tests/test_gpu_parity.py _check_topk takes it)
+        big = kind == "f32" and rows.size * rest.shape[0] > (1 << 24)
+        Dg, Ig = (osr.flat_ip_topk_blas if big else fn)(q[rows], rest, k)
         Ig = np.where(Ig >= a, Ig + (b - a), Ig)
         D[rows] = Dg
         I[rows] = np.where(Ig >= 0, Ig + label_base, -1)

@@ -10,6 +10,7 @@ import pytest
 import make_golden as mg
 from encoder_tap_cases import signature as plan_signature
 from pfann_amd import synth
+import search_kernel_cases as skc
 from score_bits import assert_canonical_topk, rescoring_path
 
 pytestmark = pytest.mark.gpu
@@ -439,11 +440,8 @@ def _check_topk(torch, db, q, k, prefilter=True, path=None, kernels=()):
     return D, I
 
 
-@pytest.mark.parametrize("n,d,nq,k", [
-    (0, 128, 3, 10), (7, 128, 19, 100), (5000, 128, 19, 100), (8192, 64, 5, 1), (8193, 16, 33, 20),
-    (100000, 128, 19, 100), (300000, 128, 130, 100), (140000, 128, 64, 300), (200000, 64, 40, 1000),
-])
-@pytest.mark.parametrize("prefilter", [True, False])
+@pytest.mark.parametrize("n,d,nq,k", skc.EXACT_SHAPES)
+@pytest.mark.parametrize("prefilter", skc.EXACT_PREFILTER)
 def test_search_topk_exact(torch_cuda, n, d, nq, k, prefilter):
     db = synth.unit_rows(11, "t/db%d" % n, max(n, 1), d)[:n]
     q = synth.unit_rows(12, "t/q%d" % n, nq, d)
@@ -456,21 +454,23 @@ def test_search_topk_exact(torch_cuda, n, d, nq, k, prefilter):
 def test_search_topk_clustered_and_duplicate_rows(torch_cuda):
     """Non-iid db: long runs of near-identical rows (one 'song') and exact duplicates; the
     sampled thresholds must stay valid lower bounds (never lose a true top-k row)."""
-    d, n = 128, 120000
+    small, both, both_f32 = skc.CLUSTERED
+    d, n, k = small.d, small.n, small.k
     base = synth.unit_rows(21, "t/cl", n, d)
     c = synth.unit_rows(22, "t/center", 1, d)
     base[40000:40600] = c + 0.05 * base[40000:40600]       # 600 rows around one centre
     base[70000:70300] = base[70000]                        # 300 exact duplicates
     base /= np.linalg.norm(base, axis=1, keepdims=True)
-    q = np.concatenate([c, base[70000:70001], synth.unit_rows(23, "t/q", 17, d)]).astype(np.float32)
-    _check_topk(torch_cuda, base.astype(np.float32), q, 100)
+    q = np.concatenate([c, base[70000:70001], synth.unit_rows(23, "t/q", small.nq - 2, d)]).astype(np.float32)
+    _check_topk(torch_cuda, base.astype(np.float32), q, k)
     # batched (fp16 pre-filter) form of the same, both ways
-    qb = np.concatenate([q, synth.unit_rows(24, "t/qb", 120, d)]).astype(np.float32)
-    _check_topk(torch_cuda, base.astype(np.float32), qb, 100, True)
-    _check_topk(torch_cuda, base.astype(np.float32), qb, 100, False)
+    qb = np.concatenate([q, synth.unit_rows(24, "t/qb", both.nq - small.nq, d)]).astype(np.float32)
+    assert (both.storage, both_f32.storage, both_f32.nq) == ("copy", "f32", both.nq)
+    _check_topk(torch_cuda, base.astype(np.float32), qb, k, True)
+    _check_topk(torch_cuda, base.astype(np.float32), qb, k, False)
 
 
-@pytest.mark.parametrize("n,d,nq,k", [(40000, 128, 1100, 100), (70001, 64, 1030, 20), (150000, 128, 2100, 300)])
+@pytest.mark.parametrize("n,d,nq,k", skc.LARGE_BATCH_SHAPES)
 def test_search_topk_large_batch_sublists(torch_cuda, n, d, nq, k):
     """nq >= 1024 takes the query-stationary fp16 scan (survivors in per-slice sub-lists, gathered
     by the select kernel); same exact answer, including a ragged last query tile and db tile."""
@@ -481,7 +481,7 @@ def test_search_topk_large_batch_sublists(torch_cuda, n, d, nq, k):
     _check_topk(torch_cuda, db.astype(np.float32), q.astype(np.float32), k, True)
 
 
-@pytest.mark.parametrize("n,d,nq", [(250007, 128, 33), (250007, 128, 76), (250007, 128, 304), (250007, 128, 1000), (130001, 64, 200)])
+@pytest.mark.parametrize("n,d,nq", skc.MID_BATCH_SHAPES)
 def test_search_topk_mid_batch_takes_the_query_stationary_kernels(torch_cuda, n, d, nq):
     """Round 6: 33 .. 1023 query rows (one to eight query tiles) run the sampled group-maximum pass + the full pass with
     sub-lists too -- up to 64 db slices per query tile, three tile buffers where the launch leaves most of the chip empty
@@ -497,10 +497,10 @@ def test_search_topk_mid_batch_takes_the_query_stationary_kernels(torch_cuda, n,
     # (three tile buffers: at most 256 workgroups in the sampled pass, fewer than 768 in the full pass on 64-row db tiles)
     kernels = {128: ["scan_f16_qres_kernel<8, true, 128, %d>" % (3 if nq <= 304 else 2), "scan_f16_qres_kernel<8, false, 64, 3>"],
                64: ["scan_f16_qres_kernel<4, true, 128, 2>", "scan_f16_qres_kernel<4, false, 128, 2>"]}[d]
-    _check_topk(torch_cuda, db.astype(np.float32), q.astype(np.float32), 100, True, "gmax", kernels)
+    _check_topk(torch_cuda, db.astype(np.float32), q.astype(np.float32), skc.MID_BATCH_K, True, "gmax", kernels)
 
 
-@pytest.mark.parametrize("nq", [130, 2100])
+@pytest.mark.parametrize("nq", skc.PRIVATE_LISTS_NQ)
 def test_search_topk_private_lists_take_whole_songs(torch_cuda, nq):
     """Round 6: the query-stationary scan keeps four PRIVATE survivor lists per (query row, db slice) -- one per owner lane --
     instead of one list behind an LDS counter, and hands groups of four consecutive db rows to the four owners in turn.  A db
@@ -508,7 +508,7 @@ def test_search_topk_private_lists_take_whole_songs(torch_cuda, nq):
     64-row tile: they must spread over the private lists (no list overflow -> no exact fallback -> the fp32 scores come from
     the select's own re-scoring) and the answer is the exact top-k, for one query tile (64 slices, lists of 32) and for
     seventeen."""
-    d, n, k = 128, 150000, 100
+    d, n, k = skc.PRIVATE_LISTS[0].d, skc.PRIVATE_LISTS[0].n, skc.PRIVATE_LISTS[0].k
     db = synth.unit_rows(61, "t/pl", n, d)
     for s0 in range(0, n, 40):
         db[s0:s0 + 40] = db[s0] + 0.05 * db[s0:s0 + 40]
@@ -522,7 +522,7 @@ def test_search_topk_private_lists_take_whole_songs(torch_cuda, nq):
 def test_search_topk_sublist_overflow_falls_back(torch_cuda):
     """More near-identical rows inside ONE interleaved db slice than a sub-list holds (256 at 32
     slices): the rows that lost survivors are recomputed exactly by the device-side fallback kernel."""
-    d, n, nq = 128, 60000, 1100
+    d, n, nq = skc.SUBLIST_OVERFLOW.d, skc.SUBLIST_OVERFLOW.n, skc.SUBLIST_OVERFLOW.nq
     db = synth.unit_rows(43, "t/of", n, d)
     c = synth.unit_rows(44, "t/ofc", 1, d)
     for u in range(3):                                   # db tiles 5, 37, 69 all belong to slice 5 of 32
@@ -532,16 +532,16 @@ def test_search_topk_sublist_overflow_falls_back(torch_cuda):
     q = synth.unit_rows(45, "t/ofq", nq, d)
     q[:3] = c + 0.05 * q[:3]
     q /= np.linalg.norm(q, axis=1, keepdims=True)
-    _check_topk(torch_cuda, db.astype(np.float32), q.astype(np.float32), 300, True)
+    _check_topk(torch_cuda, db.astype(np.float32), q.astype(np.float32), skc.SUBLIST_OVERFLOW.k, True)
 
 
-@pytest.mark.parametrize("nq", [80, 1100])
+@pytest.mark.parametrize("nq", skc.BIG_CLUSTER_NQ)
 def test_search_topk_more_than_4096_survivors(torch_cuda, nq):
     """5000 near-identical rows all clear the sampled threshold of the queries that match them: those
     rows' survivor lists (> 4096, < 8192 entries) are left to the large select kernel, the others go
     through the 256-thread one; both in the same call (nq = 1100 additionally overflows the per-slice
     sub-lists and takes the one-list-per-row rescan)."""
-    d, n = 128, 100000
+    d, n = skc.BIG_CLUSTER[0].d, skc.BIG_CLUSTER[0].n
     db = synth.unit_rows(51, "t/big", n, d)
     c = synth.unit_rows(52, "t/bigc", 1, d)
     db[20000:25000] = c + 0.003 * db[20000:25000]
@@ -549,7 +549,7 @@ def test_search_topk_more_than_4096_survivors(torch_cuda, nq):
     q = synth.unit_rows(53, "t/bigq", nq, d)
     q[:5] = c + 0.05 * q[:5]
     q /= np.linalg.norm(q, axis=1, keepdims=True)
-    _check_topk(torch_cuda, db.astype(np.float32), q.astype(np.float32), 100, True)
+    _check_topk(torch_cuda, db.astype(np.float32), q.astype(np.float32), skc.BIG_CLUSTER[0].k, True)
 
 
 @pytest.mark.parametrize("case", range(8))
@@ -572,7 +572,7 @@ def test_search_prefilter_near_ties_stay_exact(torch_cuda):
     """Adversarial for the fp16 pre-filter: thousands of rows whose exact scores differ by ~1e-6
     (far below fp16 resolution, 1e-3) around the k-th best.  The re-scoring window (2 eps below
     the k-th best approximate score) must hand the exact fp32 order to the final sort."""
-    d, n, nq = 128, 60000, 96
+    d, n, nq = skc.NEAR_TIES.d, skc.NEAR_TIES.n, skc.NEAR_TIES.nq
     base = synth.unit_rows(31, "t/tie", n, d).astype(np.float64)
     c = synth.unit_rows(32, "t/tiec", 1, d).astype(np.float64)[0]
     for lo, cnt, amp in ((1000, 3000, 0.02), (20000, 500, 0.002)):
@@ -581,7 +581,8 @@ def test_search_prefilter_near_ties_stay_exact(torch_cuda):
     q = synth.unit_rows(33, "t/tieq", nq, d).astype(np.float64)
     q[:40] = c + 0.05 * q[:40]
     q /= np.linalg.norm(q, axis=1, keepdims=True)
-    D, I = _check_topk(torch_cuda, base.astype(np.float32), q.astype(np.float32), 100, True)
+    assert skc.NEAR_TIES.k == 100
+    D, I = _check_topk(torch_cuda, base.astype(np.float32), q.astype(np.float32), skc.NEAR_TIES.k, True)
     # the interesting rows really are inside the fp16 ambiguity: k-th and (k+50)-th exact scores
     s = np.sort((q[:1].astype(np.float32) @ base.astype(np.float32).T)[0])[::-1]
     assert s[99] - s[149] < 1e-3
@@ -594,7 +595,8 @@ def test_search_small_batch_sublist_overflow_device_fallback(torch_cuda):
     row's 32 sub-lists (256 slots each), and 9000 rows tying EXACTLY at the top overflow every list of their query
     row.  Both rows are recomputed exactly by the device-side fallback kernel (no host retry, no error); exact ties
     resolve to ascending row ids like the oracle's stable sort."""
-    d, n = 64, 1000000
+    first, again = skc.SMALL_OVERFLOW
+    d, n = first.d, first.n
     rng = np.random.default_rng(61)
     db = rng.standard_normal((n, d)).astype(np.float32)
     c = rng.standard_normal((2, d)).astype(np.float32)
@@ -603,22 +605,24 @@ def test_search_small_batch_sublist_overflow_device_fallback(torch_cuda):
         lo = 70001 + u * 32 * 32
         db[lo] = c[1] + 0.01 * db[lo]
     db /= np.linalg.norm(db, axis=1, keepdims=True)
-    q = np.concatenate([c, rng.standard_normal((17, d)).astype(np.float32)])
+    q = np.concatenate([c, rng.standard_normal((first.nq - 2, d)).astype(np.float32)])
     q /= np.linalg.norm(q, axis=1, keepdims=True)
-    D, I = _check_topk(torch_cuda, db, q.astype(np.float32), 300)
+    assert (first.k, again.nq) == (300, first.nq - 2)
+    D, I = _check_topk(torch_cuda, db, q.astype(np.float32), first.k)
     assert np.array_equal(I[0, :300], np.arange(50000, 50300))          # exact ties -> lowest rows first
     # the same handle semantics again: the per-row flags were cleared by the fallback kernel
-    _check_topk(torch_cuda, db, q[2:].astype(np.float32), 100)
+    _check_topk(torch_cuda, db, q[2:].astype(np.float32), again.k)
 
 
-@pytest.mark.parametrize("prefilter", [True, False])
+@pytest.mark.parametrize("prefilter", skc.TAIL_LAUNCH_PREFILTER)
 def test_search_small_batch_d128_tail_launch(torch_cuda, prefilter):
     """d = 128, nq <= 32: the five-launch small-batch path (query preparation inside the group-maximum pass, select,
     then ONE launch for the big select and the exact fallback).  Query row 0: 5000 near-identical rows (more than 4096
     survivors: the big-select half of the tail launch); row 1: 9000 rows tying exactly at the top (every sub-list
     overflows: the fallback half, exact ties -> ascending row ids); row 2: 900 near-identical rows 32 tiles apart (one
     sub-list overflows); the rest ordinary rows through the 256-thread select."""
-    d, n = 128, 600000
+    first, again = skc.TAIL_LAUNCH[prefilter]
+    d, n = first.d, first.n
     rng = np.random.default_rng(71)
     db = rng.standard_normal((n, d)).astype(np.float32)
     c = rng.standard_normal((3, d)).astype(np.float32)
@@ -629,13 +633,14 @@ def test_search_small_batch_d128_tail_launch(torch_cuda, prefilter):
         if lo < n:
             db[lo] = c[2] + 0.01 * db[lo]
     db /= np.linalg.norm(db, axis=1, keepdims=True)
-    q = np.concatenate([c, rng.standard_normal((16, d)).astype(np.float32)])
+    q = np.concatenate([c, rng.standard_normal((first.nq - 3, d)).astype(np.float32)])
     q[0] = c[0] + 0.05 * q[3]
     q /= np.linalg.norm(q, axis=1, keepdims=True)
-    D, I = _check_topk(torch_cuda, db, q.astype(np.float32), 300, prefilter)
+    assert (first.k, again.nq) == (300, first.nq - 3)
+    D, I = _check_topk(torch_cuda, db, q.astype(np.float32), first.k, prefilter)
     assert np.array_equal(I[1, :300], np.arange(50000, 50300))
     # the flags the tail launch cleared: the same handle again, ordinary rows only
-    _check_topk(torch_cuda, db, q[3:].astype(np.float32), 100, prefilter)
+    _check_topk(torch_cuda, db, q[3:].astype(np.float32), again.k, prefilter)
 
 
 def test_search_small_batch_fp16_storage_fallback_d128(torch_cuda):
@@ -643,13 +648,13 @@ def test_search_small_batch_fp16_storage_fallback_d128(torch_cuda):
     fallback half of the combined tail launch streams the fp16 rows (its ELT = 2 form) and returns the lowest row ids."""
     from oracle import search as osr
     from pfann_amd.database import DeviceIndex
-    d, n, k = 128, 300000, 300
+    d, n, k = skc.F16_FALLBACK_D128.d, skc.F16_FALLBACK_D128.n, skc.F16_FALLBACK_D128.k
     rng = np.random.default_rng(91)
     db = rng.standard_normal((n, d)).astype(np.float32)
     c = rng.standard_normal((1, d)).astype(np.float32)
     db[50000:59000] = c[0]
     db /= np.linalg.norm(db, axis=1, keepdims=True)
-    q = np.concatenate([c, rng.standard_normal((6, d)).astype(np.float32)])
+    q = np.concatenate([c, rng.standard_normal((skc.F16_FALLBACK_D128.nq - 1, d)).astype(np.float32)])
     q = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
     idx = DeviceIndex(d, 0, storage="f16")
     idx.load(db, np.array([0, n], np.int64), 0)
@@ -664,12 +669,12 @@ def test_search_small_batch_fp16_storage_fallback_d128(torch_cuda):
 
 def test_search_all_scores_tie_zero_query(torch_cuda):
     """q = 0: every row scores 0, the survivor lists overflow at any threshold; exact answer = rows 0..k-1."""
-    d, n = 128, 30000
+    d, n = skc.ZERO_QUERY[0].d, skc.ZERO_QUERY[0].n
     db = synth.unit_rows(64, "t/zq", n, d).astype(np.float32)
-    for nq in (3, 100):
+    for nq in skc.ZERO_QUERY_NQ:
         q = np.zeros((nq, d), np.float32)
         q[-1] = db[77]
-        D, I = _check_topk(torch_cuda, db, q, 50)
+        D, I = _check_topk(torch_cuda, db, q, skc.ZERO_QUERY[0].k)
         assert np.array_equal(I[0], np.arange(50)) and I[-1, 0] == 77
 
 
@@ -677,7 +682,8 @@ def test_search_prefilter_margin_scales_with_norms(torch_cuda):
     """The fp16 pre-filter's margin must hold for non-unit rows too: db rows of norm ~40 and queries of norm
     ~25 with thousands of exact scores 1e-3 relative apart around the k-th best; and a query row far outside
     fp16's range (norm 3e5) is answered exactly through the fallback instead of through inf/NaN halves."""
-    d, n, nq = 128, 60000, 96
+    d, n, nq = skc.MARGIN_NORMS.d, skc.MARGIN_NORMS.n, skc.MARGIN_NORMS.nq
+    assert skc.MARGIN_NORMS.k == 100
     base = synth.unit_rows(71, "t/ms", n, d).astype(np.float64)
     c = synth.unit_rows(72, "t/msc", 1, d).astype(np.float64)[0]
     base[1000:4000] = c + 0.02 * base[1000:4000]
@@ -705,26 +711,23 @@ def test_search_prefilter_margin_scales_with_norms(torch_cuda):
         assert np.abs(D[r] - got).max() < 4 * tol
 
 
-@pytest.mark.parametrize("n,d,nq,k", [(7, 128, 19, 100), (5000, 128, 19, 100), (100000, 128, 19, 100),
-                                      (90000, 64, 1, 20), (150000, 128, 130, 100), (70001, 64, 1100, 100),
-                                      (40000, 128, 40, 300)])
-def test_search_fp16_storage(torch_cuda, n, d, nq, k):
-    """fp16-only storage (pfann_db_set_storage(db, PFANN_DB_F16)): the result is the top-k by
-    s16 = sum fl16(q_i) fl16(x_i) -- against the oracle's float64 evaluation of exactly that (scores to fp32
-    summation rounding; label sets identical except ties at the k-th score) on every regime (small-batch
-    streaming kernel, generic and query-stationary batched kernels)."""
+def _check_topk_f16(torch, db, q, k, path=None, kernels=(), want=None):
+    """fp16-only storage: the device's top-k against the oracle's float64 evaluation of s16 = sum fl16(q_i) fl16(x_i) (scores
+    to fp32 summation rounding; label sets identical except ties at the k-th score).  path / kernels: what the plan of the
+    call must say; want: the oracle's (Dr, Ir) where it is at hand.  -> (D, I, the index)"""
     from oracle import search as osr
     from pfann_amd.database import DeviceIndex
-    db = synth.unit_rows(81, "t/h%d" % n, n, d).astype(np.float32)
-    q = synth.unit_rows(82, "t/hq%d" % n, nq, d)
-    q[::3] = db[(np.arange(len(q[::3])) * 7919) % n] * 0.8 + 0.2 * q[::3]
-    q = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
+    n, d = db.shape
+    nq = q.shape[0]
     idx = DeviceIndex(d, 0, storage="f16")
     idx.load(db, np.array([0, n], np.int64), 0)
     assert idx.lib.pfann_db_bytes(idx.handle) == n * d * 2
-    D, I = idx.search(torch_cuda.as_tensor(q).cuda(), k)
+    stages, flags = idx.search_plan(nq, k)
+    assert path is None or flags["path"] == path, flags
+    assert not [kn for kn in kernels if kn not in [s[0] for s in stages]], stages
+    D, I = idx.search(torch.as_tensor(q).cuda(), k)
     D, I = D.cpu().numpy(), I.cpu().numpy()
-    Dr, Ir = osr.flat_ip_topk_f16(q, db, k)
+    Dr, Ir = want if want is not None else osr.flat_ip_topk_f16(q, db, k)
     kk = min(k, n)
     assert (I[:, kk:] == -1).all() and (I[:, :kk] >= 0).all()
     assert (np.diff(D[:, :kk], axis=1) <= 0).all()
@@ -735,6 +738,20 @@ def test_search_fp16_storage(torch_cuda, n, d, nq, k):
         a, b = set(I[r, :kk].tolist()), set(Ir[r, :kk].tolist())
         for lab in a ^ b:
             assert abs(float(x16[lab] @ q16[r]) - Dr[r, kk - 1]) < 2e-6, "row %d label %d not a k-th tie" % (r, lab)
+    return D, I, idx
+
+
+@pytest.mark.parametrize("n,d,nq,k", skc.F16_STORAGE_SHAPES)
+def test_search_fp16_storage(torch_cuda, n, d, nq, k):
+    """fp16-only storage (pfann_db_set_storage(db, PFANN_DB_F16)): the result is the top-k by
+    s16 = sum fl16(q_i) fl16(x_i) -- against the oracle's float64 evaluation of exactly that (scores to fp32
+    summation rounding; label sets identical except ties at the k-th score) on every regime (small-batch
+    streaming kernel, generic and query-stationary batched kernels)."""
+    db = synth.unit_rows(81, "t/h%d" % n, n, d).astype(np.float32)
+    q = synth.unit_rows(82, "t/hq%d" % n, nq, d)
+    q[::3] = db[(np.arange(len(q[::3])) * 7919) % n] * 0.8 + 0.2 * q[::3]
+    q = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
+    _check_topk_f16(torch_cuda, db, q, k)
 
 
 def test_match_on_fp16_storage_uses_stored_rows(torch_cuda):
@@ -910,7 +927,8 @@ def test_search_chunks_large_query_batches(torch_cuda):
     """pfann_search_topk walks batches above 16384 rows in chunks (bounded survivor workspace)."""
     from oracle import search as osr
     from pfann_amd.database import DeviceIndex
-    d, n, nq = 16, 3000, 16384 + 700
+    d, n, nq = skc.QUERY_CHUNKS.d, skc.QUERY_CHUNKS.n, skc.QUERY_CHUNKS.nq
+    assert (nq, skc.QUERY_CHUNKS.k) == (16384 + 700, 5)
     db = synth.unit_rows(71, "t/cdb", n, d)
     q = synth.unit_rows(72, "t/cq", nq, d)
     idx = DeviceIndex(d, 0)
@@ -971,14 +989,15 @@ def test_winner_keys_pack_and_pick_vs_numpy_statement(torch_cuda):
             assert (got["shift"][j], got["song"][j], got["offset"][j]) == b[1:], j
 
 
-@pytest.mark.parametrize("storage", ["f32", "f16"])
+@pytest.mark.parametrize("storage", skc.TWO_PHASE_STORAGE)
 def test_two_phase_sharded_search_is_the_exact_global_topk(torch_cuda, storage):
     """pfann_search_bound on every shard -> MAX over the shards -> pfann_search_topk_bounded -> pfann_topk_merge equals
     the search over the unsplit db (labels and scores), each shard's bound is a true lower bound of its k-th best, and no
     shard emits a row below the reduced bound."""
     torch = torch_cuda
     from pfann_amd.database import DeviceIndex
-    d, n, nq, k = 128, 150000, 2100, 100
+    cuts = skc.TWO_PHASE["cuts"]                      # three uneven shards
+    d, n, nq, k = skc.TWO_PHASE["d"], cuts[-1], skc.TWO_PHASE["nq"], skc.TWO_PHASE["k"]
     db = synth.unit_rows(71, "t/2p", n, d)
     # songs: runs of 40 similar consecutive rows, so that true matches cluster inside one shard
     for s0 in range(0, n, 40):
@@ -989,7 +1008,6 @@ def test_two_phase_sharded_search_is_the_exact_global_topk(torch_cuda, storage):
     q /= np.linalg.norm(q, axis=1, keepdims=True)
     db_t = torch.from_numpy(db.astype(np.float32)).cuda()
     q_t = torch.from_numpy(q.astype(np.float32)).cuda()
-    cuts = [0, 50000, 90000, n]                       # three uneven shards
     pos_all = np.array([0, n], np.int64)
     whole = DeviceIndex(d, 0, storage=storage)
     whole.load(db_t, pos_all, 0)
@@ -1005,7 +1023,7 @@ def test_two_phase_sharded_search_is_the_exact_global_topk(torch_cuda, storage):
         own = ix.reduce_bound(c[None], k)
         Dl, _ = ix.search(q_t, k)                                 # complete local list (also clears the pending state)
         assert bool((own <= Dl[:, k - 1] + 1e-6).all()), "a shard's bound exceeds its true k-th best"
-    m = min(k, 2 * k // len(shards) + 8)                          # what dist.py exchanges
+    m = skc.bound_m(k, len(shards))                               # what dist.py exchanges
     cands = torch.stack([ix.search_bound(q_t, k, m) for ix in shards])       # one pending bound per handle
     L = whole.reduce_bound(cands, k)
     assert bool((L <= D0[:, k - 1] + 1e-6).all()), "the reduced bound exceeds the true global k-th best"

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import search_excl_cases as sx
+import search_kernel_cases as skc
 
 pytestmark = pytest.mark.gpu
 
@@ -76,30 +77,7 @@ def queries(db, pos, nq, mode):
     return np.ascontiguousarray(db[rows]), lo, hi
 
 
-CASES = [
-    # name, n, d, nq, k, storage, path, a masked kernel the plan must hold
-    ("small_dense", 300, 128, 5, 10, "copy", "small_dense", "scan_small_kernel<128, 4, 2, true>"),
-    ("small_dense_d64", 300, 64, 5, 10, "copy", "small_dense", "scan_small_kernel<64, 4, 2, true>"),
-    ("folded_nq1", 12288, 128, 1, 100, "copy", "small_sampled_folded", "scan_small_kernel<128, 2, 0, true>"),
-    ("folded_nq19", 12288, 128, 19, 100, "copy", "small_sampled_folded", "select_tail_kernel<4, true>"),
-    ("sampled_d64_nq1", 12288, 64, 1, 100, "copy", "small_sampled", "scan_small_kernel<64, 2, 1, true>"),
-    ("sampled_d64_nq19", 12288, 64, 19, 100, "copy", "small_sampled", "scan_small_kernel<64, 2, 0, true>"),
-    ("gmax_nq33", 40000, 128, 33, 100, "copy", "gmax", "scan_f16_qres_kernel<8, true, 128, 3, true>"),
-    ("gmax_nq130", 40000, 128, 130, 100, "copy", "gmax", "scan_f16_qres_kernel<8, false, 64, 3, true>"),
-    ("gmax_d64", 40000, 64, 130, 100, "copy", "gmax", "scan_f16_qres_kernel<4, true, 128, 2, true>"),
-    ("ladder_f16", 20000, 128, 130, 100, "copy", "ladder_f16", "scan_f16_kernel<1, true>"),
-    ("ladder_f16_k200", 20000, 128, 130, 200, "copy", "ladder_f16", "scan_f16_qres_kernel<8, false, 128, 2, true>"),
-    # fp32 rows only.  nq = 19 at d = 128 is the small path on the fp32 streaming kernels (the plan says so); the ladder
-    # itself takes <= 32 query rows only at another d
-    ("f32_nq19", 20000, 128, 19, 100, "f32", "small_sampled_folded", "scan_small_kernel<128, 4, 0, true>"),
-    ("ladder_f32_nq19", 20000, 96, 19, 100, "f32", "ladder_f32", "scan_emit_kernel<32, 128, 32, 32, 1, true>"),
-    ("ladder_f32_nq50", 20000, 128, 50, 100, "f32", "ladder_f32", "scan_emit_kernel<64, 64, 32, 32, 1, true>"),
-    ("ladder_f32_nq130", 20000, 128, 130, 100, "f32", "ladder_f32", "scan_emit_kernel<128, 128, 64, 64, 1, true>"),
-    ("f16_small", 300, 128, 5, 10, "f16", "small_dense", "scan_small_kernel<128, 2, 2, true>"),
-    ("f16_sampled", 12288, 128, 19, 100, "f16", "small_sampled_folded", "select_tail_kernel<2, true>"),
-    ("f16_batched", 40000, 128, 130, 100, "f16", "gmax", "topk_fallback_kernel<2, true>"),
-    ("f16_ladder", 20000, 128, 130, 200, "f16", "ladder_f16", "scan_f16_kernel<1, true>"),
-]
+CASES = skc.EXCL_CASES           # name, n, d, nq, k, storage, path, a masked kernel the plan must hold
 
 
 @pytest.mark.parametrize("mode", ["run", "spread"])
@@ -125,16 +103,7 @@ def test_own_song_excluded(torch_cuda, case, mode):
     assert np.array_equal(In.cpu().numpy(), I0) and np.array_equal(Dn.cpu().numpy().view(np.int32), D0.view(np.int32))
 
 
-# The group-maximum pass samples every gs-th row, gs = the coarsest of 4, 2, 1 that leaves 4 tiles of 128 sampled rows per
-# slice (search_plan.h).  With one to five query tiles there are 64 slices, so gs = 4 from n = 131,072 rows, gs = 2 from
-# 65,536, and the 40,000-row shapes above all run at gs = 1.  The plan text does not print the stride, so these shapes
-# come from that rule; what the text does show, the kernel, is asserted.  A million-row database runs at gs = 4.
-STRIDED = [
-    # name, n, d, nq, modes, the masked sampled pass
-    ("stride2_nbuf3", 70000, 128, 130, ("run",), "scan_f16_qres_kernel<8, true, 128, 3, true>"),
-    ("stride2_d64", 70000, 64, 130, ("run",), "scan_f16_qres_kernel<4, true, 128, 2, true>"),
-    ("stride4_nbuf2", 140000, 128, 600, ("run",), "scan_f16_qres_kernel<8, true, 128, 2, true>"),
-]
+STRIDED = skc.EXCL_STRIDED       # name, n, d, nq, modes, the masked sampled pass (the shapes' rule: the registry)
 
 
 @pytest.mark.parametrize("case", STRIDED, ids=[c[0] for c in STRIDED])
@@ -143,7 +112,7 @@ def test_sampled_pass_with_a_row_stride(torch_cuda, case):
     that the sampled rows straddle must still lower the threshold by exactly its own rows.  The five-tile case is also the
     only one on the two-buffer form of the d = 128 sampled pass."""
     name, n, d, nq, modes, kern = case
-    k = 100
+    k = skc.EXCL_STRIDED_K
     db, pos = world(n, d)
     idx = make_index(db, "copy")
     kind = plan_of(idx, nq, k, "gmax", [kern])

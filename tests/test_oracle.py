@@ -348,6 +348,23 @@ def test_canonical_topk_window_matches_brute_force(d, n, k, scale):
     assert np.abs(D[:, :kk] - D64[:, :kk]).max() <= 2 * search.canon_window(q, x).max()
 
 
+def test_flat_ip_topk_f16_selects_what_the_stable_sort_keeps():
+    """Above 2^24 scores flat_ip_topk_f16 selects instead of sorting every row: the same lists as the stable argsort of the
+    definition, on exact ties across the k-th place (300 copies of one row, a query that is that row; an all-zero query:
+    every row ties) and ordinary rows."""
+    rng = np.random.default_rng(1)
+    db = rng.standard_normal((60000, 64)).astype(np.float32)
+    db[100:400] = db[100]
+    q = rng.standard_normal((300, 64)).astype(np.float32)
+    q[1], q[2] = 0.0, db[100]
+    assert q.shape[0] * db.shape[0] > (1 << 24)
+    D, I = search.flat_ip_topk_f16(q, db, 100)
+    s = q.astype(np.float16).astype(np.float64) @ db.astype(np.float16).astype(np.float64).T
+    order = np.argsort(-s, axis=1, kind="stable")[:, :100]
+    assert np.array_equal(I, order) and np.array_equal(D, np.take_along_axis(s, order, axis=1))
+    assert np.array_equal(I[1], np.arange(100)) and np.array_equal(I[2], np.arange(100, 200))
+
+
 # ------------------------------------------------------------------ a2: the float64 statement of every mode (tests/mel_cases.py)
 def _melspec_f64_before_generalisation(x, params, bank=None):
     """oracle.melspec.melspec_f64 as it stood while it stated the default mode only, kept here operation for operation:

@@ -3,8 +3,10 @@
 The expected plans do not come from the code under test: profiles/search_plan/parent_launches.json is a rocprofv3 kernel
 trace (tools/search_plan_trace.py) of the commit BEFORE the plan existed, one entry per API call -- the kernels the old
 dispatch launched, with grid, workgroup size and dynamic LDS bytes.  The plan must print exactly that list for every
-entry.  Every kernel instantiation search_topk can reach appears in at least one entry; the one class no machine can run
-(a sampling stride beyond the 2 GB tile window, shards of ~268 M rows and more) is checked here from the plan alone."""
+entry.  Every kernel of the UNMASKED search (the first three lists of search_plan.h) is launched in at least one entry;
+the one class no machine can run (a sampling stride beyond the 2 GB tile window, shards of ~268 M rows and more) is
+checked here from the plan alone.  This covers launches only: that every instantiation, the masked twins included, also
+has a case that checks what it COMPUTES against an exact reference is tests/test_search_kernel_coverage.py's to prove."""
 import json
 import os
 import subprocess
