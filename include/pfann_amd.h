@@ -139,7 +139,7 @@ typedef struct pfann_wav_info {
     int64_t n_frames;      /* per channel */
     int64_t data_pos;      /* byte offset of the samples in the file */
     int32_t n_ch;
-    int32_t sample_rate;
+    uint32_t sample_rate;  /* as the header states it, unsigned like the `wave` module reads it; 0 and absurd rates included */
     int32_t status;
     int32_t reserved;
 } pfann_wav_info;

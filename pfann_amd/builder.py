@@ -102,7 +102,7 @@ def _decode(dataset, i, pool, native_rate):
     return view, sr, buf
 
 
-_WAV_INFO = np.dtype([("n_frames", "<i8"), ("data_pos", "<i8"), ("n_ch", "<i4"), ("sample_rate", "<i4"), ("status", "<i4"),
+_WAV_INFO = np.dtype([("n_frames", "<i8"), ("data_pos", "<i8"), ("n_ch", "<i4"), ("sample_rate", "<u4"), ("status", "<i4"),
                       ("reserved", "<i4")])
 _WAV_ERR = {-1: "cannot open the file", -2: "not a RIFF/WAVE file, or fmt/data chunk missing", -3: "not PCM",
             -4: "wave stream currently only supports 16bit wav", -5: "read error"}
@@ -202,7 +202,7 @@ def _native_groups(engine, dataset, hop, batch_windows, pool, workers, rank=0, w
                         lib.pfann_wav_probe(arr, m, workers, more.ctypes.data_as(ctypes.POINTER(_l.WavInfo)))
                         n_out = more["n_frames"].copy()
                         for j in np.nonzero((more["status"] == 0) & (more["sample_rate"] != native))[0]:
-                            if more["n_frames"][j] == 0 or more["sample_rate"][j] <= 0:
+                            if more["n_frames"][j] == 0 or not 0 < more["sample_rate"][j] <= resample.MAX_RATE:
                                 more["status"][j] = -2            # the reference's resampler raises on an empty signal
                             else:
                                 n_out[j] = resample.piece_plan(int(more["n_frames"][j]), int(more["sample_rate"][j]), native)[1]

@@ -53,7 +53,7 @@ void probe_one(const char *path, pfann_wav_info *o) {
             if (size < 16 || pos + (int64_t)take > fsize || !read_full(fd, h, take, pos)) break;
             uint16_t tag = rd16(h);
             o->n_ch = rd16(h + 2);
-            o->sample_rate = (int32_t)rd32(h + 4);
+            o->sample_rate = rd32(h + 4);
             const uint16_t bits = rd16(h + 14);
             if (tag == 0xFFFE && take >= 26) tag = rd16(h + 24);          // WAVE_FORMAT_EXTENSIBLE: the sub-format's tag
             if (tag != 1 || o->n_ch < 1) { o->status = PFANN_WAV_ECODEC; close(fd); return; }

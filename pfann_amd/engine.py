@@ -220,7 +220,7 @@ class Engine:
         n = p.shape[0]
         if sample_rate is not None and int(sample_rate) != int(self.params["sample_rate"]) and n:
             from . import resample
-            key = resample.reduced_rates(sample_rate, self.params["sample_rate"])
+            key = resample.reduced_rates(resample.check_rate(sample_rate), self.params["sample_rate"])
             if key not in self._resample_tables:
                 tab, old, new, width = resample.filter_table(*key)
                 self._resample_tables[key] = (torch.from_numpy(tab).to(self.device), old, new, width)

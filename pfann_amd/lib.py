@@ -3,7 +3,7 @@ if the library is missing or no MI355X is visible, the product path raises."""
 import ctypes
 import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int16, c_int32, c_int64,
-                    c_longlong, c_void_p)
+                    c_longlong, c_uint32, c_void_p)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libpfann_amd.so")
@@ -28,7 +28,7 @@ class MatchResult(Structure):
 
 
 class WavInfo(Structure):
-    _fields_ = [("n_frames", c_int64), ("data_pos", c_int64), ("n_ch", c_int32), ("sample_rate", c_int32),
+    _fields_ = [("n_frames", c_int64), ("data_pos", c_int64), ("n_ch", c_int32), ("sample_rate", c_uint32),
                 ("status", c_int32), ("reserved", c_int32)]
 
 

@@ -11,7 +11,18 @@ import numpy as np
 import torch
 
 ZEROS, ROLLOFF = 24, 0.945
+# The highest file rate that is resampled (DXD masters: 705,600 and 768,000 Hz); a header that states 0 or more than this
+# (0x80000000 in a damaged file) is a load error, i.e. a 0-segment song, before any table is sized from it.
+MAX_RATE = 768000
 _cache = {}
+
+
+def check_rate(file_sr):
+    """-> int(file_sr), or ValueError for a rate no table is built for (<= 0 or above MAX_RATE)."""
+    file_sr = int(file_sr)
+    if file_sr <= 0 or file_sr > MAX_RATE:
+        raise ValueError("sample rate %d Hz outside 1..%d" % (file_sr, MAX_RATE))
+    return file_sr
 
 
 def reduced_rates(file_sr, sr):
